@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the ADMM projection hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config resnet50_tt]
+    python bench.py --gpus N --steps K --warmup W [--config resnet50_tt] [--full] [--dump-outputs DIR]
 
 One *step* = one ADMM projection iteration over every compressed layer of the rank table
 (ADMM.update(update_u=True) semantics: Z <- proj(W+U), U += W-Z, ||W-Z||^2).  Inputs are synthetic
 (N(0, 2/fan_in), seed 0) and resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds what takes runs of
+its own: the instrumented roofline pass (roofline, phases_ms, lanes, filter, roofline_other), per-layer timings, the
+forward block, weak scaling (N > 1) and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step handed
+its caller (Z and U of every layer, per-layer ||W-Z||^2) as DIR/<name>.npy, before any of the `--full` measurements.
+
 `--gpus N` with N > 1 and no torch.distributed environment starts the N ranks itself (a child
 `python -m torch.distributed.run ... bench.py`, before this process touches the GPU).  At N > 1 `value` is ONE
 table's iterations/s with its layers sharded over the ranks (strong scaling, BASELINE.json north_star; the only
-collective is one RCCL all-reduce of the scalar residual per step); the throughput of N tables, one per rank, is
-reported beside it under `weak_scaling`.
+collective is one RCCL all-reduce of the scalar residual per step); with `--full`, the throughput of N tables, one per
+rank, is reported beside it under `weak_scaling`.
 
 Prints ONE JSON line on rank 0.
 """
@@ -41,6 +46,11 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="resnet50_tt")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline (roofline pass, per-layer, forward, weak "
+                         "scaling, CPU baseline); the --no-* switches below thin out a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write Z, U and the per-layer residuals of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-per-layer", action="store_true")
@@ -81,6 +91,43 @@ def layer_entries(model, hp, fmt, dev):
         entries.append(e)
         names.append(name)
     return entries, names
+
+
+DUMP_BYTES = 48 << 20      # --dump-outputs budget; a larger table's Z and U are sampled down to it
+
+
+def dump_samples(numels, budget=DUMP_BYTES):
+    """Per layer of the whole table: None (keep every element) or the sorted flat indices of a fixed sample, seeded by the
+    layer's position in the table.  Z and U (float32 each) share the indices; the sample does not depend on the rank count."""
+    total = sum(numels)
+    frac = (budget - 8 * len(numels)) / (8.0 * total)
+    if frac >= 1.0:
+        return [None] * len(numels)
+    import numpy as np
+    return [np.sort(np.random.default_rng(i).choice(n, max(1, int(frac * n)), replace=False)) for i, n in enumerate(numels)]
+
+
+def dump_outputs(out_dir, names, layers, mine, resid, dev, rank, dist):
+    """--dump-outputs: what the last timed step handed its caller -- `<name>.Z` and `<name>.U` of every layer (float32, flat;
+    a fixed sample past DUMP_BYTES) and `residual_sq` (float64 ||W-Z||^2 per layer, table order) -- as out_dir/*.npy.
+    `layers` holds the whole table (dicts with W), `mine` this rank's indices into it, `resid` its plan's residuals."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    samples = dump_samples([L["W"].numel() for L in layers])
+    for i in mine:
+        idx = None if samples[i] is None else torch.from_numpy(samples[i]).to(layers[i]["W"].device)
+        for key in ("Z", "U"):
+            flat = layers[i][key].reshape(-1)
+            v = flat if idx is None else flat.index_select(0, idx)
+            np.save(os.path.join(out_dir, f"{names[i]}.{key}.npy"), v.cpu().numpy().astype(np.float32))
+    full = torch.zeros(len(layers), dtype=torch.float64, device=dev)
+    if mine:
+        full[torch.tensor(mine, device=dev)] = resid
+    if dist is not None:
+        dist.all_reduce(full)
+    if rank == 0:
+        np.save(os.path.join(out_dir, "residual_sq.npy"), full.cpu().numpy())
 
 
 def cpu_baseline(config, max_seconds=30.0):
@@ -250,6 +297,8 @@ def bench_tucker(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t[0])
     ms_per_step = 1e3 * el / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, names, layers, mine, plan.resid_sq if plan is not None else None, dev, rank, dist)
     its, errs = plan.iterations() if plan is not None else ([], [])
     fl = [tucker_flops(layers[i]["W"].shape, layers[i]["ranks"], its[j]) for j, i in enumerate(mine)]
     mfma_able = sum(f["mfma"] for f in fl)
@@ -273,7 +322,7 @@ def bench_tucker(args):
                              "note": "Gram + mode-product FLOPs of HOSVD, the HOOI sweeps each layer actually ran and Z / "
                                      "ms_per_step / fp32 MFMA peak; 0.46 M weights: the configuration is launch- and "
                                      "latency-bound (SURVEY 8d config 2)"}
-    if rank == 0 and plan is not None and not args.no_roofline:
+    if args.full and rank == 0 and plan is not None and not args.no_roofline:
         plan.enable_timing(True)
         reps, acc = max(3, min(args.steps, 10)), None
         for _ in range(reps):
@@ -295,7 +344,7 @@ def bench_tucker(args):
                     "HIP-event time of the launch on the launch stream.  The launches are latency-bound (30 workgroups on 256 "
                     "CUs, a dependent chain inside each): the fraction says how little of the chip the configuration can use"}
         out["phases_ms"] = {"eig_ms": eig_ms, "total_ms_instrumented": acc["total_ms"] / reps}
-    if rank == 0 and world == 1 and not args.no_per_layer:
+    if args.full and rank == 0 and world == 1 and not args.no_per_layer:
         seen, per_layer = {}, []
         for i, L in enumerate(layers):
             sig = (tuple(L["W"].shape), tuple(L["ranks"]))
@@ -326,7 +375,7 @@ def bench_tucker(args):
             seen[sig] = rec
             per_layer.append(rec)
         out["per_layer_svd_gflops"] = per_layer
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.config)
     if rank == 0:
         print(json.dumps(out))
@@ -435,6 +484,8 @@ def main():
     mine = parts[rank]
     plan = make_plan(entries, mine)
     elapsed = timed(plan)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, names, entries, mine, plan.resid_sq if plan is not None else None, dev, rank, dist)
     resid_headline = float(total_resid[0])
     ms_per_step = 1e3 * elapsed / args.steps
     iters_per_s = args.steps / elapsed
@@ -471,7 +522,7 @@ def main():
                              "note": "Gram + projection + chain GEMM FLOPs of one iteration (SURVEY 8d) / ms_per_step / "
                                      "fp32 MFMA peak: the whole-sweep figure north_star's 40 % target refers to"}
 
-    if rank == 0 and plan is not None and not args.no_roofline:
+    if args.full and rank == 0 and plan is not None and not args.no_roofline:
         # instrumented pass: HIP events around each phase on the launch stream, and around every launch of the
         # dominant kernel (adds syncs, so it is separate from the timed region above)
         plan.enable_timing(True)
@@ -567,7 +618,7 @@ def main():
         }
 
     # ---- per-layer SVD GFLOP/s: every distinct layer shape projected ALONE (own single-layer plan) ----
-    if rank == 0 and world == 1 and not args.no_per_layer:
+    if args.full and rank == 0 and world == 1 and not args.no_per_layer:
         seen, per_layer = {}, []
         for i, e in enumerate(entries):
             sig = (tuple(e["W"].shape), tuple(e.get("tt_shapes") or ()), str(e["ranks"]))
@@ -595,7 +646,7 @@ def main():
         out["per_layer_svd_gflops"] = per_layer
 
     # ---- weak scaling beside the headline: N tables of the configuration, table r seeded r on rank r ----
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         if plan is not None:
             plan.close()
         del plan
@@ -607,7 +658,7 @@ def main():
                                "ms_per_step": 1e3 * wel / args.steps,
                                "note": "one table per rank (table r seeded r), no data-path collective, same K/W"}
     # ---- hot path B: forward of the factorised layers against the dense layers they replace (tadmm/fwdbench.py)
-    if rank == 0 and world == 1 and not args.no_forward:
+    if args.full and rank == 0 and world == 1 and not args.no_forward:
         from tadmm import fwdbench
         rows = fwdbench.run(dev)
         head = next((r for r in rows if "qkv" in r["layer"] and r["dtype"] == "bf16" and "roofline" in r), None)
@@ -617,7 +668,7 @@ def main():
                                   "which at these sizes are host-bound on both sides (~20 us of dispatch around 10-40 us "
                                   "kernels) and measure Python overhead; roofline = chain kernel alone, executed bf16 MFMA flops",
                           "layers": rows, "roofline": None if head is None else head["roofline"]}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.config)
     if rank == 0:
         print(json.dumps(out))

@@ -5,6 +5,6 @@ CFG=$1; shift
 for rnd in 1 2 3; do
   for s in "$@"; do
     echo -n "$s : "
-    env $s python bench.py --config $CFG --no-cpu-baseline --no-forward --no-per-layer 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), d.get('filter'))"
+    env $s python bench.py --config $CFG --full --no-cpu-baseline --no-forward --no-per-layer 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), d.get('filter'))"
   done
 done

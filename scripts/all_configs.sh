@@ -4,8 +4,8 @@
 # The files are copied to profiles/ by hand after the run (gpurun_out/ is scratch).
 TAG=${1:-r03}
 for c in resnet50_tt resnet18_tt deit_small_tt resnet32_tk; do
-  extra=""
-  [ "$c" != "resnet50_tt" ] && extra="--no-forward"
+  extra="--full"
+  [ "$c" != "resnet50_tt" ] && extra="--full --no-forward"
   python bench.py --config $c $extra > gpurun_out/${TAG}_bench_$c.json 2> gpurun_out/${TAG}_bench_$c.err || { tail -5 gpurun_out/${TAG}_bench_$c.err; exit 1; }
   python - $c gpurun_out/${TAG}_bench_$c.json <<'PY'
 import json, sys

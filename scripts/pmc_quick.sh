@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/run -- python3 $R/bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-roofline > /dev/null 2> $OUT/err.log
+rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/run -- python3 $R/bench.py --steps 2 --warmup 2 --full --no-cpu-baseline --no-roofline > /dev/null 2> $OUT/err.log
 cd $R && python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections, os
 out = sys.argv[1]

@@ -10,10 +10,9 @@ d = json.load(open("gpurun_out/r03_ab_g$g.json")); print("guard=$g ms_per_step",
 PY
 done
 for sd in 1 0; do
-  TADMM_SMALL_DIRECT=$sd python bench.py --config resnet32_tk --no-cpu-baseline --no-per-layer > gpurun_out/r03_ab_tk$sd.json 2> gpurun_out/r03_ab_tk$sd.err
-  python - <<PY
-import json
-d = json.load(open("gpurun_out/r03_ab_tk$sd.json")); print("direct=$sd tk ms_per_step", d["ms_per_step"], d["hooi_sweeps"]["max"], d.get("roofline", {}).get("avg_launch_us"), d.get("roofline", {}).get("launches_per_step"))
-PY
+  TADMM_SMALL_DIRECT=$sd python bench.py --config resnet32_tk --full --no-cpu-baseline --no-per-layer 2>/dev/null | python -c "
+import json,sys
+d = json.loads(sys.stdin.read()); r = d.get('roofline', {})
+print('direct=$sd tk ms_per_step', d['ms_per_step'], d['hooi_sweeps']['max'], r.get('avg_launch_us'), r.get('launches_per_step'))"
 done
 bash scripts/chain_trace.sh resnet50_tt layer4.1.conv2 chain_l4b > /dev/null; head -32 gpurun_out/chain_l4b/seq.txt

@@ -436,3 +436,14 @@ def test_tucker_flop_model():
     per = 2.0 * 64 * 9 * 64 * 23 + 2.0 * (9 * 23) * 64 * 64 + 2.0 * 64 * 9 * 64 * 25 + 2.0 * (9 * 25) * 64 * 64 + 2.0 * 25 * 9 * 64 * 23
     final = 2.0 * 25 * 9 * 23 * 64 + 2.0 * 64 * 25 * 9 * 64
     assert abs(f["mfma"] - (hosvd + 3 * per + final)) < 1.0
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    import bench
+    numels = [2359296, 1048576, 36864, 9408]
+    a, b = bench.dump_samples(numels, budget=4 << 20), bench.dump_samples(numels, budget=4 << 20)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))                    # seeded: the same indices every run
+    assert 8 * sum(len(x) for x in a) + 8 * len(numels) <= 4 << 20            # Z and U float32 + the residuals
+    for x, n in zip(a, numels):
+        assert len(x) >= 1 and x[-1] < n and np.all(np.diff(x) > 0)
+    assert bench.dump_samples([1000, 10]) == [None, None]                     # a small table is written whole
