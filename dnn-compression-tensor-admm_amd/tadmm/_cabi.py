@@ -141,6 +141,8 @@ ABI = {
     "tadmm_eigh_scratch_bytes": (C.c_size_t, [C.c_int]),
     "tadmm_eigh_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.POINTER(C.c_int), C.c_void_p]),
+    "tadmm_eigh_partial_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.POINTER(C.c_int), C.c_void_p]),
     "tadmm_dgemm_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_dgemm3_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_dgemm3_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

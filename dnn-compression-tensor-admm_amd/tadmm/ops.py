@@ -630,6 +630,24 @@ def eigh(G: torch.Tensor):
     return ev, vec, int(sweeps.value)
 
 
+def eigh_partial(G: torch.Tensor, r: int):
+    """Leading r pairs of a symmetric PSD G (descending), as the plans solve them.  Returns (evals (r,),
+    evecs (r,N) rows, route): route 0 = direct solver, 1 = single-launch Jacobi, 2 = Jacobi tournament."""
+    assert G.dtype == torch.float64 and G.is_cuda and G.dim() == 2 and G.shape[0] == G.shape[1]
+    G = G.contiguous()
+    h = Handle.get(G.device.index)
+    lib = h.lib
+    N = G.shape[0]
+    ev = torch.empty(max(r, 1), dtype=torch.float64, device=G.device)
+    vec = torch.empty(max(r, 1), N, dtype=torch.float64, device=G.device)
+    sb = lib.tadmm_eigh_scratch_bytes(N)
+    scratch = torch.empty(sb, dtype=torch.uint8, device=G.device)
+    route = C.c_int(-1)
+    h.check(lib.tadmm_eigh_partial_f64(h.ptr, G.data_ptr(), N, int(r), ev.data_ptr(), vec.data_ptr(),
+                                       scratch.data_ptr(), sb, C.byref(route), _stream(G.device)))
+    return ev, vec, int(route.value)
+
+
 # ------------------------------------------------------------------ filtered eigen-solver building blocks (tests)
 def dgemm(a: torch.Tensor, b: torch.Tensor, b_transposed: bool = True) -> torch.Tensor:
     """fp64 matrix-core GEMM: a (M,K) @ b^T with b (N,K) (b_transposed) or a @ b with b (K,N); row-major float64."""

@@ -284,12 +284,21 @@ int tadmm_gram_ld(int m, int n, int* Npad, int* ld);
 int tadmm_gram_f64(tadmm_handle h, const float* A, int m, int n, double* G, int ldg,
                    void* partial_dev, size_t partial_bytes, void* stream);
 
-/* Symmetric eigen-decomposition of double[N][N] G (row-major, symmetric PSD) by one-sided block
- * Jacobi.  evals_out: double[N] descending; evecs_out: double[N][N], row j = eigenvector j.
- * Synchronous (polls convergence).  scratch: tadmm_eigh_scratch_bytes(N). */
+/* Symmetric eigen-decomposition of double[N][N] G (row-major, symmetric PSD) by the route the plans take:
+ * N <= 64 the direct solver (Householder tridiagonalisation, bisection, inverse iteration), with one-sided
+ * Jacobi in one launch for whatever it does not certify; larger N the Jacobi tournament kernels.
+ * evals_out: double[N] descending; evecs_out: double[N][N], row j = eigenvector j (zero where the eigenvalue
+ * is at most 1e-12 of the largest).  Synchronous.  scratch: tadmm_eigh_scratch_bytes(N).
+ * *sweeps_out: 0 when the direct route solved it. */
 size_t tadmm_eigh_scratch_bytes(int N);
 int tadmm_eigh_f64(tadmm_handle h, const double* G, int N, double* evals_out, double* evecs_out,
                    void* scratch_dev, size_t scratch_bytes, int* sweeps_out, void* stream);
+/* The same solve for the leading r pairs only (1 <= r <= N, as the plans run it): evals_out double[r],
+ * evecs_out double[r][N].  *route_out (nullable): 0 = direct route certified the result, 1 = single-launch
+ * Jacobi (jacobi_small_kernel), 2 = Jacobi tournament (N > 64, or any N with TADMM_EIGH_TICK=1).
+ * scratch: tadmm_eigh_scratch_bytes(N). */
+int tadmm_eigh_partial_f64(tadmm_handle h, const double* G, int N, int r, double* evals_out, double* evecs_out,
+                           void* scratch_dev, size_t scratch_bytes, int* route_out, void* stream);
 
 /* ---- building blocks of the filtered eigen-solver (csrc/dgemm.hip, csrc/chol.hip), exposed for tests ---- */
 /* C[M][N] = A[M][K] * B^T (b_transposed=1: B is [N][K]) or A * B (b_transposed=0: B is [K][N]); row-major fp64 on
