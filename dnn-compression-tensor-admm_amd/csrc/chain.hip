@@ -265,7 +265,34 @@ int launch_fused_ks(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t 
   }
 }
 
+// The fused chain on channels-first images (1x1 SVD convolutions): the image loader of the single entries feeds product
+// 1, the image epilogue writes product 2 through the wave-private staging area (NB2 = 6 feature tiles take two passes of
+// it in three of the four variants).  Token tiles may straddle image boundaries: every pixel is addressed through
+// elem_off, and 16-byte vectors are used only where x_hw / y_hw are multiples of the vector width (d.x_vec / d.y_vec).
+template <int KS2T>
+int launch_fused_img(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
+  if (dtype == 1) {
+    if (tile_tokens == 64) return launch_variant<1, 64, 128, 6, KS2T, uint16_t, uint16_t, true, true, true>(d, s);
+    return launch_variant<1, 32, 128, 6, KS2T, uint16_t, uint16_t, true, true, true>(d, s);
+  }
+  if (tile_tokens == 32) return launch_variant<3, 32, 128, 6, KS2T, float, float, true, true, true>(d, s);
+  return launch_variant<3, 64, 64, 3, KS2T, float, float, true, true, true>(d, s);
+}
+
 }  // namespace
+
+// Fused chain with image input and image output of the same plane size (tadmm_svdconv_fwd / _bwd).  -1 when the shape
+// does not fit (the caller validated it already).
+int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
+  if (d.T <= 0) return 0;
+  if (!d.fused || d.x_hw <= 0 || d.y_hw != d.x_hw || d.R % 64 || d.R > 256) return -1;
+  switch (d.R / 32) {
+    case 2: return launch_fused_img<2>(d, dtype, tile_tokens, s);
+    case 4: return launch_fused_img<4>(d, dtype, tile_tokens, s);
+    case 6: return launch_fused_img<6>(d, dtype, tile_tokens, s);
+    default: return launch_fused_img<8>(d, dtype, tile_tokens, s);
+  }
+}
 
 // dtype 0: fp32 in/out through three bf16 planes per operand; dtype 1: bf16 in/out.  Returns 0, or -1 when the shape
 // does not fit the kernel (the caller reports it; there is no other path inside the library).

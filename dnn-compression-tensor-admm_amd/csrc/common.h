@@ -179,6 +179,7 @@ struct ChainDesc {
   long long* stamps;                            // debugging: per-workgroup cycle stamps (nullable)
 };
 int launch_tt_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s);
+int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s);   // fused, image in / out
 
 // factorised convolution of a small image in one launch (convchain.hip): 1x1 / chain-in, k x k core, 1x1 / chain-out
 struct ConvChainDesc {

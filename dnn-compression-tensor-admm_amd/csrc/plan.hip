@@ -1361,9 +1361,17 @@ int tadmm_gemm_bf16_nt(tadmm_handle h, const void* A, const void* Bt, void* C, i
 }
 
 // ---- forward chains of the factorised layers (chain.hip) ----
-static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, const char* who, void* stream_) {
+static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, const char* who, void* stream_,
+                       bool svdconv = false) {
   DeviceGuard device_guard(h);
   if (!h || !c) return TADMM_ERR_INVALID;
+  if (svdconv) {   // 1x1 SVD convolution: NCHW in, NCHW out, one plane size, T = batch * plane
+    if (c->x_hw <= 0 || c->y_hw != c->x_hw)
+      CTX_FAIL(h, TADMM_ERR_INVALID, "svdconv: x_hw and y_hw must both equal the pixels of one image plane (H*W > 0)");
+    if (c->T % c->x_hw) CTX_FAIL(h, TADMM_ERR_INVALID, "svdconv: T must be batch * H*W (a whole number of planes)");
+    if (c->R % 64 || c->R > 256)
+      CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "svdconv: middle rank must be padded to a multiple of 64, at most 256 (larger ranks take two tadmm_tucker_1x1 launches)");
+  }
   if (!c->X || !c->Y || !c->Win || (fused && !c->Wout)) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: null operand");
   if (c->T < 0 || c->Kin <= 0 || c->R <= 0 || (fused && c->Nout <= 0)) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: bad shape");
   if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: bad dtype");
@@ -1394,8 +1402,9 @@ static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, con
   const int nfeat = fused ? c->Nout : c->R;
   if (c->y_hw > 0) d.y_vec = (c->y_hw % epl == 0 && (((uintptr_t)c->Y) & 15) == 0) ? 1 : 0;
   else d.y_vec = (c->ldy % epl == 0 && nfeat % epl == 0 && (((uintptr_t)c->Y) & 15) == 0) ? 1 : 0;
-  if (launch_tt_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_) != 0)
-    CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "chain: token tile does not fit the LDS");
+  const int rc = svdconv ? launch_svdconv_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_)
+                         : launch_tt_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_);
+  if (rc != 0) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "chain: token tile does not fit the LDS");
   HIP_OK(h, hipGetLastError());
   (void)who;
   return TADMM_OK;
@@ -1405,6 +1414,8 @@ int tadmm_ttlinear_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* s) { ret
 int tadmm_ttconv_chain_in(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 0, "ttconv_chain_in", s); }
 int tadmm_ttconv_chain_out(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 0, "ttconv_chain_out", s); }
 int tadmm_tucker_1x1(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 0, "tucker_1x1", s); }
+int tadmm_svdconv_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 1, "svdconv_fwd", s, true); }
+int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 1, "svdconv_bwd", s, true); }
 
 int tadmm_conv_chain_desc_bytes(void) { return (int)sizeof(tadmm_conv_chain_desc); }
 

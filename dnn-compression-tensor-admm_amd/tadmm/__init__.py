@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -19,6 +19,8 @@ def __getattr__(name):
         "TKConv2dC": ("tk_layers", "TKConv2dC"), "TKConv2dM": ("tk_layers", "TKConv2dM"),
         "TKConv2dR": ("tk_layers", "TKConv2dR"), "TKLinearM": ("tk_layers", "TKLinearM"),
         "TKLinearR": ("tk_layers", "TKLinearR"),
+        "SVDConv2dR": ("svd_layers", "SVDConv2dR"), "SVDConv2dC": ("svd_layers", "SVDConv2dC"),
+        "SVDConv2dM": ("svd_layers", "SVDConv2dM"),
     }
     if name in table:
         mod, attr = table[name]

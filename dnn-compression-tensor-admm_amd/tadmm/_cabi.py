@@ -134,6 +134,8 @@ ABI = {
     "tadmm_ttconv_chain_in": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_ttconv_chain_out": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_tucker_1x1": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
+    "tadmm_svdconv_fwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
+    "tadmm_svdconv_bwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_gram_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_gram_ld": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tadmm_gram_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

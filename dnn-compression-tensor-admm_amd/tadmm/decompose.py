@@ -5,6 +5,11 @@ the factorised model, with exactly the keys the reference's layer classes regist
 The reference does this inside every layer constructor on the CPU (`dense_w=dense_dict[w_name]`); here all
 layers of the table are decomposed in ONE grouped device plan (TT / SVD) or by the device HOOI (Tucker), and
 every tensor that is not in the rank table is copied through unchanged (resnet_inet_tt.py:444-449).
+
+Entries with a single rank are SVD layers wherever they appear: the reference's model files build `SVDConv2dC` for a
+single-rank 1x1 convolution of a TT / Tucker table (resnet_inet_tt.py:44-51, densenet_inet_tt.py:47,152, vgg_tt.py:74),
+and the `svd` tables hold nothing else (mobilenetv2_cifar_tt.py:206-237, class chosen by `variant`).  The reference has
+no SVD linear layer, so a single-rank 2-D entry is refused.
 """
 from __future__ import annotations
 
@@ -14,6 +19,7 @@ import torch
 
 from . import ops, tucker
 from ._cabi import KIND_TT_CONV, KIND_TT_LINEAR
+from .svd_layers import svd_factors
 
 
 def _prefix(name: str) -> str:
@@ -30,10 +36,38 @@ def _split(tt_shapes, out_dim):
     raise AssertionError("tt_shapes do not factor the output dimension")
 
 
+def _single_rank(ranks) -> bool:
+    return isinstance(ranks, int) or len(ranks) == 1
+
+
+# state_dict keys of the SVD layer classes: (name of U (O, r), name of diag(s) V^T (r, I), 1x1 kernel shapes)
+_SVD_KEYS = {"R": ("left_factor", "right_factor", False), "C": ("right_kernel", "left_kernel", True),
+             "M": ("right_factor", "left_factor", False)}
+
+
+def _decompose_svd(dense, names, hp_dict, variant, device, out):
+    if variant not in _SVD_KEYS:
+        raise ValueError(f"svd variant must be 'R', 'C' or 'M' (got {variant!r})")
+    for name in names:
+        if dense[name].dim() != 4:
+            raise ValueError(f"{name}: single-rank {dense[name].dim()}-D entry; the reference has no SVD linear layer "
+                             "(SVDConv.py holds 1x1 convolutions only)")
+    if not names:
+        return
+    u_key, sv_key, kernel = _SVD_KEYS[variant]
+    facs = svd_factors([dense[n] for n in names], [hp_dict.ranks[n] for n in names], device)
+    for name, (u, sv) in zip(names, facs):
+        p = _prefix(name)
+        u, sv = u.cpu(), sv.cpu()
+        out[f"{p}{u_key}"] = u[:, :, None, None] if kernel else u
+        out[f"{p}{sv_key}"] = sv[:, :, None, None] if kernel else sv
+
+
 def decompose_state_dict(dense: Dict[str, torch.Tensor], hp_dict, format: str, variant: str = "M",
                          device=None) -> Dict[str, torch.Tensor]:
-    """format: 'tt' | 'tk'; variant: 'M' | 'R' | 'C' (TKConv2dC only) -- selects the layer class whose keys
-    are emitted.  Returns a new state_dict on the CPU."""
+    """format: 'tt' | 'tk' | 'svd'; variant: 'M' | 'R' | 'C' (TKConv2dC / SVDConv2dC) -- selects the layer class whose
+    keys are emitted.  Single-rank entries of a 'tt' / 'tk' table come out as SVDConv2dC keys.  Returns a new
+    state_dict on the CPU."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     out: Dict[str, torch.Tensor] = {}
@@ -41,6 +75,13 @@ def decompose_state_dict(dense: Dict[str, torch.Tensor], hp_dict, format: str, v
     for k, v in dense.items():
         if k not in hp_dict.ranks:
             out[k] = v.detach().cpu().clone()
+    if format == "svd":
+        _decompose_svd(dense, table, hp_dict, variant, device, out)
+        return out
+    if format in ("tt", "tk"):
+        single = [k for k in table if _single_rank(hp_dict.ranks[k])]
+        table = [k for k in table if not _single_rank(hp_dict.ranks[k])]
+        _decompose_svd(dense, single, hp_dict, "C", device, out)
     if format == "tt":
         layers, meta = [], []
         for name in table:

@@ -238,3 +238,64 @@ def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias:
         return ops.chain_fused(x.reshape(-1, x.shape[-1]), planes[0], planes[1], bias, w_out.shape[0],
                                memo=not fresh).reshape(*lead, w_out.shape[0])
     return _ChainFused.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes).reshape(*lead, w_out.shape[0])
+
+
+def _channel_major(t: torch.Tensor) -> torch.Tensor:
+    """(B, C, H, W) -> (C, B*H*W) float32 operand of a weight-gradient product."""
+    return _as_gemm_operand(t.permute(1, 0, 2, 3).reshape(t.shape[1], -1).float())
+
+
+class _Conv1x1Chain(torch.autograd.Function):
+    """y[b,:,p] = Wout (Win x[b,:,p]) + bias on NCHW images in one launch; Win (R, C), Wout (N, R), R <= 256."""
+
+    @staticmethod
+    def forward(ctx, x, w_in, w_out, bias, planes):
+        if not x.is_cuda:
+            raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
+        n = _nplanes(x)
+        fresh = planes is None
+        if fresh:
+            planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
+        y = ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
+        ctx.save_for_backward(x, w_in, w_out)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w_in, w_out = ctx.saved_tensors
+        g = g.contiguous()
+        n = _nplanes(g)
+        gx = gwi = gwo = gb = None
+        if ctx.needs_input_grad[0]:                 # dX = Win^T (Wout^T dY): the fused kernel on the transposed factors
+            gx = ops.svd_conv(g, planes_of(w_out, n, pad_rows=64, transpose=True),
+                              planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
+                              entry="tadmm_svdconv_bwd", memo=False)
+        if ctx.needs_input_grad[1]:                 # dWin = (Wout^T dY) X^T over all pixels
+            gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], entry="tadmm_tucker_1x1",
+                                  image_out=True, memo=False)
+            gwi = ops.mm(_channel_major(gr), _channel_major(x).t()).to(w_in.dtype)
+        if ctx.needs_input_grad[2]:                 # dWout = dY (Win X)^T over all pixels
+            h = ops.chain_single(x, planes_of(w_in, _nplanes(x)), None, w_in.shape[0], entry="tadmm_tucker_1x1",
+                                 image_out=True, memo=False)
+            gwo = ops.mm(_channel_major(g), _channel_major(h).t()).to(w_out.dtype)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            gb = g.sum((0, 2, 3))
+        return gx, gwi, gwo, gb, None
+
+
+def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None, planes=None):
+    """(B, C, H, W) -> (B, N, H, W): the 1x1 convolution with the rank-R factorisation Wout Win (SVDConv.py) as one launch
+    of the fused chain on the NCHW tensors in place (`tadmm_svdconv_fwd`).  Differentiable; the data gradient is one
+    `tadmm_svdconv_bwd` launch.  `planes`: prebuilt (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))."""
+    if x.dim() != 4:
+        raise ValueError("conv1x1_chain expects an NCHW image")
+    if not fused_rank_ok(w_in.shape[0]):
+        raise TadmmError(-5, f"conv1x1_chain: rank {w_in.shape[0]} does not fit the fused kernel (at most 256)")
+    if not _needs_grad(x, w_in, w_out, bias):         # inference: straight to the C ABI, no autograd node
+        fresh = planes is None
+        if fresh:
+            n = _nplanes(x)
+            planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
+        return ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
+    return _Conv1x1Chain.apply(x.contiguous(), w_in, w_out, bias, planes)

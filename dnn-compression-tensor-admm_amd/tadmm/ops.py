@@ -493,6 +493,27 @@ def chain_single(x, w_planes, bias, n_out: int, entry: str = "tadmm_ttconv_chain
     return _chain_call(entry, x, w_planes, None, bias, kin, n_out, 0, image_out, tile_tokens, prepare_only, memo)
 
 
+def svd_conv(x, win_planes, wout_planes, bias, n_out: int, entry: str = "tadmm_svdconv_fwd", tile_tokens: int = 0,
+             prepare_only: bool = False, memo: bool = True):
+    """y (B, n_out, H, W) = Wout (Win x[b,:,p]) + bias for every pixel of an NCHW image, in one launch, in place on both
+    sides (SVDConv.py: SVDConv2dC / SVDConv2dM at padding 0).  Planes as for `chain_fused`: `win_planes` with the rank
+    padded to a multiple of 64 (<= 256), `wout_planes` with `pad_cols=64`."""
+    if x.dim() != 4:
+        raise TadmmError(-1, "svd_conv: x must be an NCHW image")
+    return _chain_call(entry, x, win_planes, wout_planes, bias, x.shape[1], win_planes.shape[1] * 16, n_out, True,
+                       tile_tokens, prepare_only, memo)
+
+
+def svd_conv_pays(x: torch.Tensor, rank: int) -> bool:
+    """True when the one-launch 1x1 chain (`svd_conv`) is the path to take for a rank-`rank` 1x1 convolution of x; False:
+    two `tadmm_tucker_1x1` launches.  Measured (scripts/bench_svd_layers.py): in bf16 the fused
+    launch is faster on all 56 single-rank layers of svd_mobilenetv2_cifar / tk_resnet50 (1.06x - 2.3x); in fp32 (three
+    planes, six MFMA products per product, the rank padded to 64) the second product's padded work costs more than the
+    intermediate's round trip saves, and two launches are 4 - 17 % faster over each table.  Ranks above 256 never fit
+    the LDS of the fused kernel."""
+    return x.dtype == torch.bfloat16 and 0 < rank <= 256
+
+
 def _conv_chain_plan(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation):
     """(pixels per workgroup, output rows per workgroup, halo tiles, workgroups per image) of the one-launch factorised
     convolution, or None when it does not apply -- the rule tadmm_ttconv_fused applies."""

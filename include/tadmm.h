@@ -255,6 +255,14 @@ int tadmm_ttconv_chain_in(tadmm_handle h, const tadmm_chain_desc* d, void* strea
 int tadmm_ttconv_chain_out(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 /* TKConv2dC first / last 1x1 stage (TKConv.py:93-98): per-pixel channel mixing, single product. */
 int tadmm_tucker_1x1(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
+/* SVDConv2dC / SVDConv2dM forward (SVDConv.py: two 1x1 convolutions / two per-pixel linears, padding 0):
+ * y[b,:,p] = Wout (Win x[b,:,p]) + bias on NCHW images in place, one launch, the R-vector of a pixel in LDS.
+ * x_hw = y_hw = H*W, T = B*H*W, Kin = C_in, Nout = C_out; Win (R x C_in) / Wout (C_out x R) planes with the rank padded
+ * to R (multiple of 64, <= 256) as for tadmm_ttlinear_fwd.  Ranks above 256 are not served (two tadmm_tucker_1x1). */
+int tadmm_svdconv_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
+/* Its data gradient dX = Win^T (Wout^T dY): the same kernel with X = dY, Win = Wout^T planes (R x C_out),
+ * Wout = Win^T planes (C_in x R), bias NULL. */
+int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 
 /* The whole factorised convolution of a SMALL image in one launch (csrc/convchain.hip): y = W3 conv_kxk(W1 x; Wc) + bias
  * for NCHW tensors with output rows of at most 64 pixels: one workgroup per tile of output rows (<= 64 output pixels, a halo of
