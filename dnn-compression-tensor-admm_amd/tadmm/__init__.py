@@ -21,6 +21,7 @@ def __getattr__(name):
         "TKLinearR": ("tk_layers", "TKLinearR"),
         "SVDConv2dR": ("svd_layers", "SVDConv2dR"), "SVDConv2dC": ("svd_layers", "SVDConv2dC"),
         "SVDConv2dM": ("svd_layers", "SVDConv2dM"),
+        "append_double_l2_loss": ("orthogonal", "append_double_l2_loss"),
     }
     if name in table:
         mod, attr = table[name]

@@ -80,6 +80,13 @@ class ConvChainDesc(C.Structure):
 
 CHAIN_F32, CHAIN_BF16 = 0, 1
 
+
+class OrthDesc(C.Structure):
+    _fields_ = [
+        ("P", C.c_void_p), ("grad_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
+        ("ld", C.c_int64), ("gram_of_rows", C.c_int32), ("reserved", C.c_int32),
+    ]
+
 # name -> (restype, argtypes); this table IS the list of symbols include/tadmm.h declares
 ABI = {
     "tadmm_version": (C.c_int, []),
@@ -120,6 +127,12 @@ ABI = {
     "tadmm_penalty_scratch_doubles": (C.c_int, []),
     "tadmm_penalty": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tadmm_orth_desc_bytes": (C.c_int, []),
+    "tadmm_orth_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(OrthDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_orth_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OrthDesc), C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.POINTER(C.c_void_p)]),
+    "tadmm_orth_l2": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tadmm_orth_plan_destroy": (C.c_int, [C.c_void_p]),
     "tadmm_gemm_pack_bytes": (C.c_size_t, [C.c_int, C.POINTER(GemmDesc)]),
     "tadmm_gemm_pack": (C.c_int, [C.c_int, C.POINTER(GemmDesc), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "tadmm_gemm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -206,6 +219,8 @@ def load():
                                     f"bytes, binding {C.sizeof(ChainDesc)})")
         if lib.tadmm_conv_chain_desc_bytes() != C.sizeof(ConvChainDesc):
             raise TadmmLibraryError(f"{path}: tadmm_conv_chain_desc layout mismatch")
+        if lib.tadmm_orth_desc_bytes() != C.sizeof(OrthDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_orth_desc layout mismatch")
         _lib = lib
         return lib
 

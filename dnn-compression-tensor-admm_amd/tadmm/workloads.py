@@ -199,3 +199,37 @@ def build(config: str, seed: int = 0, fresh_table: bool = True):
     table = hp.fresh_table(key) if fresh_table else hp.table(key)
     shapes = {name: fn(name) for name in table.ranks}
     return SyntheticModel(shapes, seed), table, fmt
+
+
+# ---------------------------------------------------------------- factorised models of the orthogonality regulariser
+ORTH_TABLES = {
+    # name: rank table; every two-rank entry becomes a TKConv2dC (4-D) / TKLinearM (2-D), every single-rank 1x1 entry
+    # an SVDConv2dC (the reference's tt_conv1x1, resnet_inet_tt.py:48-50)
+    "tk_resnet50_3x": "tk_resnet50_hp.HyperParamsDictRatio3x",
+    "tk_resnet32_2x": "tk_resnet32_hp.HyperParamsDictRatio2x",
+    "tk_deit_tiny_2x": "tk_deit_tiny_patch16_224_hp.HyperParamsDictRatio2x",
+    "tk_vgg16_2x": "tk_vgg16_hp.HyperParamsDictRatio2x",
+    "svd_mobilenetv2_cifar_2x": "svd_mobilenetv2_cifar_hp.HyperParamsDictRatio2x",
+}
+
+
+def orth_model(name: str, seed: int = 0) -> torch.nn.Module:
+    """The factorised layers of a rank table (shapes from this module, xavier initialisation), on the CPU."""
+    from .svd_layers import SVDConv2dC
+    from .tk_layers import TKConv2dC, TKLinearM
+    key = ORTH_TABLES[name]
+    table = hp.table(key)
+    fn = shape_fn_for(key)
+    torch.manual_seed(seed)
+    layers = torch.nn.ModuleList()
+    for lname, r in table.ranks.items():
+        shp = fn(lname)
+        single = isinstance(r, int) or len(r) == 1
+        if single and len(shp) == 4 and tuple(shp[2:]) == (1, 1):
+            layers.append(SVDConv2dC(shp[1], shp[0], 1, hp_dict=table, name=lname))
+        elif not single and len(r) == 2:
+            if len(shp) == 4:
+                layers.append(TKConv2dC(shp[1], shp[0], tuple(shp[2:]), hp_dict=table, name=lname))
+            else:
+                layers.append(TKLinearM(shp[1], shp[0], hp_dict=table, name=lname))
+    return layers

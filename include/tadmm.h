@@ -190,6 +190,38 @@ int tadmm_penalty(tadmm_handle h, int n, const void* const* ptrs_dev, const int6
                   int64_t total_numel, float rho, float grad_scale, double* loss_dev, double* partial_dev,
                   void* stream);
 
+/* ---- orthogonality regulariser of Tucker / SVD factors (orthogonal.py: append_double_l2_loss) ---------------------
+ * For every factor P (a rows x cols float32 matrix, row stride ld >= cols, 4-byte aligned):
+ *   gram_of_rows != 0:  E = P P^T - I,  grad = 2 rho E P        gram_of_rows == 0:  E = P^T P - I,  grad = 2 rho P E
+ *   loss_dev[0] += 0.5 * rho * sum ||E||_F^2
+ * The Grams are exact fp32 products accumulated in fp64 on v_mfma_f64_16x16x4_f64 (csrc/gram.hip), E P / P E run on
+ * the fp64 matrix cores as well and each gradient entry is rounded to float32 once.  Fixed reduction orders, no
+ * floating-point atomics: results are bitwise reproducible.
+ * grad_offset: where the factor's gradient (contiguous rows x cols float32) starts, in elements, inside the gradient
+ *   buffer given to each tadmm_orth_l2 call; negative: the factor adds to the loss but gets no gradient.
+ * The plan captures the P pointers and uploads its tables into the workspace once, ordered on `stream` (the call waits
+ * for the copy); each tadmm_orth_l2 call is then stream-ordered, copies nothing and launches at most four kernels
+ * whatever the number of factors (a call with grad == NULL launches only the workgroups that sum ||E||^2).
+ * tadmm_orth_plan_create returns TADMM_ERR_INVALID for n <= 0, an empty factor (rows * cols == 0), ld < cols or a
+ * misaligned P, and TADMM_ERR_WORKSPACE when workspace_bytes < tadmm_orth_workspace_bytes. */
+typedef struct {
+  const float* P;
+  int64_t grad_offset;
+  int32_t rows, cols;
+  int64_t ld;
+  int32_t gram_of_rows;
+  int32_t reserved;
+} tadmm_orth_desc;
+typedef struct tadmm_orth_plan_s* tadmm_orth_plan;
+/* sizeof(tadmm_orth_desc) as the library was built */
+int tadmm_orth_desc_bytes(void);
+int tadmm_orth_workspace_bytes(int n, const tadmm_orth_desc* descs, size_t* bytes);
+int tadmm_orth_plan_create(tadmm_handle h, int n, const tadmm_orth_desc* descs, void* workspace,
+                           size_t workspace_bytes, void* stream, tadmm_orth_plan* out);
+/* grad: device float32 buffer holding every factor's gradient at its grad_offset, or NULL (loss only). */
+int tadmm_orth_l2(tadmm_orth_plan p, double rho, float* grad, double* loss_dev, void* stream);
+int tadmm_orth_plan_destroy(tadmm_orth_plan p);
+
 /* ---- building blocks (also used by the factorised layers) -------------- */
 /* C[i,j] = alpha * sum_k A(i,k) B(k,j) (+ beta*C) with arbitrary element strides; one of the two
  * strides of each operand must be 1.  Replaces the torch.mm / F.linear chains of
