@@ -87,6 +87,15 @@ class OrthDesc(C.Structure):
         ("ld", C.c_int64), ("gram_of_rows", C.c_int32), ("reserved", C.c_int32),
     ]
 
+
+class WgradDesc(C.Structure):
+    _fields_ = [
+        ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
+        ("T", C.c_int64), ("M", C.c_int32), ("N", C.c_int32),
+        ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64),
+        ("hw", C.c_int32), ("dtype", C.c_int32), ("alpha", C.c_float), ("reserved", C.c_int32),
+    ]
+
 # name -> (restype, argtypes); this table IS the list of symbols include/tadmm.h declares
 ABI = {
     "tadmm_version": (C.c_int, []),
@@ -149,6 +158,9 @@ ABI = {
     "tadmm_tucker_1x1": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_svdconv_fwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_svdconv_bwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
+    "tadmm_wgrad_desc_bytes": (C.c_int, []),
+    "tadmm_wgrad_workspace_bytes": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "tadmm_wgrad": (C.c_int, [C.c_void_p, C.POINTER(WgradDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "tadmm_gram_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_gram_ld": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tadmm_gram_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -221,6 +233,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_conv_chain_desc layout mismatch")
         if lib.tadmm_orth_desc_bytes() != C.sizeof(OrthDesc):
             raise TadmmLibraryError(f"{path}: tadmm_orth_desc layout mismatch")
+        if lib.tadmm_wgrad_desc_bytes() != C.sizeof(WgradDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_wgrad_desc layout mismatch")
         _lib = lib
         return lib
 

@@ -41,11 +41,25 @@ class _Mm(torch.autograd.Function):
         ga = gb = gbias = None
         if ctx.needs_input_grad[0]:
             ga = ops.mm(g_, b_.t())            # dA = dC B^T   (B^T is a stride swap)
-        if ctx.needs_input_grad[1]:
-            gb = ops.mm(a_.t(), g_)            # dB = A^T dC
+        if ctx.needs_input_grad[1]:            # dB = A^T dC
+            gb = ops.wgrad(a_, g_) if mm_wgrad_pays(a_, g_) else ops.mm(a_.t(), g_)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gbias = g.sum(0)
         return ga, gb, gbias
+
+
+_MM_WGRAD_MIN_T = 512
+
+
+def mm_wgrad_pays(a: torch.Tensor, g: torch.Tensor) -> bool:
+    """True when `dB = A^T dC` of `mm` goes to the split-T kernel (`ops.wgrad`); False: `ops.mm`, which keeps the short
+    reductions of the core contractions that share `_Mm`.  A pure function of the shapes and strides: both operands are
+    token rows (unit feature stride, so nothing is copied) and the reduction has at least `_MM_WGRAD_MIN_T` rows.
+    Measured (`scripts/bench_wgrad.py --threshold`): the two routes cross between 128 and 256 rows,
+    where their spreads still overlap; from 512 rows the kernel is ahead beyond the spread at every (M, N) of the sweep
+    (1.8x - 2.5x there, growing linearly with the rows).  Reductions of 512 rows and more also occur in the later steps
+    of `_chain_recover` (up to out_features rows); they switch as well, which is what the sweep favours."""
+    return a.shape[0] >= _MM_WGRAD_MIN_T and a.stride(1) == 1 and g.stride(1) == 1 and a.shape[1] > 0 and g.shape[1] > 0
 
 
 def mm(a: torch.Tensor, b: torch.Tensor, bias_n: torch.Tensor = None) -> torch.Tensor:
@@ -156,13 +170,8 @@ class _ChainSingle(torch.autograd.Function):
         if ctx.needs_input_grad[0]:                 # dX = dY W : the same kernel with the transposed weight
             gx = ops.chain_single(g, planes_of(w, _nplanes(g), transpose=True), None, w.shape[1], entry=ctx.entry,
                                   image_out=ctx.image, memo=False)
-        if ctx.needs_input_grad[1]:                 # dW = dY^T X  (N x K), plain fp32 product
-            if ctx.image:
-                g2 = g.permute(1, 0, 2, 3).reshape(g.shape[1], -1)
-                x2 = x.permute(1, 0, 2, 3).reshape(x.shape[1], -1)
-                gw = ops.mm(_as_gemm_operand(g2.float()), _as_gemm_operand(x2.float()).t())
-            else:
-                gw = ops.mm(_as_gemm_operand(g.float()).t(), _as_gemm_operand(x.float()))
+        if ctx.needs_input_grad[1]:                 # dW = dY^T X  (N x K) over tokens / pixels, operands in place
+            gw = ops.wgrad(g, x)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g.sum((0, 2, 3)) if ctx.image else g.sum(0)
         return gx, gw, gb, None, None
@@ -216,10 +225,11 @@ class _ChainFused(torch.autograd.Function):
                                  entry="tadmm_ttlinear_bwd", memo=False)
         if ctx.needs_input_grad[1]:                 # dWin = (dY Wout)^T X
             gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], memo=False)
-            gwi = ops.mm(_as_gemm_operand(gr.float()).t(), _as_gemm_operand(x.float()))
+            gwi = ops.wgrad(gr, x)
+            del gr
         if ctx.needs_input_grad[2]:                 # dWout = dY^T (X Win^T)
             h = ops.chain_single(x, planes_of(w_in, _nplanes(x)), None, w_in.shape[0], memo=False)
-            gwo = ops.mm(_as_gemm_operand(g.float()).t(), _as_gemm_operand(h.float()))
+            gwo = ops.wgrad(g, h)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(0)
         return gx, gwi, gwo, gb, None
@@ -238,11 +248,6 @@ def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias:
         return ops.chain_fused(x.reshape(-1, x.shape[-1]), planes[0], planes[1], bias, w_out.shape[0],
                                memo=not fresh).reshape(*lead, w_out.shape[0])
     return _ChainFused.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes).reshape(*lead, w_out.shape[0])
-
-
-def _channel_major(t: torch.Tensor) -> torch.Tensor:
-    """(B, C, H, W) -> (C, B*H*W) float32 operand of a weight-gradient product."""
-    return _as_gemm_operand(t.permute(1, 0, 2, 3).reshape(t.shape[1], -1).float())
 
 
 class _Conv1x1Chain(torch.autograd.Function):
@@ -274,11 +279,12 @@ class _Conv1x1Chain(torch.autograd.Function):
         if ctx.needs_input_grad[1]:                 # dWin = (Wout^T dY) X^T over all pixels
             gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], entry="tadmm_tucker_1x1",
                                   image_out=True, memo=False)
-            gwi = ops.mm(_channel_major(gr), _channel_major(x).t()).to(w_in.dtype)
+            gwi = ops.wgrad(gr, x).to(w_in.dtype)
+            del gr                                  # released before the other intermediate is made
         if ctx.needs_input_grad[2]:                 # dWout = dY (Win X)^T over all pixels
             h = ops.chain_single(x, planes_of(w_in, _nplanes(x)), None, w_in.shape[0], entry="tadmm_tucker_1x1",
                                  image_out=True, memo=False)
-            gwo = ops.mm(_channel_major(g), _channel_major(h).t()).to(w_out.dtype)
+            gwo = ops.wgrad(g, h).to(w_out.dtype)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum((0, 2, 3))
         return gx, gwi, gwo, gb, None

@@ -345,6 +345,83 @@ def mm_nt_bf16(a: torch.Tensor, bt: torch.Tensor, bias_n: Optional[torch.Tensor]
     return out
 
 
+# ------------------------------------------------------------------ weight gradients (csrc/wgrad.hip)
+def _wgrad_operands(a: torch.Tensor, b: torch.Tensor):
+    """Validated (a, b, T, M, N, hw) of a weight-gradient product; the only copies are `.contiguous()` of a row tensor
+    without unit feature stride or of a non-contiguous image (alignment is the kernel's business)."""
+    for t, what in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TadmmError(-1, f"wgrad: {what} must live on a HIP device; there is no CPU path")
+    if a.device != b.device:
+        raise TadmmError(-1, f"wgrad: operands on different devices ({a.device}, {b.device})")
+    if a.dtype != b.dtype:
+        raise TadmmError(-1, f"wgrad: operands must share one dtype (got {a.dtype}, {b.dtype})")
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise TadmmError(-1, f"wgrad: operands must be float32 or bfloat16 (got {a.dtype})")
+    if a.dim() != b.dim() or a.dim() not in (2, 4):
+        raise TadmmError(-1, f"wgrad: two (T, features) row tensors or two NCHW images (got {a.dim()}-D and {b.dim()}-D)")
+    if a.dim() == 4:
+        if (a.shape[0],) + tuple(a.shape[2:]) != (b.shape[0],) + tuple(b.shape[2:]):
+            raise TadmmError(-1, f"wgrad: images differ in (B, H, W): {tuple(a.shape)} vs {tuple(b.shape)}")
+        hw = a.shape[2] * a.shape[3]
+        if a.shape[0] > 0 and hw == 0:
+            raise TadmmError(-1, "wgrad: images without pixels")
+        a = a if a.is_contiguous() else a.contiguous()
+        b = b if b.is_contiguous() else b.contiguous()
+        return a, b, a.shape[0] * hw, a.shape[1], b.shape[1], max(hw, 1)
+    if a.shape[0] != b.shape[0]:
+        raise TadmmError(-1, f"wgrad: operands differ in T: {a.shape[0]} vs {b.shape[0]}")
+    a = a if a.stride(1) == 1 and a.stride(0) >= a.shape[1] else a.contiguous()
+    b = b if b.stride(1) == 1 and b.stride(0) >= b.shape[1] else b.contiguous()
+    return a, b, a.shape[0], a.shape[1], b.shape[1], 0
+
+
+def _wgrad_desc(a, b, T, M, N, hw, alpha: float = 1.0):
+    d = _cabi.WgradDesc()
+    d.A, d.B, d.T, d.M, d.N, d.hw = a.data_ptr(), b.data_ptr(), T, M, N, hw
+    d.lda, d.ldb = (0, 0) if hw else (a.stride(0), b.stride(0))
+    d.dtype = _cabi.CHAIN_F32 if a.dtype == torch.float32 else _cabi.CHAIN_BF16
+    d.alpha = float(alpha)
+    return d
+
+
+def wgrad_plan(a: torch.Tensor, b: torch.Tensor):
+    """(workspace bytes, slices of T) `wgrad(a, b)` will use: `tadmm_wgrad_workspace_bytes`, a pure function of the
+    shapes."""
+    a, b, T, M, N, hw = _wgrad_operands(a, b)
+    if M == 0 or N == 0:
+        return 0, 1
+    nbytes, slices = C.c_size_t(), C.c_int()
+    rc = _cabi.load().tadmm_wgrad_workspace_bytes(C.byref(_wgrad_desc(a, b, T, M, N, hw)), C.byref(nbytes),
+                                                  C.byref(slices))
+    if rc < 0:
+        raise TadmmError(rc, "tadmm_wgrad_workspace_bytes: the launch does not take this shape")
+    return nbytes.value, slices.value
+
+
+def wgrad(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, alpha: float = 1.0) -> torch.Tensor:
+    """out (M, N) float32 = alpha * sum_t a[t, :]^T b[t, :]: the weight-gradient product of the factorised layers
+    (`tadmm_wgrad`, csrc/wgrad.hip).  `a`, `b`: two row tensors (T, M) / (T, N) or two NCHW images (B, M, H, W) /
+    (B, N, H, W), t = (batch, pixel), both float32 or both bfloat16, read in place; split over T, deterministic."""
+    a, b, T, M, N, hw = _wgrad_operands(a, b)
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    elif (not out.is_cuda or out.device != a.device or out.dtype != torch.float32 or tuple(out.shape) != (M, N)
+          or (N > 1 and out.stride(1) != 1)):
+        raise TadmmError(-1, f"wgrad: out must be a float32 ({M}, {N}) device tensor with unit column stride")
+    if M == 0 or N == 0:
+        return out
+    d = _wgrad_desc(a, b, T, M, N, hw, alpha)
+    d.C, d.ldc = out.data_ptr(), out.stride(0) if M > 1 else max(out.stride(0), N)
+    dev = a.device
+    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    nbytes, slices = C.c_size_t(), C.c_int()
+    h.check(h.lib.tadmm_wgrad_workspace_bytes(C.byref(d), C.byref(nbytes), C.byref(slices)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    h.check(h.lib.tadmm_wgrad(h.ptr, C.byref(d), None if ws is None else ws.data_ptr(), nbytes.value, _stream(dev)))
+    return out
+
+
 # ------------------------------------------------------------------ forward chains (csrc/chain.hip)
 def weight_planes(w: torch.Tensor, planes: int, pad_rows: int = 16, pad_cols: int = 32) -> torch.Tensor:
     """(N, K) weight -> (planes, Np/16, Kp/32, 64, 8) bfloat16 in the fragment-major order of csrc/chain.hip

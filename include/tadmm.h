@@ -296,6 +296,38 @@ int tadmm_svdconv_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
  * Wout = Win^T planes (C_in x R), bias NULL. */
 int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 
+/* ---- weight gradients of the factorised layers (csrc/wgrad.hip) ---------------------------------------------------
+ * C[m][n] = alpha * sum_{t < T} A[t][m] * B[t][n], float32 C with row stride ldc: dW = dY^T X and its kin, a small
+ * output (a rank times a channel count) over a long reduction (tokens or batch * pixels).  A and B are read in place,
+ * both of `dtype` (TADMM_CHAIN_F32: exact three-plane bf16 split, six products per product, fp32-GEMM accuracy;
+ * TADMM_CHAIN_BF16: one plane, products exact), both in one layout:
+ *   hw == 0: token rows, A (T, M) with row stride lda >= M, B (T, N) with row stride ldb >= N (elements);
+ *   hw  > 0: channels-first images, A contiguous (T / hw, M, hw), B contiguous (T / hw, N, hw); lda / ldb ignored.
+ * Any alignment the element type allows: 16-byte loads where base and stride (lda / ldb, or hw) permit, 8-byte or
+ * element loads otherwise.  The reduction is split over slices of T; the number of slices is a pure function of
+ * (M, N, T).  With more than one slice every slice writes its tile to `workspace` (16-byte aligned, at least
+ * tadmm_wgrad_workspace_bytes) and a second launch adds them in fixed order in fp64: no atomics, bitwise reproducible,
+ * and independent of what workspace and C held before.  T == 0 writes zeros.
+ * TADMM_ERR_INVALID: M <= 0, N <= 0, T < 0, unknown dtype, a null operand with T > 0, T not a multiple of hw, a row
+ * stride below the feature count; TADMM_ERR_WORKSPACE: workspace too small (nothing is launched);
+ * TADMM_ERR_UNSUPPORTED: T >= 2^31 - 256 or more than 2^20 output tiles. */
+typedef struct {
+  const void* A; const void* B; float* C;
+  int64_t T;
+  int32_t M, N;
+  int64_t lda, ldb, ldc;                      /* elements */
+  int32_t hw;                                 /* 0: token rows; > 0: NCHW images of hw pixels */
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16, for A and B alike */
+  float alpha;
+  int32_t reserved;
+} tadmm_wgrad_desc;
+/* sizeof(tadmm_wgrad_desc) as the library was built */
+int tadmm_wgrad_desc_bytes(void);
+/* Host only, no device needed: bytes of workspace tadmm_wgrad wants for this descriptor (0 when one slice serves it)
+ * and, when slices_out is not NULL, the number of slices. */
+int tadmm_wgrad_workspace_bytes(const tadmm_wgrad_desc* d, size_t* bytes, int* slices_out);
+int tadmm_wgrad(tadmm_handle h, const tadmm_wgrad_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The whole factorised convolution of a SMALL image in one launch (csrc/convchain.hip): y = W3 conv_kxk(W1 x; Wc) + bias
  * for NCHW tensors with output rows of at most 64 pixels: one workgroup per tile of output rows (<= 64 output pixels, a halo of
  * <= 192 input pixels); the two intermediates stay in LDS.  TTConv2dM
