@@ -1290,24 +1290,31 @@ int tadmm_penalty(tadmm_handle h, int n, const void* const* ptrs_dev, const int6
 }
 
 // ---- grouped GEMM ----
+static bool gemm_desc_valid(const tadmm_gemm_desc& s) {
+  return s.M > 0 && s.N > 0 && s.K > 0 && ((s.a_rs == 1) || (s.a_cs == 1)) && ((s.b_rs == 1) || (s.b_cs == 1));
+}
+
+// 0 for a group that tadmm_gemm_pack refuses: a negative extent must not turn into a huge tile count
 size_t tadmm_gemm_pack_bytes(int n, const tadmm_gemm_desc* descs) {
   if (n <= 0 || !descs) return 0;
   size_t blocks = 0;
-  for (int i = 0; i < n; ++i)
+  for (int i = 0; i < n; ++i) {
+    if (!gemm_desc_valid(descs[i])) return 0;
     blocks += (size_t)((descs[i].M + kGemmBM - 1) / kGemmBM) * ((descs[i].N + kGemmBN - 1) / kGemmBN);
+  }
   return align_up((size_t)n * sizeof(GemmDesc), 256) + blocks * sizeof(BlockRef);
 }
 
 int tadmm_gemm_pack(int n, const tadmm_gemm_desc* descs, void* blob_host, size_t blob_bytes, int* nblocks_out) {
   if (n <= 0 || !descs || !blob_host || !nblocks_out) return TADMM_ERR_INVALID;
+  for (int i = 0; i < n; ++i)       // shapes and strides first: the byte count of an invalid group means nothing
+    if (!gemm_desc_valid(descs[i])) return TADMM_ERR_INVALID;
   if (blob_bytes < tadmm_gemm_pack_bytes(n, descs)) return TADMM_ERR_WORKSPACE;
   GemmDesc* gd = (GemmDesc*)blob_host;
   BlockRef* map = (BlockRef*)((char*)blob_host + align_up((size_t)n * sizeof(GemmDesc), 256));
   int nb = 0;
   for (int i = 0; i < n; ++i) {
     const tadmm_gemm_desc& s = descs[i];
-    if (s.M <= 0 || s.N <= 0 || s.K <= 0) return TADMM_ERR_INVALID;
-    if (!((s.a_rs == 1) || (s.a_cs == 1)) || !((s.b_rs == 1) || (s.b_cs == 1))) return TADMM_ERR_INVALID;
     GemmDesc& g = gd[i];
     memset(&g, 0, sizeof g);
     g.A = s.A; g.B = s.B; g.C = s.C; g.M = s.M; g.N = s.N; g.K = s.K;

@@ -293,6 +293,9 @@ class GemmBatch:
         n = len(descs)
         arr = (GemmDesc * n)(*descs)
         nbytes = lib.tadmm_gemm_pack_bytes(n, arr)
+        if nbytes == 0:
+            raise TadmmError(-1, "tadmm_gemm_pack: invalid GEMM descriptor (positive extents, and each "
+                                                "operand needs one unit stride)")
         host = torch.empty(nbytes, dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else \
             torch.empty(nbytes, dtype=torch.uint8)
         nblocks = C.c_int()
@@ -308,14 +311,16 @@ class GemmBatch:
                                                _stream(self.device)))
 
 
-def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, alpha=1.0, bias_n=None, bias_m=None):
-    """out = alpha * a @ b (+bias) for 2-D float32 device tensors with arbitrary (one unit) strides."""
+def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, alpha=1.0, bias_n=None, bias_m=None,
+       beta=0.0):
+    """out = alpha * a @ b (+ beta * out) (+bias) for 2-D float32 device tensors with arbitrary (one unit) strides.
+    `out` is read only when beta != 0."""
     assert a.dim() == 2 and b.dim() == 2 and a.shape[1] == b.shape[0]
     M, K = a.shape
     N = b.shape[1]
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    d = gemm_desc(a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, a.stride(), b.stride(), out.stride(), alpha, 0.0,
+    d = gemm_desc(a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, a.stride(), b.stride(), out.stride(), alpha, beta,
                   None if bias_n is None else bias_n.data_ptr(), None if bias_m is None else bias_m.data_ptr())
     dev = a.device
     h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())

@@ -236,7 +236,10 @@ typedef struct {
   const float* bias_m;   /* nullable: added along M */
 } tadmm_gemm_desc;
 /* pack: writes GemmDesc[n] + block map into a host blob the caller uploads (and may cache) itself;
- * run: launches one grouped kernel over the uploaded blob. */
+ * run: launches one grouped kernel over the uploaded blob.
+ * A descriptor with M, N or K <= 0 or an operand A / B without a unit stride is refused before anything is sized:
+ * tadmm_gemm_pack returns TADMM_ERR_INVALID (TADMM_ERR_WORKSPACE only for a valid group in a short blob) and
+ * tadmm_gemm_pack_bytes returns 0. */
 size_t tadmm_gemm_pack_bytes(int n, const tadmm_gemm_desc* descs);
 int tadmm_gemm_pack(int n, const tadmm_gemm_desc* descs, void* blob_host, size_t blob_bytes, int* nblocks_out);
 int tadmm_gemm_run(tadmm_handle h, const void* blob_dev, int n, int nblocks, void* stream);
