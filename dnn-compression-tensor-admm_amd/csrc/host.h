@@ -1,6 +1,7 @@
-// Host-side pieces shared by the plan builders (plan.hip: TT / SVD projection, tucker_plan.hip: Tucker-2):
-// the context object behind tadmm_handle, error macros, the two-pass workspace arena, the XCD-aware block
-// order of the Jacobi tournament, and the driver loop of one grouped eigen-solve.
+// Host-side pieces shared by the plan builders (plan.hip: TT / SVD projection, tucker_plan.hip: Tucker-2) and the
+// stand-alone entries (abi_ops.hip): the context object behind tadmm_handle, error macros, the two-pass workspace
+// arena and its placement helpers, the geometry of one eigen-problem, the XCD-aware block order of the Jacobi
+// tournament, and the layout and driver loop of one grouped eigen-solve.
 #pragma once
 #include "common.h"
 
@@ -55,11 +56,9 @@ struct Phase {  // one grouped launch: descriptor array + block map inside the d
   int nprob = 0, nblocks = 0;
 };
 
-// A simple bump allocator that is run twice: once with base==nullptr to size the workspace, once for real.
+// A simple bump allocator of workspace offsets; a layout is run twice, once to size the workspace, once for real.
 struct Arena {
-  char* base;
   size_t off = 0;
-  explicit Arena(char* b) : base(b) {}
   size_t take(size_t bytes, size_t align = 256) {
     off = align_up(off, align);
     const size_t o = off;
@@ -68,9 +67,10 @@ struct Arena {
   }
 };
 
-struct HostImage {   // host copy of the descriptor part of the arena
+struct HostImage {   // host copy of the descriptor part of the arena; it ends at the last non-empty array put into it
   std::vector<char> bytes;
   void put(size_t off, const void* src, size_t n) {
+    if (!n) return;
     if (bytes.size() < off + n) bytes.resize(off + n);
     memcpy(bytes.data() + off, src, n);
   }
@@ -84,9 +84,67 @@ static inline void place_phase(Phase& ph, Arena& da, HostImage* img, const void*
   ph.desc_off = da.take(std::max<size_t>(dbytes, 16));
   ph.map_off = da.take(std::max<size_t>(map.size() * sizeof(BlockRef), 16));
   if (img) {
-    if (dbytes) img->put(ph.desc_off, descs, dbytes);
-    if (!map.empty()) img->put(ph.map_off, map.data(), map.size() * sizeof(BlockRef));
+    img->put(ph.desc_off, descs, dbytes);
+    img->put(ph.map_off, map.data(), map.size() * sizeof(BlockRef));
   }
+}
+
+// the descriptors of `like` under another block map (Gram reduce; self / norms / extract of an eigen group)
+static inline void place_map_like(Phase& ph, const Phase& like, Arena& da, HostImage* img, const std::vector<BlockRef>& map) {
+  ph = like;
+  ph.nblocks = (int)map.size();
+  ph.map_off = da.take(std::max<size_t>(map.size() * sizeof(BlockRef), 16));
+  if (img) img->put(ph.map_off, map.data(), map.size() * sizeof(BlockRef));
+}
+
+// sets the tile counts of one fp32 GEMM and returns the number of its blocks
+static inline size_t set_gemm_tiles(GemmDesc& g) {
+  g.tiles_m = (g.M + kGemmBM - 1) / kGemmBM;
+  g.tiles_n = (g.N + kGemmBN - 1) / kGemmBN;
+  return (size_t)g.tiles_m * g.tiles_n;
+}
+// the same, appending the blocks to the map of the grouped launch as problem `prob`
+static inline void gemm_tiles(GemmDesc& g, int prob, std::vector<BlockRef>& map) {
+  const int nt = (int)set_gemm_tiles(g);
+  for (int b = 0; b < nt; ++b) map.push_back(BlockRef{prob, b});
+}
+
+// Geometry of one eigen-problem: the N x N Gram of an m x cols matrix, taken on its smaller side, and the split-K
+// shape of the launch that forms it.
+struct EigGeom {
+  int m = 0;            // rows of the matrix
+  int64_t cols = 0;     // columns of the matrix
+  bool trans = false;   // m > cols : eigen-solve on A^T A
+  int N = 0, Npad = 0, nb = 0, ld = 0;
+  int nt = 0, ksplit = 1, kchunk = 0;
+};
+
+// wg_target: Gram workgroups a problem should at least have; cap_chunk: no K chunk longer than 2048.  The plans pass
+// (64, true), the stand-alone Gram (256, false).
+static inline EigGeom eig_geom(int m, int64_t cols, int wg_target, bool cap_chunk) {
+  EigGeom g;
+  g.m = m; g.cols = cols;
+  g.trans = (int64_t)m > cols;
+  g.N = (int)std::min<int64_t>(m, cols);
+  g.Npad = (int)align_up(g.N, 4 * kJB);     // whole super-pairs of 2 x 16 columns
+  g.nb = g.Npad / kJB;
+  // row length of the eigen-solver's X image: whole 1 KiB chunks (tick3 wants ld % 64 == 0)
+  g.ld = eig_ld(g.N);
+  g.nt = (g.N + 31) / 32;
+  // (an empty problem, N <= 0, gets a valid split too: the size queries of the ABI are total, the entries refuse it)
+  const int64_t K = std::max<int64_t>(1, g.trans ? m : cols);
+  const int ntp = std::max(1, g.nt * (g.nt + 1) / 2);
+  // split-K only where a problem has too few tiles to matter beside the others of its level (levels batch
+  // 15-30 problems): >= 64 workgroups per problem in a plan; big problems (ks = 1) write G directly, no reduce pass
+  int ks = (wg_target + ntp - 1) / ntp;
+  const int maxks = (int)std::max<int64_t>(1, (K + 255) / 256);
+  ks = std::max(1, std::min(ks, maxks));
+  // a workgroup's duration grows with its K chunk and it shares the CU's matrix cores with its neighbours:
+  // cap the chunk so that the long reductions (K = 4608 beside K = 512) do not form the tail of the launch
+  if (cap_chunk) ks = std::max(ks, (int)((K + 2047) / 2048));
+  g.kchunk = (int)align_up((K + ks - 1) / ks, 64);
+  g.ksplit = (int)((K + g.kchunk - 1) / g.kchunk);
+  return g;
 }
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share one, MI355X_MICROARCH "Workgroup
@@ -244,6 +302,94 @@ struct EigGroup {
   // debug only
   const double* off_dev = nullptr; const int* done_dev = nullptr;
 };
+
+// Plan-time state of one grouped eigen-solve: where its descriptors and block maps sit in the workspace, and the
+// kernel choice of the group.  tick carries the EigDesc array; self / norm / ext are further maps over it.
+struct EigLayout {
+  Phase tick, self, norm, ext;
+  std::vector<int> players;       // per problem: tournament players
+  std::vector<int> row_len;       // per problem: ld of the X image (instrumented runs)
+  std::vector<int> mid;           // per problem: 128 / 192 when it may take the direct route of tridiag_mid.hip, else 0
+  int neig = 0;
+  int gsteps = 0;                 // ticks per global sweep = max(players - 1)
+  int mode = 0;                   // 0: pairs (tick1), 1: LDS super-pairs (tick2), 3: tick3 + self pass
+  int ld_max = 0, npad_max = 0;
+  size_t tick_lds = 0;            // dynamic LDS of the tick launches
+  bool aligned = false;           // every EigDesc carries period = gsteps
+  size_t prev_off = 0;            // [neig] doubles of the convergence kernel (taken by the caller)
+  int last_sweeps = 0;            // global sweeps the previous run needed
+
+  // The run-time view; the caller adds what is its own (off_dev / done_dev, warm, after_init, expected).
+  // mid_sizes is always given: only Rayleigh-Ritz descriptors carry EigDesc::scratch (filter_layout), so the fallback and
+  // Tucker groups have all-zero `mid` and stay off the direct route of tridiag_mid.hip -- setting `scratch` on their
+  // descriptors would change their launch sequence.  row_len feeds the flop count of instrumented runs only.
+  EigGroup group(char* ws, const int32_t* skip) const {
+    EigGroup g;
+    g.ed = (const EigDesc*)(ws + tick.desc_off); g.neig = neig;
+    g.players = players.data(); g.row_len = row_len.data(); g.mid_sizes = mid.data();
+    g.gsteps = gsteps; g.mode = mode; g.aligned = aligned;
+    g.ld_max = ld_max; g.npad_max = npad_max; g.tick_lds = tick_lds;
+    g.tick_map = (const BlockRef*)(ws + tick.map_off); g.tick_blocks = tick.nblocks;
+    g.self_map = (const BlockRef*)(ws + self.map_off); g.self_blocks = self.nblocks;
+    g.prev_dev = (double*)(ws + prev_off);
+    g.skip = skip;
+    return g;
+  }
+  // eigenvalues and their order; then the kept vectors and sigma (a caller may queue work on the sorted columns between)
+  void sort(char* ws, hipStream_t s, const int32_t* skip) const {
+    const EigDesc* ed = (const EigDesc*)(ws + tick.desc_off);
+    launch_eig_norms(ed, (const BlockRef*)(ws + norm.map_off), norm.nblocks, s, skip);
+    launch_eig_sort(ed, neig, s, skip, npad_max);
+  }
+  void extract(char* ws, hipStream_t s, const int32_t* skip) const {
+    launch_eig_extract((const EigDesc*)(ws + tick.desc_off), (const BlockRef*)(ws + ext.map_off), ext.nblocks, s, skip);
+  }
+  void finalize(char* ws, hipStream_t s, const int32_t* skip) const { sort(ws, s, skip); extract(ws, s, skip); }
+};
+
+// Kernel choice, players and the four block maps of a group (counts go into the layout's phases, offsets do not).
+// `align` (tick3 groups, unless TADMM_JACOBI_ALIGN=0): stamp one sweep period on every problem.
+struct EigMaps { std::vector<BlockRef> tick, self, norm, ext; };
+static inline EigMaps eig_maps(EigLayout& l, std::vector<EigDesc>& descs, bool align) {
+  EigMaps m;
+  l.neig = (int)descs.size();
+  l.ld_max = l.npad_max = l.gsteps = 0;
+  l.players.clear(); l.row_len.clear(); l.mid.clear();
+  for (const EigDesc& e : descs) { l.ld_max = std::max(l.ld_max, e.ld); l.npad_max = std::max(l.npad_max, e.Npad); }
+  // tick shape of the group: LDS-resident super-pairs when every problem fits, else plain pairs
+  l.mode = descs.empty() ? 0 : choose_jacobi_mode(l.ld_max);
+  const bool super = l.mode >= 1;
+  l.tick_lds = l.mode == 1 ? jacobi_tick2_lds_bytes(l.ld_max) : jacobi_tick_lds_bytes(l.ld_max);
+  for (int pq = 0; pq < l.neig; ++pq) {
+    const EigDesc& e = descs[pq];
+    const int units = super ? e.nb / 2 : e.nb;       // players of the tournament
+    l.players.push_back(units);
+    l.row_len.push_back(e.ld);
+    l.mid.push_back((e.scratch && eig_mid_direct_size(e.N) && e.N == e.Npad) ? e.N : 0);
+    l.gsteps = std::max(l.gsteps, units - 1);
+    for (int b = 0; b < units / 2; ++b) m.tick.push_back(BlockRef{pq, b});
+    if (l.mode >= 2) for (int b = 0; b < units; ++b) m.self.push_back(BlockRef{pq, b});
+    for (int b = 0; b < (e.Npad + 3) / 4; ++b) m.norm.push_back(BlockRef{pq, b});
+    for (int b = 0; b < (e.r + 3) / 4; ++b) m.ext.push_back(BlockRef{pq, b});
+  }
+  xcd_group(m.tick);
+  xcd_group(m.self);
+  l.aligned = l.mode >= 2 && align && align_sweeps_on();
+  if (l.aligned) for (EigDesc& e : descs) e.period = l.gsteps;
+  l.tick.nprob = l.self.nprob = l.norm.nprob = l.ext.nprob = l.neig;
+  l.tick.nblocks = (int)m.tick.size(); l.self.nblocks = (int)m.self.size();
+  l.norm.nblocks = (int)m.norm.size(); l.ext.nblocks = (int)m.ext.size();
+  return m;
+}
+
+// eig_maps + placement: descriptors and tick map, then the self, norm and ext maps, in that order from `da`
+static inline void build_eig_layout(EigLayout& l, std::vector<EigDesc>& descs, bool align, Arena& da, HostImage* img) {
+  const EigMaps m = eig_maps(l, descs, align);
+  place_phase(l.tick, da, img, descs.data(), descs.size() * sizeof(EigDesc), l.neig, m.tick);
+  place_map_like(l.self, l.tick, da, img, m.self);
+  place_map_like(l.norm, l.tick, da, img, m.norm);
+  place_map_like(l.ext, l.tick, da, img, m.ext);
+}
 
 // Runs jacobi_init + sweeps until every problem of the group has its `done` flag.
 // Convergence is decided on the device after every sweep (jacobi_conv_kernel sets the sticky per-problem flags,

@@ -190,7 +190,7 @@ int orth_layout(tadmm_handle h, int n, const tadmm_orth_desc* descs, char* base,
     nslots += g.nt;
   }
   if (np > INT32_MAX / 2 || ntile > INT32_MAX / 2) CTX_FAIL(h, TADMM_ERR_INVALID, "orth: too many workgroups");
-  Arena a(base);
+  Arena a;
   const size_t o_gram = a.take(n * sizeof(GramDesc));
   const size_t o_mp = a.take(np * sizeof(BlockRef));
   const size_t o_mr = a.take(nr * sizeof(BlockRef));

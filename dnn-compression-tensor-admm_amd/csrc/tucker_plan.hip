@@ -25,44 +25,10 @@ using namespace tadmm;
 
 namespace {
 
-struct TkArena {
-  size_t off = 0;
-  size_t take(size_t bytes, size_t align = 256) {
-    off = align_up(off, align);
-    const size_t o = off;
-    off += bytes;
-    return o;
-  }
-};
-
-struct OpGeom {   // eigen-problem geometry of one "leading singular vectors" request
-  int m = 0, n = 0, N = 0, Npad = 0, ld = 0, nb = 0, nt = 0, ksplit = 1, kchunk = 0, r_eff = 0;
-  bool trans = false;
-};
-
-OpGeom op_geom(int m, int n, int r) {
-  OpGeom g;
-  g.m = m; g.n = n; g.trans = m > n;
-  g.N = std::min(m, n);
-  g.Npad = (int)align_up(g.N, 4 * kJB);
-  g.nb = g.Npad / kJB;
-  g.ld = eig_ld(g.N);
-  g.nt = (g.N + 31) / 32;
-  const int64_t K = g.trans ? m : n;
-  const int ntp = g.nt * (g.nt + 1) / 2;
-  int ks = (64 + ntp - 1) / ntp;
-  const int maxks = (int)std::max<int64_t>(1, (K + 255) / 256);
-  ks = std::max(1, std::min(ks, maxks));
-  ks = std::max(ks, (int)((K + 2047) / 2048));
-  g.kchunk = (int)align_up((K + ks - 1) / ks, 64);
-  g.ksplit = (int)((K + g.kchunk - 1) / g.kchunk);
-  g.r_eff = std::min(r, g.N);
-  return g;
-}
-
-struct Group {   // descriptors + block map of one grouped launch (offsets into the workspace)
-  size_t desc_off = 0, map_off = 0;
-  int nblocks = 0;
+struct OpGeom : EigGeom {   // one "leading singular vectors" request
+  int r_eff = 0;            // vectors it can deliver
+  OpGeom() = default;
+  OpGeom(int m, int n, int r) : EigGeom(eig_geom(m, n, 64, true)), r_eff(std::min(r, N)) {}
 };
 
 // Warm start of a streamed (N > 1152) HOOI eigen-solve: X0 = V G with V the eigenvectors of the same mode's previous solve.
@@ -78,13 +44,10 @@ struct BigWarm {
 
 struct Lsv {     // one grouped "leading singular vectors" phase over all layers
   std::vector<BigWarm> big;
-  Group gram_p, gram_r, tick, self, norm, ext, xg;
-  size_t eig_desc_off = 0;
-  std::vector<int> players;
+  Phase gram_p, gram_r, xg;
+  EigLayout eig;
   std::vector<int> players_n;     // per problem: N of the eigen-problem (timing: 8 N^3 model)
-  int gsteps = 0, mode = 0, ld_max = 0, npad_max = 0;
   bool warm = false;              // some problem of the group has a warm-start image
-  size_t tick_lds = 0;
 };
 
 struct TLayer {
@@ -200,8 +163,8 @@ struct tadmm_tucker_plan_s {
   char* ws = nullptr;
   size_t ws_bytes = 0, desc_bytes = 0;
   Lsv lsv[4];            // 0: init U_out, 1: init U_in, 2: HOOI U_out, 3: HOOI U_in
-  Group gemm[5];         // 0: P = T x1 U_in, 1: P = T x0 U_out, 2: C, 3: Z' = C x1 U_in, 4: Zmat = Z' x0 U_out
-  Group unfold, fold;
+  Phase gemm[5];         // 0: P = T x1 U_in, 1: P = T x0 U_out, 2: C, 3: Z' = C x1 U_in, 4: Zmat = Z' x0 U_out
+  Phase unfold, fold;
   size_t sweep_desc_off = 0, resid_partial_off = 0, fac_begin = 0, fac_end = 0;
   size_t warm_ok_off = 0;
   size_t off_off = 0, done_off = 0, prev_off = 0, skip_off = 0, nT_off = 0, nC_off = 0, err_off = 0, iters_off = 0,
@@ -227,24 +190,12 @@ static bool warm_start_on() {      // read at every plan creation (tests switch 
 }
 
 static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const* W, float* const* U, float* const* Z,
-                         std::vector<char>* img, size_t desc_region, size_t* desc_bytes, size_t* total_bytes) {
+                         HostImage* img, size_t desc_region, size_t* desc_bytes, size_t* total_bytes) {
   tadmm_handle h = P->h;
   const int n = P->n;
-  TkArena da, ar;
+  Arena da, ar;
   ar.off = desc_region;
   auto dev = [&](size_t off) -> char* { return base ? base + off : reinterpret_cast<char*>((uintptr_t)off); };
-  auto put = [&](size_t off, const void* src, size_t bytes) {
-    if (!img || bytes == 0) return;
-    if (img->size() < off + bytes) img->resize(off + bytes);
-    memcpy(img->data() + off, src, bytes);
-  };
-  auto place = [&](Group& g, const void* descs, size_t dbytes, const std::vector<BlockRef>& map) {
-    g.desc_off = da.take(std::max<size_t>(dbytes, 16));
-    g.map_off = da.take(std::max<size_t>(map.size() * sizeof(BlockRef), 16));
-    g.nblocks = (int)map.size();
-    put(g.desc_off, descs, dbytes);
-    put(g.map_off, map.data(), map.size() * sizeof(BlockRef));
-  };
 
   // ---- per-layer data buffers ----
   // the factors of all layers sit back to back so that one memset clears them at the start of a run
@@ -258,10 +209,10 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
   std::vector<OpGeom> og(4 * n);
   for (int l = 0; l < n; ++l) {
     TLayer& t = P->L[l];
-    og[0 * n + l] = op_geom(t.O, t.K2 * t.I, t.ro);        // init  : LEFT  of T (O x K2 I)
-    og[1 * n + l] = op_geom(t.O * t.K2, t.I, t.ri);        // init  : RIGHT of T (O K2 x I)
-    og[2 * n + l] = op_geom(t.O, t.K2 * t.ri, t.ro);       // HOOI  : LEFT  of P (O x K2 r_in)
-    og[3 * n + l] = op_geom(t.ro * t.K2, t.I, t.ri);       // HOOI  : RIGHT of P (r_out K2 x I)
+    og[0 * n + l] = OpGeom(t.O, t.K2 * t.I, t.ro);        // init  : LEFT  of T (O x K2 I)
+    og[1 * n + l] = OpGeom(t.O * t.K2, t.I, t.ri);        // init  : RIGHT of T (O K2 x I)
+    og[2 * n + l] = OpGeom(t.O, t.K2 * t.ri, t.ro);       // HOOI  : LEFT  of P (O x K2 r_in)
+    og[3 * n + l] = OpGeom(t.ro * t.K2, t.I, t.ri);       // HOOI  : RIGHT of P (r_out K2 x I)
     size_t xtb = 0, gpb = 0, vsb = 0, npad = 0;
     for (int k = 0; k < 4; ++k) {
       const OpGeom& g = og[k * n + l];
@@ -333,10 +284,10 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
   }
   P->resid_partial_off = ar.take(smap.size() * 8);
   P->sweep_desc_off = da.take(sd.size() * sizeof(SweepDesc));
-  put(P->sweep_desc_off, sd.data(), sd.size() * sizeof(SweepDesc));
+  if (img) img->put(P->sweep_desc_off, sd.data(), sd.size() * sizeof(SweepDesc));
   P->unfold.map_off = da.take(smap.size() * sizeof(BlockRef));
   P->unfold.nblocks = (int)smap.size();
-  put(P->unfold.map_off, smap.data(), smap.size() * sizeof(BlockRef));
+  if (img) img->put(P->unfold.map_off, smap.data(), smap.size() * sizeof(BlockRef));
   P->fold = P->unfold;
 
   // ---- small per-layer tables: tolerances, pointer / length lists of the norm kernel ----
@@ -350,11 +301,16 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
       pT[l] = (const float*)dev(t.T); nT[l] = t.numel;
       pC[l] = (const float*)dev(t.C); nC[l] = (int64_t)t.ro * t.K2 * t.ri;
     }
-    P->tol_off = da.take((size_t)n * 4);   put(P->tol_off, tol.data(), (size_t)n * 4);
-    P->ptrT_off = da.take((size_t)n * 8);  put(P->ptrT_off, pT.data(), (size_t)n * 8);
-    P->ptrC_off = da.take((size_t)n * 8);  put(P->ptrC_off, pC.data(), (size_t)n * 8);
-    P->numT_off = da.take((size_t)n * 8);  put(P->numT_off, nT.data(), (size_t)n * 8);
-    P->numC_off = da.take((size_t)n * 8);  put(P->numC_off, nC.data(), (size_t)n * 8);
+    auto table = [&](const void* src, size_t bytes) {
+      const size_t o = da.take(bytes);
+      if (img) img->put(o, src, bytes);
+      return o;
+    };
+    P->tol_off = table(tol.data(), (size_t)n * 4);
+    P->ptrT_off = table(pT.data(), (size_t)n * 8);
+    P->ptrC_off = table(pC.data(), (size_t)n * 8);
+    P->numT_off = table(nT.data(), (size_t)n * 8);
+    P->numC_off = table(nC.data(), (size_t)n * 8);
   }
 
   // ---- the four "leading singular vectors" phases ----
@@ -364,21 +320,11 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
     std::vector<GramDesc> gd(n);
     std::vector<EigDesc> ed(n);
     std::vector<GemmDesc> xg(n);
-    std::vector<BlockRef> m_gp, m_gr, m_tick, m_self, m_norm, m_ext, m_xg;
+    std::vector<BlockRef> m_gp, m_gr, m_xg;
     std::vector<int> gp_cost(n);
-    v.players.assign(n, 0);
     v.players_n.assign(n, 0);
-    v.ld_max = 0;
-    v.npad_max = 0;
     v.warm = false;
     v.big.clear();
-    for (int l = 0; l < n; ++l) {
-      v.ld_max = std::max(v.ld_max, og[k * n + l].ld);
-      v.npad_max = std::max(v.npad_max, og[k * n + l].Npad);
-    }
-    v.mode = choose_jacobi_mode(v.ld_max);
-    v.tick_lds = v.mode == 1 ? jacobi_tick2_lds_bytes(v.ld_max) : jacobi_tick_lds_bytes(v.ld_max);
-    v.gsteps = 0;
     for (int l = 0; l < n; ++l) {
       const TLayer& t = P->L[l];
       const OpGeom& g = og[k * n + l];
@@ -387,7 +333,7 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
       const int r_full = want_left ? t.ro : t.ri;
       GramDesc& q = gd[l];
       memset(&q, 0, sizeof q);
-      q.A = A; q.m = g.m; q.n = g.n; q.trans = g.trans ? 1 : 0; q.N = g.N; q.K = g.trans ? g.m : g.n;
+      q.A = A; q.m = g.m; q.n = (int)g.cols; q.trans = g.trans ? 1 : 0; q.N = g.N; q.K = g.trans ? g.m : (int)g.cols;
       q.nt = g.nt; q.ksplit = g.ksplit; q.kchunk = g.kchunk;
       q.partial = (double*)dev(t.gpart); q.G = (double*)dev(t.XT); q.Npad = g.Npad; q.ld = g.ld;
       const int ntp = g.nt * (g.nt + 1) / 2;
@@ -430,20 +376,13 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
         bw.nblocks = (int)m64.size();
         bw.desc_off = da.take(sizeof(DgemmDesc));
         bw.map_off = da.take(m64.size() * sizeof(BlockRef));
-        put(bw.desc_off, &dg, sizeof dg);
-        put(bw.map_off, m64.data(), m64.size() * sizeof(BlockRef));
+        if (img) img->put(bw.desc_off, &dg, sizeof dg);
+        if (img) img->put(bw.map_off, m64.data(), m64.size() * sizeof(BlockRef));
         v.big.push_back(bw);
       }
       if (direct) { e.mode = 0; e.out_a = factor; e.ldo = r_full; }
       else { e.mode = 3; e.out_a = (float*)dev(t.Vs); e.ldo = 0; }
-      const int units = v.mode >= 1 ? g.nb / 2 : g.nb;
-      v.players[l] = units;
       v.players_n[l] = g.N;
-      v.gsteps = std::max(v.gsteps, units - 1);
-      for (int b = 0; b < units / 2; ++b) m_tick.push_back(BlockRef{l, b});
-      if (v.mode >= 2) for (int b = 0; b < units; ++b) m_self.push_back(BlockRef{l, b});
-      for (int b = 0; b < (g.Npad + 3) / 4; ++b) m_norm.push_back(BlockRef{l, b});
-      for (int b = 0; b < (g.r_eff + 3) / 4; ++b) m_ext.push_back(BlockRef{l, b});
       // the other side: factor = A * (V / sigma)  |  A^T * (U / sigma)
       GemmDesc& x = xg[l];
       memset(&x, 0, sizeof x);
@@ -452,33 +391,19 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
         x.N = g.r_eff; x.b_rs = g.r_eff; x.b_cs = 1; x.c_rs = r_full; x.c_cs = 1;
         x.alpha = 1.f; x.beta = 0.f;
         x.A = A;
-        if (want_left) { x.M = g.m; x.K = g.n; x.a_rs = g.n; x.a_cs = 1; }     // (m x n)(n x r)
-        else { x.M = g.n; x.K = g.m; x.a_rs = 1; x.a_cs = g.n; }                // (n x m)(m x r)
-        x.tiles_m = (x.M + kGemmBM - 1) / kGemmBM; x.tiles_n = (x.N + kGemmBN - 1) / kGemmBN;
-        for (int b = 0; b < x.tiles_m * x.tiles_n; ++b) m_xg.push_back(BlockRef{l, b});
+        const int gn = (int)g.cols;
+        if (want_left) { x.M = g.m; x.K = gn; x.a_rs = gn; x.a_cs = 1; }       // (m x n)(n x r)
+        else { x.M = gn; x.K = g.m; x.a_rs = 1; x.a_cs = gn; }                  // (n x m)(m x r)
+        gemm_tiles(x, l, m_xg);
       }
     }
     std::stable_sort(m_gp.begin(), m_gp.end(),
                      [&](const BlockRef& a, const BlockRef& b) { return gp_cost[a.prob] > gp_cost[b.prob]; });
-    xcd_group(m_tick);
-    xcd_group(m_self);
-    place(v.gram_p, gd.data(), gd.size() * sizeof(GramDesc), m_gp);
-    v.gram_r = v.gram_p;
-    v.gram_r.map_off = da.take(std::max<size_t>(m_gr.size() * sizeof(BlockRef), 16));
-    v.gram_r.nblocks = (int)m_gr.size();
-    put(v.gram_r.map_off, m_gr.data(), m_gr.size() * sizeof(BlockRef));
-    place(v.tick, ed.data(), ed.size() * sizeof(EigDesc), m_tick);
-    v.eig_desc_off = v.tick.desc_off;
-    auto extra = [&](Group& g, const std::vector<BlockRef>& m) {
-      g = v.tick;
-      g.map_off = da.take(std::max<size_t>(m.size() * sizeof(BlockRef), 16));
-      g.nblocks = (int)m.size();
-      put(g.map_off, m.data(), m.size() * sizeof(BlockRef));
-    };
-    extra(v.self, m_self);
-    extra(v.norm, m_norm);
-    extra(v.ext, m_ext);
-    place(v.xg, xg.data(), xg.size() * sizeof(GemmDesc), m_xg);
+    place_phase(v.gram_p, da, img, gd.data(), gd.size() * sizeof(GramDesc), n, m_gp);
+    place_map_like(v.gram_r, v.gram_p, da, img, m_gr);
+    build_eig_layout(v.eig, ed, false, da, img);     // (all four phases keep per-problem sweep periods)
+    v.eig.prev_off = P->prev_off;
+    place_phase(v.xg, da, img, xg.data(), xg.size() * sizeof(GemmDesc), n, m_xg);
   }
 
   // ---- the five GEMM phases ----
@@ -505,10 +430,9 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
         default: x.A = Uo; x.M = t.O; x.K = t.ro; x.a_rs = t.ro; x.a_cs = 1;
                 x.B = Pb; x.N = (int)KI; x.b_rs = KI; x.b_cs = 1; x.C = T; x.c_rs = KI; x.c_cs = 1; break;
       }
-      x.tiles_m = (x.M + kGemmBM - 1) / kGemmBM; x.tiles_n = (x.N + kGemmBN - 1) / kGemmBN;
-      for (int b = 0; b < x.tiles_m * x.tiles_n; ++b) m.push_back(BlockRef{l, b});
+      gemm_tiles(x, l, m);
     }
-    place(P->gemm[k], g.data(), g.size() * sizeof(GemmDesc), m);
+    place_phase(P->gemm[k], da, img, g.data(), g.size() * sizeof(GemmDesc), n, m);
   }
   *desc_bytes = align_up(da.off, 4096);
   *total_bytes = ar.off;
@@ -568,11 +492,11 @@ int tadmm_tucker_create(tadmm_handle h, int n_layers, const tadmm_layer_desc* de
   if (rc != TADMM_OK) { delete P; return rc; }
   if (!workspace || workspace_bytes < tb) { delete P; CTX_FAIL(h, TADMM_ERR_WORKSPACE, "Tucker workspace too small: need %zu bytes", tb); }
   P->ws = (char*)workspace; P->ws_bytes = workspace_bytes; P->desc_bytes = db;
-  std::vector<char> img;
+  HostImage img;
   size_t db2 = 0, tb2 = 0;
   rc = tucker_layout(P, P->ws, W, U, Z, &img, db, &db2, &tb2);
   if (rc != TADMM_OK) { delete P; return rc; }
-  hipError_t e = hipMemcpy(P->ws, img.data(), img.size(), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(P->ws, img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = P->poll.create((size_t)std::max(1, n_layers));
   if (e == hipSuccess) e = P->hooi.create((size_t)std::max(1, n_layers));
   if (e != hipSuccess) {
@@ -603,16 +527,9 @@ int tadmm_tucker_run(tadmm_tucker_plan p, int update_u, int use_u, double* resid
   auto run_lsv = [&](Lsv& v, const int32_t* sk) -> int {
     launch_gram_partial((const GramDesc*)D(v.gram_p.desc_off), (const BlockRef*)D(v.gram_p.map_off), v.gram_p.nblocks, s, sk);
     launch_gram_reduce((const GramDesc*)D(v.gram_r.desc_off), (const BlockRef*)D(v.gram_r.map_off), v.gram_r.nblocks, s, sk);
-    const EigDesc* ed = (const EigDesc*)D(v.eig_desc_off);
-    EigGroup eg;
-    eg.ed = ed; eg.neig = n; eg.players = v.players.data(); eg.gsteps = v.gsteps; eg.mode = v.mode;
-    eg.ld_max = v.ld_max; eg.tick_lds = v.tick_lds;
-    eg.tick_map = (const BlockRef*)D(v.tick.map_off); eg.tick_blocks = v.tick.nblocks;
-    eg.self_map = (const BlockRef*)D(v.self.map_off); eg.self_blocks = v.self.nblocks;
-    eg.prev_dev = (double*)D(p->prev_off);
+    const EigDesc* ed = (const EigDesc*)D(v.eig.tick.desc_off);
+    EigGroup eg = v.eig.group(ws, sk);
     eg.off_dev = (const double*)D(p->off_off); eg.done_dev = (const int*)D(p->done_off);
-    eg.skip = sk;
-    eg.npad_max = v.npad_max;
     eg.warm = v.warm;
     if (!v.big.empty())
       eg.after_init = [&](hipStream_t st) {
@@ -633,14 +550,13 @@ int tadmm_tucker_run(tadmm_tucker_plan p, int update_u, int use_u, double* resid
     const int rc = run_eig_group(h, eg, p->poll, p->jtol, p->inner, p->max_sweeps, p->debug, s, &gs, &small_pending, &p->jtm);
     if (rc != TADMM_OK) return rc;
     jac_sweeps += gs;
-    launch_eig_norms(ed, (const BlockRef*)D(v.norm.map_off), v.norm.nblocks, s, sk);
-    launch_eig_sort(ed, n, s, sk, v.npad_max);
+    v.eig.sort(ws, s, sk);
     for (const BigWarm& bw : v.big) {
       hipLaunchKernelGGL(bigwarm_check_kernel, dim3(1), dim3(256), 0, s, ed, bw.layer, sk, (int32_t*)D(bw.ok));
       hipLaunchKernelGGL(bigwarm_save_kernel, dim3((bw.Npad + 3) / 4), dim3(256), 0, s, ed, bw.layer, sk,
                          (const int32_t*)D(bw.ok), (double*)D(bw.V));
     }
-    launch_eig_extract(ed, (const BlockRef*)D(v.ext.map_off), v.ext.nblocks, s, sk);
+    v.eig.extract(ws, s, sk);
     launch_gemm((const GemmDesc*)D(v.xg.desc_off), (const BlockRef*)D(v.xg.map_off), v.xg.nblocks, s, sk);
     return small_pending ? check_small_group(h, eg, p->poll) : TADMM_OK;
   };
