@@ -247,6 +247,21 @@ int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* c, void* str
   return TADMM_OK;
 }
 
+// ---- k x k core convolution of the factorised layers (coreconv.hip; its weight gradient lives in wgrad.hip) ----
+int tadmm_core_conv_desc_bytes(void) { return (int)sizeof(tadmm_core_conv_desc); }
+
+int tadmm_core_conv_fwd(tadmm_handle h, const tadmm_core_conv_desc* d, void* stream_) {
+  DeviceGuard device_guard(h);
+  if (!h) return TADMM_ERR_INVALID;
+  return launch_core_conv(h, d, 0, (hipStream_t)stream_);
+}
+
+int tadmm_core_conv_dgrad(tadmm_handle h, const tadmm_core_conv_desc* d, void* stream_) {
+  DeviceGuard device_guard(h);
+  if (!h) return TADMM_ERR_INVALID;
+  return launch_core_conv(h, d, 1, (hipStream_t)stream_);
+}
+
 // ---- standalone Gram / eigh (tests, Tucker path) ----
 // ~256 Gram workgroups for the one problem of a launch (the plans, whose levels batch 15-30 problems, ask for 64 each
 // and cap the K chunk)

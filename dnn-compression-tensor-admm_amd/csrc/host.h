@@ -51,6 +51,10 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// core convolution (coreconv.hip): descriptor checks shared with its weight gradient (wgrad.hip), and the launch
+int core_conv_check(tadmm_ctx_s* h, const tadmm_core_conv_desc* c, bool need_planes, int planes_rows, int planes_cols);
+int launch_core_conv(tadmm_ctx_s* h, const tadmm_core_conv_desc* c, int transposed, hipStream_t s);
+
 struct Phase {  // one grouped launch: descriptor array + block map inside the device arena
   size_t desc_off = 0, map_off = 0;
   int nprob = 0, nblocks = 0;

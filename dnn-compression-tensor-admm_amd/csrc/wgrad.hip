@@ -402,6 +402,233 @@ int wgrad_vec(const void* p, int64_t step_elems, int esz) {
   return 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weight gradient of the k x k core convolution (coreconv.hip):
+//   dWc[r2][r1][ky][kx] = sum_{b, oy, ox} dY[b][r2][oy][ox] * X[b][r1][oy*sh - ph + ky*dh][ox*sw - pw + kx*dw]
+// The scheme above with t = (b, oy, ox), A = dY read by the image loader and B = X read by a TAP-SHIFTED image loader
+// (the pixel a tap reaches from output pixel t, zero outside the image); the tap is blockIdx.y, so every (tap, tile,
+// slice) is one workgroup and the result goes to dWc + tap with column stride kh * kw.  Same slices, same fold of the
+// accumulator every 1024 tokens, same fixed-order fp64 reduce.
+struct CoreWgradArgs {
+  WgradArgs g;                            // A = dY, B = X, C = dWc, M = R2, N = R1, hw = Ho * Wo, T = B * Ho * Wo
+  int32_t H, W, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw;
+};
+
+template <int P, int F, typename TIn> struct TapLoader {
+  using Base = WgradLoader<P, F, TIn, true>;
+  static constexpr int EPL = Base::EPL;
+  Base base;                              // its register image and its LDS store
+
+  __device__ __forceinline__ void load(const TIn* X, const CoreWgradArgs& d, int ky, int kx, int f0, int t0, int tend, int tid) {
+    const int nfeat = d.g.N;
+    const int64_t plane = (int64_t)d.H * d.W;
+#pragma unroll
+    for (int i = 0; i < Base::NU; ++i) {
+      const int v = tid + 256 * i;
+      const int c = f0 + v / (kWgKC / EPL);
+      const int t = t0 + (v % (kWgKC / EPL)) * EPL;
+      uint4 r = make_uint4(0, 0, 0, 0);
+      if (c < nfeat && t < tend) {
+        uint32_t b = (uint32_t)t / (uint32_t)d.g.hw;
+        const uint32_t p = (uint32_t)t - b * (uint32_t)d.g.hw;
+        int oy = (int)(p / (uint32_t)d.Wo), ox = (int)p - oy * d.Wo;
+        r = gather<TIn>([&](int j) -> uint32_t {                 // called for j = 0, 1, .. in order
+          const int iy = oy * d.sh - d.ph + ky * d.dh, ix = ox * d.sw - d.pw + kx * d.dw;
+          uint32_t e = 0u;
+          if (t + j < tend && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W)
+            e = raw_bits(X[((int64_t)b * nfeat + c) * plane + (int64_t)iy * d.W + ix]);
+          if (++ox == d.Wo) { ox = 0; if (++oy == d.Ho) { oy = 0; ++b; } }
+          return e;
+        });
+      }
+      base.regs[i][0] = r;
+    }
+  }
+  __device__ __forceinline__ void store(uint16_t* S, int tid) const { base.store(S, tid); }
+};
+
+template <int P, int TM, int TN, typename TIn>
+__global__ __launch_bounds__(256) void core_wgrad_kernel(const CoreWgradArgs cd) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
+  using SP = WgradSplit<TM, TN>;
+  constexpr int WM = SP::WM, WK = SP::WK, MS = SP::MS, NS = SP::NS, SUB = SP::SUB;
+  static_assert(wgrad_lds_bytes<P, TM, TN>() >= (size_t)4 * MS * NS * 1024, "k-split reduction reuses the tile image");
+  const WgradArgs& d = cd.g;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  const int wk = wave % WK, wm = (wave / WK) % WM, wn = wave / (WK * WM);
+  const int tile = blockIdx.x % d.tiles, slice = blockIdx.x / d.tiles;
+  const int tap = blockIdx.y, taps = cd.kh * cd.kw;
+  const int ky = tap / cd.kw, kx = tap - ky * cd.kw;
+  const int m0 = (tile / d.tiles_n) * TM, n0 = (tile % d.tiles_n) * TN;
+  const int c_begin = (int)((int64_t)slice * d.nchunks / d.slices);
+  const int c_end = (int)((int64_t)(slice + 1) * d.nchunks / d.slices);
+  const int tend = min(d.T, c_end * kWgKC);
+  const TIn* A = static_cast<const TIn*>(d.A);
+  const TIn* B = static_cast<const TIn*>(d.B);
+  uint16_t* As = lds;                                   // [P][TM][kWgLD]
+  uint16_t* Bs = lds + P * TM * kWgLD;                  // [P][TN][kWgLD]
+
+  float4v_t acc[NS][MS], tot[NS][MS];
+#pragma unroll
+  for (int ns = 0; ns < NS; ++ns)
+#pragma unroll
+    for (int ms = 0; ms < MS; ++ms) acc[ns][ms] = tot[ns][ms] = float4v_t{0.f, 0.f, 0.f, 0.f};
+
+  WgradLoader<P, TM, TIn, true> la;
+  TapLoader<P, TN, TIn> lb;
+  if (c_begin < c_end) {
+    la.load(A, 0, d.hw, d.M, m0, c_begin * kWgKC, tend, d.vec_a, tid);
+    lb.load(B, cd, ky, kx, n0, c_begin * kWgKC, tend, tid);
+  }
+  for (int c = c_begin; c < c_end; ++c) {
+    __syncthreads();                                    // the fragment reads of the previous chunk are done
+    la.store(As, tid);
+    lb.store(Bs, tid);
+    __syncthreads();
+    if (c + 1 < c_end) {                                // workgroup-uniform: the last trip requests nothing
+      la.load(A, 0, d.hw, d.M, m0, (c + 1) * kWgKC, tend, d.vec_a, tid);
+      lb.load(B, cd, ky, kx, n0, (c + 1) * kWgKC, tend, tid);
+    }
+#pragma unroll
+    for (int ks = 0; ks < kWgKC / 32 / WK; ++ks) {
+      bf16x8_t af[P][MS], bfr[P][NS];
+      wgrad_frags<P, MS, TM>(af, As, wm * MS, ks * WK + wk, r, q);
+      wgrad_frags<P, NS, TN>(bfr, Bs, wn * NS, ks * WK + wk, r, q);
+      mma_step<P, NS, MS>(bfr, af, acc);                // acc[ns][ms][e] = C[16 ms + 4 q + e][16 ns + r]
+    }
+    if (((c - c_begin) & (kWgFold - 1)) == kWgFold - 1) {
+#pragma unroll
+      for (int ns = 0; ns < NS; ++ns)
+#pragma unroll
+        for (int ms = 0; ms < MS; ++ms) {
+          tot[ns][ms] += acc[ns][ms];
+          acc[ns][ms] = float4v_t{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+  }
+#pragma unroll
+  for (int ns = 0; ns < NS; ++ns)
+#pragma unroll
+    for (int ms = 0; ms < MS; ++ms) tot[ns][ms] += acc[ns][ms];
+
+  if constexpr (WK > 1) {                               // k-split waves: summed by wave wk == 0 in the order 0, 1, ..
+    __syncthreads();
+    float4v_t* red = reinterpret_cast<float4v_t*>(lds);
+    if (wk != 0) {
+#pragma unroll
+      for (int ns = 0; ns < NS; ++ns)
+#pragma unroll
+        for (int ms = 0; ms < MS; ++ms) red[(wave * NS * MS + ns * MS + ms) * 64 + lane] = tot[ns][ms];
+    }
+    __syncthreads();
+    if (wk != 0) return;
+#pragma unroll
+    for (int k = 1; k < WK; ++k)
+#pragma unroll
+      for (int ns = 0; ns < NS; ++ns)
+#pragma unroll
+        for (int ms = 0; ms < MS; ++ms) tot[ns][ms] += red[((wave + k) * NS * MS + ns * MS + ms) * 64 + lane];
+  }
+
+#pragma unroll
+  for (int ns = 0; ns < NS; ++ns)
+#pragma unroll
+    for (int ms = 0; ms < MS; ++ms) {
+      const int gms = wm * MS + ms, gns = wn * NS + ns;
+      if (d.slices == 1) {
+        const int n = n0 + 16 * gns + r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int m = m0 + 16 * gms + 4 * q + e;
+          if (m < d.M && n < d.N) d.C[((int64_t)m * d.N + n) * taps + tap] = tot[ns][ms][e];
+        }
+      } else {
+        float4v_t* dst = reinterpret_cast<float4v_t*>(d.part) +
+                         ((((int64_t)tap * d.slices + slice) * d.tiles + tile) * SUB + gms * (TN / 16) + gns) * 64 + lane;
+        *dst = tot[ns][ms];
+      }
+    }
+}
+
+// wgrad_reduce_kernel with the tap as blockIdx.y: dWc[m][n][tap] = sum over the slices in the same fixed order, fp64.
+__global__ __launch_bounds__(256) void core_wgrad_reduce_kernel(const WgradArgs d, int TM, int TN, int taps) {
+  const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3;
+  const int j = threadIdx.x & 7, tap = blockIdx.y;
+  const int64_t total = (int64_t)d.M * d.N;
+  const bool valid = idx < total;
+  const int64_t id = valid ? idx : total - 1;
+  const int m = (int)(id / d.N), n = (int)(id - (int64_t)m * d.N);
+  const int sub_n = TN / 16, SUB = (TM / 16) * sub_n;
+  const int tile = (m / TM) * d.tiles_n + n / TN;
+  const int ml = m % TM, nl = n % TN;
+  const int64_t off = ((int64_t)tile * SUB + (ml / 16) * sub_n + nl / 16) * 256 + (((ml & 15) >> 2) * 16 + (nl & 15)) * 4 + (ml & 3);
+  const int64_t stride = (int64_t)d.tiles * SUB * 256;
+  const float* part = d.part + (int64_t)tap * d.slices * stride;
+  double s = 0.0;
+  for (int sl = j; sl < d.slices; sl += 8) s += (double)part[sl * stride + off];
+  s += __shfl_xor(s, 4, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 1, 64);
+  if (valid && j == 0) d.C[((int64_t)m * d.N + n) * taps + tap] = (float)s;
+}
+
+template <int P, int TM, int TN, typename TIn>
+hipError_t core_wgrad_launch(const CoreWgradArgs& a, hipStream_t s, size_t* lds_out) {
+  auto kern = core_wgrad_kernel<P, TM, TN, TIn>;
+  constexpr size_t lds = wgrad_lds_bytes<P, TM, TN>();
+  *lds_out = lds;
+  if (lds > 64 * 1024) {
+    static bool attr_done[64] = {false};
+    int devi = 0;
+    hipError_t e = hipGetDevice(&devi);
+    if (e != hipSuccess) return e;
+    if (!attr_done[devi & 63]) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      attr_done[devi & 63] = true;
+    }
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)a.g.tiles * a.g.slices, (unsigned)(a.kh * a.kw)), dim3(256), lds, s, a);
+  return hipGetLastError();
+}
+template <int P, typename TIn, int TM>
+hipError_t core_wgrad_launch_tn(const CoreWgradArgs& a, int TN, hipStream_t s, size_t* lds) {
+  if (TN == 64) return core_wgrad_launch<P, TM, 64, TIn>(a, s, lds);
+  if (TN == 32) return core_wgrad_launch<P, TM, 32, TIn>(a, s, lds);
+  return core_wgrad_launch<P, TM, 16, TIn>(a, s, lds);
+}
+template <int P, typename TIn>
+hipError_t core_wgrad_launch_tile(const CoreWgradArgs& a, int TM, int TN, hipStream_t s, size_t* lds) {
+  if (TM == 64) return core_wgrad_launch_tn<P, TIn, 64>(a, TN, s, lds);
+  if (TM == 32) return core_wgrad_launch_tn<P, TIn, 32>(a, TN, s, lds);
+  return core_wgrad_launch_tn<P, TIn, 16>(a, TN, s, lds);
+}
+
+// Tiles as for tadmm_wgrad; slices count the taps among the workgroups: a pure function of the descriptor's shapes.
+int core_wgrad_geom(tadmm_handle h, const tadmm_core_conv_desc* d, WgradGeom& g) {
+  const int rc = core_conv_check(h, d, false, 0, 0);
+  if (rc != TADMM_OK) return rc;
+  const int64_t T = (int64_t)d->B * d->Ho * d->Wo, taps = (int64_t)d->kh * d->kw;
+  if (T > INT32_MAX - 2 * kWgKC) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "core conv wgrad: %lld output pixels exceed the launch", (long long)T);
+  if (taps > 65535) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "core conv wgrad: %lld taps exceed the launch", (long long)taps);
+  g.TM = wgrad_tile(d->R2);
+  g.TN = wgrad_tile(d->R1);
+  g.tiles_m = (d->R2 + g.TM - 1) / g.TM;
+  g.tiles_n = (d->R1 + g.TN - 1) / g.TN;
+  const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+  if (tiles > kWgMaxTiles) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "core conv wgrad: %lld output tiles exceed the launch", (long long)tiles);
+  g.tiles = (int)tiles;
+  g.nchunks = (int)((T + kWgKC - 1) / kWgKC);
+  int64_t s = (kWgTargetWG + tiles * taps - 1) / (tiles * taps);
+  s = std::min<int64_t>(s, T / kWgMinSlice);
+  g.slices = (int)std::max<int64_t>(s, 1);
+  g.ws_bytes = g.slices > 1 ? (size_t)taps * g.slices * g.tiles * g.TM * g.TN * sizeof(float) : 0;
+  return TADMM_OK;
+}
+
 }  // namespace
 }  // namespace tadmm
 
@@ -456,6 +683,58 @@ int tadmm_wgrad(tadmm_handle h, const tadmm_wgrad_desc* d, void* workspace, size
   if (g.slices > 1) {
     const int64_t nb = ((int64_t)d->M * d->N * 8 + 255) / 256;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, s, a, g.TM, g.TN);
+  }
+  HIP_OK(h, hipGetLastError());
+  return TADMM_OK;
+}
+
+int tadmm_core_conv_wgrad_workspace_bytes(const tadmm_core_conv_desc* d, size_t* bytes, int* slices_out) {
+  if (!bytes) return TADMM_ERR_INVALID;
+  WgradGeom g;
+  const int rc = core_wgrad_geom(nullptr, d, g);
+  if (rc != TADMM_OK) return rc;
+  *bytes = g.ws_bytes;
+  if (slices_out) *slices_out = g.slices;
+  return TADMM_OK;
+}
+
+int tadmm_core_conv_wgrad(tadmm_handle h, const tadmm_core_conv_desc* d, float* dW, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  DeviceGuard device_guard(h);
+  if (!h) return TADMM_ERR_INVALID;
+  WgradGeom g;
+  const int rc = core_wgrad_geom(h, d, g);
+  if (rc != TADMM_OK) return rc;
+  if (!dW || ((uintptr_t)dW & 3)) CTX_FAIL(h, TADMM_ERR_INVALID, "core conv wgrad: dW is null or misaligned");
+  if (g.ws_bytes && (!workspace || workspace_bytes < g.ws_bytes))
+    CTX_FAIL(h, TADMM_ERR_WORKSPACE, "core conv wgrad workspace too small: need %zu bytes, got %zu", g.ws_bytes, workspace_bytes);
+  if (g.ws_bytes && ((uintptr_t)workspace & 15)) CTX_FAIL(h, TADMM_ERR_INVALID, "core conv wgrad: workspace must be 16-byte aligned");
+  const int esz = d->dtype == TADMM_CHAIN_F32 ? 4 : 2;
+  const int hwo = d->Ho * d->Wo;
+  CoreWgradArgs a;
+  memset(&a, 0, sizeof a);
+  a.g.A = d->Y; a.g.B = d->X; a.g.C = dW; a.g.part = (float*)workspace;
+  a.g.T = (int32_t)((int64_t)d->B * hwo); a.g.M = d->R2; a.g.N = d->R1; a.g.hw = hwo; a.g.ldc = d->R1;
+  a.g.tiles_n = g.tiles_n; a.g.tiles = g.tiles; a.g.slices = g.slices; a.g.nchunks = g.nchunks;
+  a.g.vec_a = wgrad_vec(d->Y, hwo, esz);
+  a.g.alpha = 1.f;
+  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kh = d->kh; a.kw = d->kw; a.sh = d->stride_h; a.sw = d->stride_w;
+  a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
+  const hipStream_t s = (hipStream_t)stream;
+  const int taps = d->kh * d->kw;
+  if (a.g.T == 0) {                                      // B == 0: the sum over nothing
+    HIP_OK(h, hipMemsetAsync(dW, 0, (size_t)d->R2 * d->R1 * taps * sizeof(float), s));
+    return TADMM_OK;
+  }
+  size_t lds = 0;
+  const hipError_t e = d->dtype == TADMM_CHAIN_F32 ? core_wgrad_launch_tile<3, float>(a, g.TM, g.TN, s, &lds)
+                                                   : core_wgrad_launch_tile<1, uint16_t>(a, g.TM, g.TN, s, &lds);
+  if (e != hipSuccess)
+    CTX_FAIL(h, TADMM_ERR_HIP, "core conv wgrad: launch of the %d x %d tile kernel (%zu bytes of LDS) failed: %s", g.TM, g.TN,
+             lds, hipGetErrorString(e));
+  if (g.slices > 1) {
+    const int64_t nb = ((int64_t)d->R2 * d->R1 * 8 + 255) / 256;
+    hipLaunchKernelGGL(core_wgrad_reduce_kernel, dim3((unsigned)nb, (unsigned)taps), dim3(256), 0, s, a.g, g.TM, g.TN, taps);
   }
   HIP_OK(h, hipGetLastError());
   return TADMM_OK;

@@ -96,6 +96,17 @@ class WgradDesc(C.Structure):
         ("hw", C.c_int32), ("dtype", C.c_int32), ("alpha", C.c_float), ("reserved", C.c_int32),
     ]
 
+
+class CoreConvDesc(C.Structure):
+    _fields_ = [
+        ("X", C.c_void_p), ("Y", C.c_void_p), ("Wc", C.c_void_p), ("wc_plane", C.c_int64),
+        ("B", C.c_int32), ("R1", C.c_int32), ("R2", C.c_int32),
+        ("H", C.c_int32), ("W", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
+        ("stride_h", C.c_int32), ("stride_w", C.c_int32), ("pad_h", C.c_int32), ("pad_w", C.c_int32),
+        ("dil_h", C.c_int32), ("dil_w", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols include/tadmm.h declares
 ABI = {
     "tadmm_version": (C.c_int, []),
@@ -161,6 +172,13 @@ ABI = {
     "tadmm_wgrad_desc_bytes": (C.c_int, []),
     "tadmm_wgrad_workspace_bytes": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "tadmm_wgrad": (C.c_int, [C.c_void_p, C.POINTER(WgradDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tadmm_core_conv_desc_bytes": (C.c_int, []),
+    "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
+    "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
+    "tadmm_core_conv_wgrad_workspace_bytes": (C.c_int, [C.POINTER(CoreConvDesc), C.POINTER(C.c_size_t),
+                                                        C.POINTER(C.c_int)]),
+    "tadmm_core_conv_wgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
     "tadmm_gram_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_gram_ld": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tadmm_gram_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -235,6 +253,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_orth_desc layout mismatch")
         if lib.tadmm_wgrad_desc_bytes() != C.sizeof(WgradDesc):
             raise TadmmLibraryError(f"{path}: tadmm_wgrad_desc layout mismatch")
+        if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         _lib = lib
         return lib
 

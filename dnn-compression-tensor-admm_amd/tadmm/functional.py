@@ -110,7 +110,7 @@ def param_key(*params):
 
 class InferenceCacheMixin:
     """Inference-only caches of the factorised layers (contracted factors, packed bf16 planes): see `param_key`."""
-    _CACHE_ATTRS = ("_chain_cache", "_plane_cache", "_fused_cache")
+    _CACHE_ATTRS = ("_chain_cache", "_plane_cache", "_fused_cache", "_core_cache")
 
     def invalidate_caches(self):
         for a in self._CACHE_ATTRS:
@@ -305,3 +305,71 @@ def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias
             planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
         return ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
     return _Conv1x1Chain.apply(x.contiguous(), w_in, w_out, bias, planes)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The k x k core convolution between the two 1x1 stages (csrc/coreconv.hip, csrc/wgrad.hip): forward, data gradient
+# (the same kernel with a transposed gather) and weight gradient (split over batch * output pixels, deterministic).
+# ---------------------------------------------------------------------------------------------------------------
+class _CoreConv(torch.autograd.Function):
+    """y = conv2d(x, core) with groups = 1 on NCHW images in place; core (r2, r1, kh, kw)."""
+
+    @staticmethod
+    def forward(ctx, x, core, stride, padding, dilation, planes):
+        if not x.is_cuda:
+            raise TadmmError(-1, "core conv operands must live on the HIP device (no CPU fallback)")
+        fresh = planes is None                      # planes packed for this call only: keep them out of the launch memo
+        if fresh:
+            planes = ops.conv_core_planes(core, _nplanes(x))
+        y = ops.core_conv(x, planes, core.shape[0], core.shape[2:], stride, padding, dilation, memo=not fresh)
+        ctx.save_for_backward(x, core)
+        ctx.geom = (tuple(core.shape[2:]), stride, padding, dilation)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, core = ctx.saved_tensors
+        ksize, stride, padding, dilation = ctx.geom
+        g = g.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:                 # dX: the same kernel, transposed gather, planes of the transposed core
+            gx = ops.core_conv_dgrad(g, ops.conv_core_planes(core.permute(1, 0, 2, 3), _nplanes(g)), x.shape, ksize,
+                                     stride, padding, dilation, memo=False)
+        if ctx.needs_input_grad[1]:                 # dWc over (batch, output pixel), float32, cast to the parameter's dtype
+            gw = ops.core_conv_wgrad(g, x, ksize, stride, padding, dilation).to(core.dtype)
+        return gx, gw, None, None, None, None
+
+
+def core_conv(x: torch.Tensor, core: torch.Tensor, stride=1, padding=0, dilation=1, cache: dict = None):
+    """(B, r1, H, W) -> (B, r2, Ho, Wo): `F.conv2d(x, core, None, stride, padding, dilation, 1)` on the native kernel
+    (`tadmm_core_conv_fwd` / `_dgrad` / `_wgrad`).  Differentiable.  `cache` (a dict owned by the layer): in inference
+    the packed planes are reused until the core's version counter or storage address changes (`param_key`)."""
+    if x.dim() != 4 or core.dim() != 4 or x.shape[1] != core.shape[1]:
+        raise ValueError("core_conv expects an NCHW image and a (r2, r1, kh, kw) core with r1 = the image's channels")
+    stride, padding, dilation = ops._pair(stride), ops._pair(padding), ops._pair(dilation)
+    if _needs_grad(x, core):
+        return _CoreConv.apply(x.contiguous(), core, stride, padding, dilation, None)
+    n = _nplanes(x)
+    planes = None
+    if cache is not None:
+        key = ("core", n, x.device, param_key(core), tuple(core.shape))
+        if cache.get("core_key") != key:
+            cache.update(core_key=key, core_planes=ops.conv_core_planes(core, n))
+        planes = cache["core_planes"]
+    fresh = planes is None
+    if fresh:
+        planes = ops.conv_core_planes(core, n)
+    return ops.core_conv(x, planes, core.shape[0], core.shape[2:], stride, padding, dilation, memo=not fresh)
+
+
+
+def core_conv_routed(layer, x: torch.Tensor):
+    """`core_conv` of a factorised layer's `core_kernel` when `ops.core_conv_pays` routes it to the native kernel (its
+    planes cached on the layer in inference), else None: the caller keeps the device library's conv2d."""
+    core = layer.core_kernel
+    grad = _needs_grad(x, core)
+    if layer.groups != 1 or not ops.core_conv_pays(x, core.shape[0], layer.kernel_size, layer.stride, layer.padding,
+                                                    layer.dilation, layer.groups, training=grad):
+        return None
+    cache = None if grad else layer.__dict__.setdefault("_core_cache", {})
+    return core_conv(x, core, layer.stride, layer.padding, layer.dilation, cache=cache)

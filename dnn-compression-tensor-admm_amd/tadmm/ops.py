@@ -699,6 +699,164 @@ def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch
     return y
 
 
+# ------------------------------------------------------------------ k x k core convolution (csrc/coreconv.hip)
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def _conv_out_hw(h: int, w: int, kernel_size, stride, padding, dilation):
+    ho = (h + 2 * padding[0] - dilation[0] * (kernel_size[0] - 1) - 1) // stride[0] + 1
+    wo = (w + 2 * padding[1] - dilation[1] * (kernel_size[1] - 1) - 1) // stride[1] + 1
+    return ho, wo
+
+
+def core_conv_fits(x: torch.Tensor, r2: int, kernel_size, stride, padding, dilation, groups: int = 1) -> bool:
+    """True when the native core convolution (csrc/coreconv.hip) takes this call: a 4-D float32 or bfloat16 input,
+    groups == 1 and a non-empty output plane.  Neither the plane's width nor a rank bounds it.  Host-only shape logic."""
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or groups != 1 or r2 <= 0 or x.shape[1] <= 0:
+        return False
+    k, s, p, dl = _pair(kernel_size), _pair(stride), _pair(padding), _pair(dilation)
+    if min(k) <= 0 or min(s) <= 0 or min(dl) <= 0 or min(p) < 0 or x.shape[2] <= 0 or x.shape[3] <= 0:
+        return False
+    ho, wo = _conv_out_hw(x.shape[2], x.shape[3], k, s, p, dl)
+    return ho > 0 and wo > 0
+
+
+def core_conv_pays(x: torch.Tensor, r2: int, kernel_size, stride, padding, dilation, groups: int = 1,
+                   training: bool = False) -> bool:
+    """True when the layers route their k x k core convolution to `core_conv` instead of the device library's conv2d:
+    bfloat16 inference only.  Measured (scripts/bench_core_conv.py) on the 30 distinct 3 x 3 core
+    shapes of resnet18_tt 2x, resnet50_tt 3x, tk_resnet50 3x and tk_resnet32 3x: the bf16 forward is ahead of the library
+    beyond its round-to-round spread at all 30 (1.05x - 3.6x).  The fp32 forward (three planes, six MFMA products per
+    product) is ahead at 5, inside the spread at 4 and behind at 21 (0.46x - 1.9x) with no shape class that separates
+    them, and forward + backward (`training`: something the convolution reads wants a gradient) is behind at all 30 in
+    both dtypes (0.28x - 0.96x: the element-load tap-shifted weight gradient and the zero rows of the strided data
+    gradient): both keep the library."""
+    if not core_conv_fits(x, r2, kernel_size, stride, padding, dilation, groups):
+        return False
+    return x.dtype == torch.bfloat16 and not training
+
+
+def _core_conv_desc(x_shape, r2: int, dtype, kernel_size, stride, padding, dilation):
+    B, r1, H, W = x_shape
+    k, s, p, dl = _pair(kernel_size), _pair(stride), _pair(padding), _pair(dilation)
+    d = _cabi.CoreConvDesc()
+    d.dtype = _cabi.CHAIN_F32 if dtype == torch.float32 else _cabi.CHAIN_BF16
+    d.B, d.R1, d.R2, d.H, d.W = B, r1, r2, H, W
+    d.Ho, d.Wo = _conv_out_hw(H, W, k, s, p, dl)
+    d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = k + s + p + dl
+    return d
+
+
+def _core_conv_call(entry: str, src: torch.Tensor, planes: torch.Tensor, x_shape, r2: int, kernel_size, stride, padding,
+                    dilation, memo: bool):
+    """Forward (src = x, result y) or data gradient (src = dy, result dx) of the core convolution on x_shape inputs."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise TadmmError(-1, "core conv: tensors must live on a HIP device; there is no CPU path")
+    if src.dim() != 4 or src.dtype not in (torch.float32, torch.bfloat16):
+        raise TadmmError(-1, f"core conv: a float32 or bfloat16 NCHW image is needed (got {src.dim()}-D {src.dtype})")
+    if not src.is_contiguous():
+        src = src.contiguous()
+    fwd = entry == "tadmm_core_conv_fwd"
+    key = (entry, tuple(x_shape), r2, src.dtype, src.device, planes.data_ptr(), _pair(kernel_size), _pair(stride),
+           _pair(padding), _pair(dilation))
+    hit = _CHAIN_MEMO.lookup(key) if memo else None
+    if hit is None:
+        nplanes = 3 if src.dtype == torch.float32 else 1
+        d = _core_conv_desc(x_shape, r2, src.dtype, kernel_size, stride, padding, dilation)
+        rows, cols = (r2, x_shape[1]) if fwd else (x_shape[1], r2)
+        if (planes.dtype != torch.bfloat16 or planes.dim() != 5 or planes.shape[0] != nplanes or not planes.is_contiguous()
+                or planes.shape[1] * 16 < rows or planes.shape[2] != d.kh * d.kw * -(-cols // 32)):
+            raise TadmmError(-1, f"core conv: weights must be {nplanes} contiguous bf16 plane(s) of the tap-major core "
+                                 "(ops.conv_core_planes)")
+        if d.Ho <= 0 or d.Wo <= 0:
+            raise TadmmError(-1, "core conv: empty output plane")
+        d.Wc, d.wc_plane = planes.data_ptr(), planes[0].numel()
+        dev = src.device
+        h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+        y_shape = (x_shape[0], r2, d.Ho, d.Wo)
+        hit = (d, getattr(h.lib, entry), h, y_shape, planes)                    # the tuple keeps the planes alive
+        if memo:
+            _CHAIN_MEMO.store(key, hit)
+    d, fn, h, y_shape, _ = hit
+    if tuple(src.shape) != (tuple(x_shape) if fwd else y_shape):
+        raise TadmmError(-1, f"core conv: operand of shape {tuple(src.shape)} does not match the geometry")
+    out = torch.empty(y_shape if fwd else tuple(x_shape), dtype=src.dtype, device=src.device)
+    if fwd:
+        d.X, d.Y = src.data_ptr(), out.data_ptr()
+    else:
+        d.X, d.Y = out.data_ptr(), src.data_ptr()
+    if x_shape[0] > 0:
+        h.check(fn(h.ptr, C.byref(d), _stream(src.device)))
+    return out
+
+
+def core_conv(x: torch.Tensor, planes: torch.Tensor, r2: int, kernel_size, stride=1, padding=0, dilation=1,
+              memo: bool = True) -> torch.Tensor:
+    """y (B, r2, Ho, Wo) = conv2d(x (B, r1, H, W), core) with groups = 1, `planes = conv_core_planes(core, P)` (P = 3 for
+    float32, 1 for bfloat16): `tadmm_core_conv_fwd`, NCHW in place, any plane size and any rank."""
+    if isinstance(x, torch.Tensor) and x.dim() != 4:
+        raise TadmmError(-1, "core conv: x must be an NCHW image")
+    return _core_conv_call("tadmm_core_conv_fwd", x, planes, tuple(x.shape), r2, kernel_size, stride, padding, dilation, memo)
+
+
+def core_conv_dgrad(dy: torch.Tensor, planes_t: torch.Tensor, x_shape, kernel_size, stride=1, padding=0, dilation=1,
+                    memo: bool = True) -> torch.Tensor:
+    """dx (x_shape) of `core_conv` from dy (B, r2, Ho, Wo); `planes_t = conv_core_planes(core.permute(1, 0, 2, 3), P)` --
+    the kernel's transposed gather maps the taps, nothing is flipped (`tadmm_core_conv_dgrad`)."""
+    r2 = dy.shape[1] if isinstance(dy, torch.Tensor) and dy.dim() == 4 else 0
+    return _core_conv_call("tadmm_core_conv_dgrad", dy, planes_t, tuple(x_shape), r2, kernel_size, stride, padding,
+                           dilation, memo)
+
+
+def _core_wgrad_operands(dy, x, kernel_size, stride, padding, dilation):
+    for t, what in ((dy, "dy"), (x, "x")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TadmmError(-1, f"core conv wgrad: {what} must live on a HIP device; there is no CPU path")
+    if dy.dtype != x.dtype or x.dtype not in (torch.float32, torch.bfloat16) or dy.dim() != 4 or x.dim() != 4:
+        raise TadmmError(-1, f"core conv wgrad: two NCHW images of one dtype, float32 or bfloat16 (got {dy.dtype}, {x.dtype})")
+    if dy.device != x.device:
+        raise TadmmError(-1, f"core conv wgrad: operands on different devices ({dy.device}, {x.device})")
+    d = _core_conv_desc(tuple(x.shape), dy.shape[1], x.dtype, kernel_size, stride, padding, dilation)
+    if tuple(dy.shape) != (x.shape[0], dy.shape[1], d.Ho, d.Wo) or d.Ho <= 0 or d.Wo <= 0:
+        raise TadmmError(-1, f"core conv wgrad: dy of shape {tuple(dy.shape)} is not the output of x {tuple(x.shape)}")
+    dy = dy if dy.is_contiguous() else dy.contiguous()
+    x = x if x.is_contiguous() else x.contiguous()
+    d.X, d.Y = x.data_ptr(), dy.data_ptr()
+    return dy, x, d
+
+
+def core_conv_wgrad_plan(dy: torch.Tensor, x: torch.Tensor, kernel_size, stride=1, padding=0, dilation=1):
+    """(workspace bytes, slices) `core_conv_wgrad` will use: a pure function of the shapes."""
+    dy, x, d = _core_wgrad_operands(dy, x, kernel_size, stride, padding, dilation)
+    nbytes, slices = C.c_size_t(), C.c_int()
+    rc = _cabi.load().tadmm_core_conv_wgrad_workspace_bytes(C.byref(d), C.byref(nbytes), C.byref(slices))
+    if rc < 0:
+        raise TadmmError(rc, "tadmm_core_conv_wgrad_workspace_bytes: the launch does not take this shape")
+    return nbytes.value, slices.value
+
+
+def core_conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kernel_size, stride=1, padding=0, dilation=1,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dW (r2, r1, kh, kw) float32 of `core_conv` from dy (B, r2, Ho, Wo) and x (B, r1, H, W), both read in place
+    (`tadmm_core_conv_wgrad`): split over (batch, output pixel), deterministic.  `workspace`: a uint8 device tensor of at
+    least `core_conv_wgrad_plan(...)[0]` bytes to use instead of a fresh one."""
+    dy, x, d = _core_wgrad_operands(dy, x, kernel_size, stride, padding, dilation)
+    out = torch.empty(d.R2, d.R1, d.kh, d.kw, dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    dev = x.device
+    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    nbytes = C.c_size_t()
+    h.check(h.lib.tadmm_core_conv_wgrad_workspace_bytes(C.byref(d), C.byref(nbytes), None))
+    ws = workspace
+    if ws is None and nbytes.value:
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    h.check(h.lib.tadmm_core_conv_wgrad(h.ptr, C.byref(d), out.data_ptr(), None if ws is None else ws.data_ptr(),
+                                        0 if ws is None else ws.numel() * ws.element_size(), _stream(dev)))
+    return out
+
+
 # ------------------------------------------------------------------ Gram / eigh (tests, Tucker)
 def gram(a: torch.Tensor):
     """fp64 Gram of a float32 (m,n) matrix: A A^T if m<=n else A^T A.  Returns (N,N) float64."""

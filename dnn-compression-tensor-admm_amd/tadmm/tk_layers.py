@@ -10,7 +10,8 @@
 `dense_w` is decomposed by the device HOSVD+HOOI of `tadmm.tucker` (parity unpinned, see there):
 first = U_in^T, last = U_out, core = W x_0 U_out^T x_1 U_in^T  (TKConv.py:79-83).  The channel-mixing
 contractions run through `functional.mm` / `functional.linear` on the fp32 matrix cores; the k x k core
-conv is the device library's conv2d as in the reference.
+conv is the native kernel of csrc/coreconv.hip where `ops.core_conv_pays` routes it there, else the device library's
+conv2d as in the reference.
 """
 from __future__ import annotations
 
@@ -109,8 +110,10 @@ class TKConv2dC(_TKConvBase):
         p1 = None if grad else HF.planes_of(self.first_kernel.reshape(self.in_rank, self.in_channels), n, cache=cache,
                                             tag="first")
         f1 = HF.pointwise(x, w1, None, "tadmm_tucker_1x1", p1)
-        core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
-        f2 = F.conv2d(f1, core, None, self.stride, self.padding, self.dilation, self.groups)
+        f2 = HF.core_conv_routed(self, f1)                      # the native k x k kernel where it pays (csrc/coreconv.hip)
+        if f2 is None:
+            core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
+            f2 = F.conv2d(f1, core, None, self.stride, self.padding, self.dilation, self.groups)
         p3 = None if grad else HF.planes_of(w3, n, cache=cache, tag="last")
         f3 = HF.pointwise(f2, w3, self.bias, "tadmm_tucker_1x1", p3)
         return f1, f2, f3
@@ -194,8 +197,11 @@ class TKConv2dM(_TKConvBase):
         n = 1 if x.dtype == torch.bfloat16 else 3
         p1 = None if grad else HF.planes_of(self.first_factor, n, cache=cache, tag="first")
         out = HF.pointwise(x, self.first_factor, None, "tadmm_tucker_1x1", p1)
-        core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
-        out = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
+        mid = HF.core_conv_routed(self, out)
+        if mid is None:
+            core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
+            mid = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
+        out = mid
         p3 = None if grad else HF.planes_of(self.last_factor, n, cache=cache, tag="last")
         return HF.pointwise(out, self.last_factor, self.bias, "tadmm_tucker_1x1", p3)
 

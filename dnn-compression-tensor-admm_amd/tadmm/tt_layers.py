@@ -10,7 +10,8 @@
 
 Every contraction runs on the fp32 matrix cores through `functional.mm`; the one-shot decomposition of
 `dense_w` (the --decompose hand-off) runs the device TT-SVD of libtadmm_hip.so.  The k x k core conv
-is the stock conv2d of the device library, exactly as in the reference.
+is the native kernel of csrc/coreconv.hip where `ops.core_conv_pays` routes it there, else the stock conv2d of
+the device library.
 
 Deliberate deviation: the reference's TTConv2dM adds its (O,) bias to a (B,O,H,W) tensor
 (TTConv.py:150-151), i.e. broadcasts it along W and raises unless W == O.  Here the bias is added per
@@ -201,9 +202,11 @@ class TTConv2dM(_TTConvBase):
             return ops.conv_chain(x, f1, f2, f3, self.bias, self.out_channels, self.kernel_size, self.stride, self.padding,
                                   self.dilation)
         out = HF.pointwise(x, w_in, None, "tadmm_ttconv_chain_in", p_in)
-        core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
-        out = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
-        return HF.pointwise(out, w_out, self.bias, "tadmm_ttconv_chain_out", p_out)
+        mid = HF.core_conv_routed(self, out)                    # the native k x k kernel where it pays (csrc/coreconv.hip)
+        if mid is None:
+            core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
+            mid = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
+        return HF.pointwise(mid, w_out, self.bias, "tadmm_ttconv_chain_out", p_out)
 
     def forward_flops(self, x):                                   # TTConv.py:155-195
         out, tt_flops, (h2, w2) = self._chains(x, True)

@@ -350,6 +350,43 @@ typedef struct {
 int tadmm_conv_chain_desc_bytes(void);
 int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* d, void* stream);
 
+/* ---- k x k core convolution of the factorised layers (csrc/coreconv.hip, csrc/wgrad.hip) ---------------------------
+ * The convolution between the two 1x1 stages of TTConv2dM (TTConv.py:130-153) and TKConv2dC / TKConv2dM
+ * (TKConv.py:93-98, :210-214), groups = 1, on contiguous NCHW tensors in place; any plane size and any rank:
+ *   fwd    Y (B, R2, Ho, Wo) = conv(X (B, R1, H, W); Wc (R2, R1, kh, kw))       reads X, Wc planes; writes Y
+ *   dgrad  X (B, R1, H, W)   = the data gradient for Y = dY                      reads Y, Wc planes; writes X
+ *   wgrad  dW (R2, R1, kh, kw) float32, contiguous = the weight gradient         reads X and Y = dY; Wc is ignored
+ * X and Y are both of `dtype` (TADMM_CHAIN_F32: exact three-plane bf16 split, fp32-GEMM accuracy; TADMM_CHAIN_BF16: one
+ * plane), element aligned: 16-byte, 8-byte or element accesses as base and run length allow.
+ * Wc: fragment-major bf16 planes (3 for float32, 1 for bfloat16; plane p at Wc + p * wc_plane elements, 16-byte aligned)
+ * of the tap-major matrix, as for W2 of tadmm_conv_chain_desc: fwd takes the (R2 x kh*kw*R1p) matrix with column
+ * (ky*kw + kx)*R1p + c, R1p = R1 rounded up to 32 and rows rounded up to 32; dgrad takes the same packing of the
+ * transposed core (R1 x kh*kw*R2p) -- the kernel maps taps to source pixels itself, nothing is flipped
+ * (tadmm.ops.conv_core_planes builds both).
+ * wgrad splits the reduction over (batch, output pixel) into slices as tadmm_wgrad does, one workgroup per (tap, tile,
+ * slice): no atomics, bitwise reproducible, independent of what workspace and dW held before.  The workspace (16-byte
+ * aligned) is needed when there is more than one slice; tadmm_core_conv_wgrad_workspace_bytes is host only and a pure
+ * function of the descriptor's shapes.
+ * TADMM_ERR_INVALID: a non-positive extent, stride or dilation, negative padding or B, Ho / Wo that are not the output
+ * size of the geometry or an empty output plane, unknown dtype, a null or misaligned operand with B > 0, weight planes
+ * too small or misaligned (fwd, dgrad); TADMM_ERR_WORKSPACE: workspace too small; TADMM_ERR_UNSUPPORTED: planes of 2^31
+ * pixels and more, more than 4096 taps, 2^31 - 256 output pixels in the batch (wgrad), a halo beyond the LDS.  Nothing
+ * is launched in any of these cases.  B == 0 succeeds with nothing launched (wgrad writes zeros). */
+typedef struct {
+  void* X; void* Y;
+  const void* Wc;                             /* bf16 planes; ignored by wgrad */
+  int64_t wc_plane;                           /* elements */
+  int32_t B, R1, R2;
+  int32_t H, W, Ho, Wo, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 */
+} tadmm_core_conv_desc;
+int tadmm_core_conv_desc_bytes(void);
+int tadmm_core_conv_fwd(tadmm_handle h, const tadmm_core_conv_desc* d, void* stream);
+int tadmm_core_conv_dgrad(tadmm_handle h, const tadmm_core_conv_desc* d, void* stream);
+int tadmm_core_conv_wgrad_workspace_bytes(const tadmm_core_conv_desc* d, size_t* bytes, int* slices_out);
+int tadmm_core_conv_wgrad(tadmm_handle h, const tadmm_core_conv_desc* d, float* dW, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
