@@ -191,10 +191,10 @@ int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* s) { retu
 
 int tadmm_conv_chain_desc_bytes(void) { return (int)sizeof(tadmm_conv_chain_desc); }
 
-int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* c, void* stream_) {
-  DeviceGuard device_guard(h);
-  if (!h || !c) return TADMM_ERR_INVALID;
-  if (!c->X || !c->Y || !c->W1 || !c->W2 || !c->W3) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: null operand");
+// Extents, geometry and tiling shared by the forward, the data gradient and the host-only plan.  Fills the kernel's
+// descriptor in the roles of `mode` (forward: source = X on H x W, destination = Y on Ho x Wo; data gradient: source = dY
+// on Ho x Wo, destination = dX on H x W, the ranks and channel counts swapped) without touching an operand.
+static int conv_chain_shape(tadmm_handle h, const tadmm_conv_chain_desc* c, int mode, ConvChainDesc& d, size_t* lds) {
   if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: bad dtype");
   if (c->B < 0 || c->C <= 0 || c->Nout <= 0 || c->H <= 0 || c->W <= 0 || c->kh <= 0 || c->kw <= 0 || c->stride_h <= 0 ||
       c->stride_w <= 0 || c->dil_h <= 0 || c->dil_w <= 0 || c->pad_h < 0 || c->pad_w < 0)
@@ -202,48 +202,110 @@ int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* c, void* str
   const int ho = (c->H + 2 * c->pad_h - c->dil_h * (c->kh - 1) - 1) / c->stride_h + 1;
   const int wo = (c->W + 2 * c->pad_w - c->dil_w * (c->kw - 1) - 1) / c->stride_w + 1;
   if (ho != c->Ho || wo != c->Wo) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: output size does not match the geometry");
-  if (ho <= 0 || wo <= 0 || wo > 64) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: output rows of more than 64 pixels take the three-launch path");
+  if (mode == TADMM_CONV_CHAIN_FWD) {
+    if (ho <= 0 || wo <= 0 || wo > 64) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: output rows of more than 64 pixels take the three-launch path");
+  } else {
+    if (ho <= 0 || wo <= 0) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: empty output plane");
+    if (c->W > 64) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: input rows of more than 64 pixels take the three data-gradient launches");
+  }
   if (c->R1 <= 0 || c->R2 <= 0 || c->R1 % 32 || c->R2 % 32 || c->R1 > 256 || c->R2 > 256)
     CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: ranks must be padded to multiples of 32 and at most 256");
-  const int64_t taps = (int64_t)c->kh * c->kw;
-  if ((((uintptr_t)c->W1) & 15) || (((uintptr_t)c->W2) & 15) || (((uintptr_t)c->W3) & 15) || (((uintptr_t)c->bias) & 15) ||
-      c->w1_plane < (int64_t)(c->R1 / 16) * ((c->C + 31) / 32) * 512 || c->w2_plane < (int64_t)(c->R2 / 16) * taps * (c->R1 / 32) * 512 ||
-      c->w3_plane < (int64_t)((c->Nout + 15) / 16) * (c->R2 / 32) * 512)
-    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: weight planes too small or misaligned");
-  ConvChainDesc d;
   memset(&d, 0, sizeof d);
-  d.X = c->X; d.Y = c->Y; d.W1 = (const uint16_t*)c->W1; d.W2 = (const uint16_t*)c->W2; d.W3 = (const uint16_t*)c->W3;
-  d.bias = c->bias; d.w1_plane = c->w1_plane; d.w2_plane = c->w2_plane; d.w3_plane = c->w3_plane;
-  d.B = c->B; d.C = c->C; d.R1 = c->R1; d.R2 = c->R2; d.Nout = c->Nout;
-  d.H = c->H; d.W = c->W; d.Ho = ho; d.Wo = wo; d.kh = c->kh; d.kw = c->kw; d.sh = c->stride_h; d.sw = c->stride_w;
+  d.B = c->B; d.kh = c->kh; d.kw = c->kw; d.sh = c->stride_h; d.sw = c->stride_w;
   d.ph = c->pad_h; d.pw = c->pad_w; d.dh = c->dil_h; d.dw = c->dil_w;
-  {
-    // pixels per workgroup: 64, or 32 when the intermediates of 64 do not fit the LDS; output rows per workgroup: as many
-    // as give <= TM output pixels and a halo of <= 3 TM input pixels
-    const int planes = c->dtype == TADMM_CHAIN_F32 ? 3 : 1, kc = c->dtype == TADMM_CHAIN_F32 ? 64 : 128;
-    bool found = false;
-    for (int tmx = 64; tmx >= 32 && !found; tmx /= 2) {
-      if (wo > tmx) continue;
-      int tr = std::min(ho, tmx / wo), nt = 0;
-      for (; tr >= 1; --tr) {
-        const int irows = std::min(c->H, (tr - 1) * c->stride_h + (c->kh - 1) * c->dil_h + 1);
-        nt = (irows * c->W + tmx - 1) / tmx;
-        if (nt <= 3) break;
-      }
-      if (tr < 1) continue;
-      const size_t lds = ((size_t)2 * planes * tmx * (kc + 8) + (size_t)planes * tmx * nt * (c->R1 + 8) +
-                          (size_t)planes * tmx * (c->R2 + 8)) * 2;
-      if (lds > 160 * 1024) continue;
-      d.TM = tmx; d.TR = tr; d.tiles = (ho + tr - 1) / tr; d.NT = nt;
-      found = true;
-    }
-    if (!found) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: halo or intermediates do not fit the LDS");
+  if (mode == TADMM_CONV_CHAIN_FWD) {
+    d.C = c->C; d.R1 = c->R1; d.R2 = c->R2; d.Nout = c->Nout; d.H = c->H; d.W = c->W; d.Ho = ho; d.Wo = wo;
+  } else {
+    d.C = c->Nout; d.R1 = c->R2; d.R2 = c->R1; d.Nout = c->C; d.H = ho; d.W = wo; d.Ho = c->H; d.Wo = c->W; d.transposed = 1;
   }
+  if (!plan_tt_conv(d, c->dtype, lds)) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: halo or intermediates do not fit the LDS");
+  return TADMM_OK;
+}
+
+// weight planes of the kernel's three products, in the kernel's roles
+static bool conv_chain_planes_ok(const tadmm_conv_chain_desc* c, const ConvChainDesc& d) {
+  const int64_t taps = (int64_t)c->kh * c->kw;
+  return !((((uintptr_t)c->W1) & 15) || (((uintptr_t)c->W2) & 15) || (((uintptr_t)c->W3) & 15) ||
+           c->w1_plane < (int64_t)(d.R1 / 16) * ((d.C + 31) / 32) * 512 || c->w2_plane < (int64_t)(d.R2 / 16) * taps * (d.R1 / 32) * 512 ||
+           c->w3_plane < (int64_t)((d.Nout + 15) / 16) * (d.R2 / 32) * 512);
+}
+
+static void conv_chain_operands(const tadmm_conv_chain_desc* c, ConvChainDesc& d) {
+  d.X = c->X; d.Y = c->Y; d.W1 = (const uint16_t*)c->W1; d.W2 = (const uint16_t*)c->W2; d.W3 = (const uint16_t*)c->W3;
+  d.w1_plane = c->w1_plane; d.w2_plane = c->w2_plane; d.w3_plane = c->w3_plane;
   const int epl = c->dtype == TADMM_CHAIN_F32 ? 4 : 8;
-  d.x_vec = ((c->H * c->W) % epl == 0 && (((uintptr_t)c->X) & 15) == 0) ? 1 : 0;
+  d.x_vec = ((d.H * d.W) % epl == 0 && (((uintptr_t)c->X) & 15) == 0) ? 1 : 0;
+}
+
+int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* c, void* stream_) {
+  DeviceGuard device_guard(h);
+  if (!h || !c) return TADMM_ERR_INVALID;
+  if (!c->X || !c->Y || !c->W1 || !c->W2 || !c->W3) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: null operand");
+  ConvChainDesc d;
+  const int rc = conv_chain_shape(h, c, TADMM_CONV_CHAIN_FWD, d, nullptr);
+  if (rc != TADMM_OK) return rc;
+  if (!conv_chain_planes_ok(c, d) || (((uintptr_t)c->bias) & 15))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: weight planes too small or misaligned");
+  conv_chain_operands(c, d);
+  d.bias = c->bias;
   if (launch_tt_conv(d, c->dtype, (hipStream_t)stream_) != 0)
     CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: the intermediates do not fit the LDS");
   HIP_OK(h, hipGetLastError());
+  return TADMM_OK;
+}
+
+// forward with saved intermediates (mode FWD) and data gradient (mode BWD): statuses as tadmm_core_conv_*
+static int conv_chain_train(tadmm_handle h, const tadmm_conv_chain_desc* c, int mode, int r1, int r2, void* s1, void* s2,
+                            void* stream_) {
+  DeviceGuard device_guard(h);
+  if (!h) return TADMM_ERR_INVALID;
+  if (!c) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: null descriptor");
+  ConvChainDesc d;
+  const int rc = conv_chain_shape(h, c, mode, d, nullptr);
+  if (rc != TADMM_OK) return rc;
+  if (r1 <= 0 || r1 > c->R1 || r2 <= 0 || r2 > c->R2)
+    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: true ranks (%d, %d) outside (0, %d] x (0, %d]", r1, r2, c->R1, c->R2);
+  const bool bwd = mode == TADMM_CONV_CHAIN_BWD;
+  if (!bwd && (!s1 || !s2) && c->B > 0) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: null intermediate (H1, H2)");
+  if (bwd && (s1 == nullptr) != (s2 == nullptr)) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: dH1 and dH2 are saved together or not at all");
+  if (c->B > 0 && (!c->X || !c->Y || !c->W1 || !c->W2 || !c->W3)) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: null operand");
+  const uintptr_t esz = c->dtype == TADMM_CHAIN_F32 ? 4 : 2;
+  if (((uintptr_t)c->X | (uintptr_t)c->Y | (uintptr_t)s1 | (uintptr_t)s2) & (esz - 1))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: misaligned operand");
+  if (!conv_chain_planes_ok(c, d) || (!bwd && (((uintptr_t)c->bias) & 15)))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: weight planes too small or misaligned");
+  if (c->B == 0) return TADMM_OK;
+  conv_chain_operands(c, d);
+  d.bias = bwd ? nullptr : c->bias;
+  // S1 is product 1's tensor, S2 product 2's: H1, H2 forward; dH2, dH1 in the data gradient
+  d.S1 = bwd ? s2 : s1; d.S2 = bwd ? s1 : s2;
+  d.r1t = bwd ? r2 : r1; d.r2t = bwd ? r1 : r2;
+  if (launch_tt_conv(d, c->dtype, (hipStream_t)stream_) != 0)
+    CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: the intermediates do not fit the LDS");
+  HIP_OK(h, hipGetLastError());
+  return TADMM_OK;
+}
+
+int tadmm_ttconv_fused_save(tadmm_handle h, const tadmm_conv_chain_desc* d, int r1, int r2, void* H1, void* H2, void* stream) {
+  return conv_chain_train(h, d, TADMM_CONV_CHAIN_FWD, r1, r2, H1, H2, stream);
+}
+
+int tadmm_ttconv_fused_bwd(tadmm_handle h, const tadmm_conv_chain_desc* d, int r1, int r2, void* dH1, void* dH2, void* stream) {
+  return conv_chain_train(h, d, TADMM_CONV_CHAIN_BWD, r1, r2, dH1, dH2, stream);
+}
+
+int tadmm_ttconv_fused_plan(const tadmm_conv_chain_desc* c, int mode, int* tile_pixels, int* tile_rows, int* halo_tiles,
+                            int* tiles_per_image, size_t* lds_bytes) {
+  if (!c || (mode != TADMM_CONV_CHAIN_FWD && mode != TADMM_CONV_CHAIN_BWD)) return TADMM_ERR_INVALID;
+  ConvChainDesc d;
+  size_t lds = 0;
+  const int rc = conv_chain_shape(nullptr, c, mode, d, &lds);
+  if (rc != TADMM_OK) return rc;
+  if (tile_pixels) *tile_pixels = d.TM;
+  if (tile_rows) *tile_rows = d.TR;
+  if (halo_tiles) *halo_tiles = d.NT;
+  if (tiles_per_image) *tiles_per_image = d.tiles;
+  if (lds_bytes) *lds_bytes = lds;
   return TADMM_OK;
 }
 

@@ -182,6 +182,36 @@ __device__ __forceinline__ void load_x(bf16x8_t (&a)[P][TM / 16], const uint16_t
       a[p][mt] = *reinterpret_cast<const bf16x8_t*>(&img[(p * TM + 16 * mt + r) * ld + 32 * kloc + 8 * q]);
 }
 
+// ---- tap <-> pixel maps of a convolution axis (coreconv.hip, convchain.hip).  transposed 0: destination = output
+// coordinate, source = input coordinate; 1: the data gradient's map (destination = input, source = output)
+// first and last source coordinate that destination coordinates [t0, t0 + n) reach over all taps of one axis
+__device__ __host__ inline void halo_range(int transposed, int t0, int n, int k, int s, int p, int dl, int lim, int& lo, int& hi) {
+  if (!transposed) {
+    lo = t0 * s - p;
+    hi = (t0 + n - 1) * s - p + (k - 1) * dl;
+  } else {
+    const int a = t0 + p - (k - 1) * dl, b = t0 + n - 1 + p;
+    lo = a <= 0 ? 0 : (a + s - 1) / s;
+    hi = b < 0 ? -1 : b / s;
+  }
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > lim - 1 ? lim - 1 : hi;
+}
+
+// source coordinate of destination coordinate t under tap j of one axis, or -1
+__device__ __host__ inline int tap_src(int transposed, int t, int j, int s, int p, int dl, int lim) {
+  int v;
+  if (!transposed) {
+    v = t * s - p + j * dl;
+  } else {
+    const int num = t + p - j * dl;
+    if (num < 0) return -1;
+    v = num / s;
+    if (v * s != num) return -1;
+  }
+  return (v >= 0 && v < lim) ? v : -1;
+}
+
 #ifdef TADMM_CHAIN_STAMPS
 #define STAMP()                                                                                                  \
   do {                                                                                                           \

@@ -191,8 +191,17 @@ struct ConvChainDesc {
   int32_t H, W, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw;
   int32_t TM, TR, tiles, NT;                                    // pixels per workgroup (64 | 32), its output rows, tiles per image, TM-pixel tiles of its halo
   int32_t x_vec;
+  // data-gradient mode (transposed gather): X = dY on the plane H x W, Y = dX on the plane Ho x Wo, W1 / W2 / W3 the
+  // planes of W3^T / the transposed core / W1^T, (sh, ph, dh, ...) still the FORWARD convolution's geometry
+  int32_t transposed;
+  // saved intermediates (both or neither): S1 (B, r1t, H, W) = product 1, S2 (B, r2t, Ho, Wo) = product 2, of X's dtype
+  void* S1; void* S2;
+  int32_t r1t, r2t;                                             // true ranks (<= R1, R2)
 };
 int launch_tt_conv(const ConvChainDesc& d, int dtype, hipStream_t s);
+// host only: tile of the one-launch convolution (TM, TR, tiles, NT of `d`, from its planes, ranks and geometry) and its
+// LDS bytes; false when no tile fits
+bool plan_tt_conv(ConvChainDesc& d, int dtype, size_t* lds_bytes);
 
 // ---------------------------------------------------------------- grouped GEMM (fp64 MFMA) -- filtered eigen-solver
 // See dgemm.hip.  M, N multiples of 32, K multiple of 16; every leading dimension even (16-byte rows).

@@ -13,6 +13,22 @@
 //      H1 row of the shifted input pixel (a per-lane LDS gather), zero outside the image (padding)
 //   3. Y[opixel][O]   = H2[opixel][r2] * W3^T + bias   written to the NCHW tensor
 // Weights are fragment-major bf16 planes (chain.hip); Wc is packed as an (r2 x taps*r1) matrix, tap-major.
+//
+// DATA GRADIENT (BWD): dX = W1^T conv^T_kxk(W3^T dY; Wc) is the same three products with the factors' roles swapped: the
+// workgroup owns a tile of dX rows, its halo is the dY rows its taps reach ((iy + ph - ky*dh) / sh where the division is
+// exact), product 1 is dH2 = dY W3, product 2 gathers through a per-workgroup LDS table [tap][pixel] of halo indices (-1:
+// a zero row; built once, so the MFMA loop carries no division -- coreconv.hip), product 3 is dX = dH1 W1, no bias.  The
+// host passes the planes of W3^T, of the transposed core and of W1^T; nothing is flipped.  A dX pixel no tap reaches
+// gathers only zero rows; a tile with an empty halo skips product 1 and still stores its zeros.
+// SAVED INTERMEDIATES (SAVE): the launch also writes its two LDS intermediates as contiguous NCHW tensors (true ranks,
+// the call's dtype): H1 / H2 in the forward, dH2 / dH1 in the data gradient -- what the weight gradients read.  Product
+// 2's pixels belong to exactly one tile.  Product 1's halo rows are recomputed by neighbouring tiles; source row y is
+// written by the FIRST tile whose halo holds it: tile t owns rows (hi(t-1), hi(t)] with hi(t) the last row of its halo
+// (hi(-1) = -1, and the last tile owns through the plane's last row), a rule of the geometry alone.  Owned rows outside
+// the tile's halo and pixels no tap reaches are stored as zeros, so every element of both tensors is written exactly
+// once and nothing else is.  The LDS images are their own staging: a lane reads 8 features of up to 8 consecutive
+// pixels (16-byte LDS reads) and stores, per feature, one 16-byte, 8-byte or element unit of the pixel run -- the unit
+// by the test conv_load applies (base, plane size and run length).
 // Wider planes (more than 64 output columns) and intermediates beyond the LDS take the three-launch path (tadmm_ttconv_chain_in, the device library's conv2d, tadmm_ttconv_chain_out).
 #include "chain_common.h"
 
@@ -20,6 +36,7 @@ namespace tadmm {
 namespace {
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+constexpr size_t kConvMaxLds = 160 * 1024;
 
 // gathered token fragments of one k-step: row src[mt] of the LDS image (or zeros), three or one plane
 template <int P>
@@ -91,9 +108,68 @@ __device__ __forceinline__ void conv_load(ChunkLoader<P, TM, KC, T, true>& ld, c
   }
 }
 
+__device__ __forceinline__ float bf16_bits_to_f32(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
+
+// Features [0, nfeat) of the plane pixels [run0, run0 + runlen) of one image, from an LDS image [P][prow][ld]: pixel p is
+// row p - pix0 of the image where that lies in [0, nrows) and `mask` (nullable) marks it, zero elsewhere.  G: feature 0,
+// pixel 0 of the image's block; U bytes per store.
+template <int P, typename T, int U>
+__device__ __forceinline__ void save_units(const uint16_t* img, int prow, int ld, const uint8_t* mask, int pix0, int nrows,
+                                           T* G, int nfeat, int64_t plane, int run0, int runlen, int tid) {
+  constexpr int V = U / (int)sizeof(T);
+  const int upr = runlen / V, units = ((nfeat + 7) / 8) * upr;
+  for (int i = tid; i < units; i += 256) {
+    const int fg = i / upr, u = i - fg * upr;
+    alignas(16) T val[8][V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int row = run0 + u * V + j - pix0;
+      bool ok = row >= 0 && row < nrows;
+      const int rr = ok ? row : 0;
+      if (mask) ok = ok && mask[rr] != 0;
+      u32x4_t w[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) w[p] = *reinterpret_cast<const u32x4_t*>(&img[(p * prow + rr) * ld + 8 * fg]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int sh = (e & 1) * 16;
+        if constexpr (P == 1) {
+          val[e][j] = ok ? (T)((w[0][e >> 1] >> sh) & 0xffffu) : T(0);
+        } else {                                                  // smallest plane first: the fp32 value product 2 read
+          const float f = (bf16_bits_to_f32((w[2][e >> 1] >> sh) & 0xffffu) + bf16_bits_to_f32((w[1][e >> 1] >> sh) & 0xffffu)) +
+                          bf16_bits_to_f32((w[0][e >> 1] >> sh) & 0xffffu);
+          val[e][j] = ok ? f : 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int f = fg * 8 + e;
+      if (f >= nfeat) continue;
+      T* dst = G + (int64_t)f * plane + run0 + u * V;
+      if constexpr (U == 16) *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(val[e]);
+      else if constexpr (U == 8) *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(val[e]);
+      else *dst = val[e][0];
+    }
+  }
+}
+
+template <int P, typename T>
+__device__ __forceinline__ void save_image(const uint16_t* img, int prow, int ld, const uint8_t* mask, int pix0, int nrows,
+                                           T* G, int nfeat, int64_t plane, int run0, int runlen, int tid) {
+  constexpr int SZ = sizeof(T);
+  if (runlen <= 0) return;
+  auto unit_ok = [&](int U) { return (((uintptr_t)(G + run0)) % U) == 0 && (plane * SZ) % U == 0 && (runlen * SZ) % U == 0; };
+  if (unit_ok(16)) save_units<P, T, 16>(img, prow, ld, mask, pix0, nrows, G, nfeat, plane, run0, runlen, tid);
+  else if (unit_ok(8)) save_units<P, T, 8>(img, prow, ld, mask, pix0, nrows, G, nfeat, plane, run0, runlen, tid);
+  else save_units<P, T, SZ>(img, prow, ld, mask, pix0, nrows, G, nfeat, plane, run0, runlen, tid);
+}
+
 // TM: pixels per workgroup (64, or 32 when three planes of a TT-rank intermediate would not fit the LDS otherwise).
 // NBW: feature tiles (16 wide) per wave in products 1 and 2 (4 * NBW * 16 >= max(R1, R2)) and per pass in product 3
-template <int P, int TM, int KC, int NBW, typename T>
+// BWD: the data gradient's transposed gather (d.H x d.W is then the plane of dY, d.Ho x d.Wo that of dX); SAVE: also store
+// the two intermediates (d.S1, d.S2)
+template <int P, int TM, int KC, int NBW, typename T, bool BWD, bool SAVE>
 __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
   extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
   constexpr int MT = TM / 16, LDX = KC + kPad, SPC = KC / 32;
@@ -105,7 +181,8 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
   const int hw_in = d.H * d.W, hw_out = d.Ho * d.Wo;
   // this workgroup's output rows and the input rows their taps reach (clipped to the image)
   const int oy0 = tile * d.TR, orows = min(d.TR, d.Ho - oy0), n_out = orows * d.Wo;
-  const int iy_lo = max(0, oy0 * d.sh - d.ph), iy_hi = min(d.H - 1, (oy0 + orows - 1) * d.sh - d.ph + (d.kh - 1) * d.dh);
+  int iy_lo, iy_hi;
+  halo_range(BWD ? 1 : 0, oy0, orows, d.kh, d.sh, d.ph, d.dh, d.H, iy_lo, iy_hi);
   const int n_in = max(0, iy_hi - iy_lo + 1) * d.W, p_in0 = iy_lo * d.W;
   const int ntt = (n_in + TM - 1) / TM;                    // token tiles of product 1 (<= d.NT)
   const int prow1 = TM * d.NT;
@@ -113,6 +190,22 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
   const int ld1 = d.R1 + kPad, ld2 = d.R2 + kPad;
   uint16_t* H1s = lds + 2 * P * TM * LDX;                    // [P][64 * NT][ld1]
   uint16_t* H2s = H1s + P * prow1 * ld1;                       // [P][64][ld2]
+  int16_t* tab = reinterpret_cast<int16_t*>(H2s + P * TM * ld2);   // BWD: [taps][TM] halo pixel of (tap, tile pixel), or -1
+  if constexpr (BWD) {
+    const int ntab = d.kh * d.kw * TM;
+    for (int i = tid; i < ntab; i += 256) {
+      const int tap = i / TM, t = i - tap * TM;
+      int v = -1;
+      if (t < n_out) {
+        const int ly = t / d.Wo, lx = t - ly * d.Wo;
+        const int ky = tap / d.kw, kx = tap - ky * d.kw;
+        const int sy = tap_src(1, oy0 + ly, ky, d.sh, d.ph, d.dh, d.H);
+        const int sx = tap_src(1, lx, kx, d.sw, d.pw, d.dw, d.W);
+        if (sy >= iy_lo && sy <= iy_hi && sx >= 0) v = (sy - iy_lo) * d.W + sx;
+      }
+      tab[i] = (int16_t)v;
+    }
+  }
 
   // ---------------- product 1: H1 = X W1^T over the halo's input pixels, 64 at a time (chain.hip, product 1)
   {
@@ -167,6 +260,26 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
   }
   __syncthreads();
 
+  if constexpr (SAVE) {
+    // pixels of the halo that some tap of some destination pixel reads (the chunk buffers are free after product 1)
+    uint8_t* reach = reinterpret_cast<uint8_t*>(Xs);
+    for (int i = tid; i < n_in; i += 256) {
+      const int ry = i / d.W, sy = iy_lo + ry, sx = i - ry * d.W;
+      bool hity = false, hitx = false;
+      for (int j = 0; j < d.kh; ++j) hity = hity || tap_src(BWD ? 0 : 1, sy, j, d.sh, d.ph, d.dh, d.Ho) >= 0;
+      for (int j = 0; j < d.kw; ++j) hitx = hitx || tap_src(BWD ? 0 : 1, sx, j, d.sw, d.pw, d.dw, d.Wo) >= 0;
+      reach[i] = (hity && hitx) ? 1 : 0;
+    }
+    __syncthreads();
+    // rows (hi(tile - 1), hi(tile)] of the source plane are this tile's to write
+    int plo, phi;
+    halo_range(BWD ? 1 : 0, oy0 - d.TR, d.TR, d.kh, d.sh, d.ph, d.dh, d.H, plo, phi);
+    const int own_lo = tile == 0 ? 0 : max(phi, -1) + 1;
+    const int own_hi = tile == d.tiles - 1 ? d.H - 1 : iy_hi;
+    save_image<P, T>(H1s, prow1, ld1, reach, p_in0, n_in, static_cast<T*>(d.S1) + (int64_t)img * d.r1t * hw_in, d.r1t, hw_in,
+                     own_lo * d.W, (own_hi - own_lo + 1) * d.W, tid);
+  }
+
   // ---------------- product 2: the k x k core convolution as taps * R1/32 k-steps with gathered token rows
   {
     float4v_t acc[MT][NBW];
@@ -184,11 +297,13 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
     }
     // output pixel of (mt, r) -> its coordinates; the source row of a tap is computed on the fly
     int oy[MT], ox[MT];
+    if constexpr (!BWD) {
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int px = 16 * mt + r;
-      oy[mt] = px < n_out ? oy0 + px / d.Wo : -(1 << 20);     // invalid output pixels gather nothing
-      ox[mt] = px - (px / d.Wo) * d.Wo;
+      for (int mt = 0; mt < MT; ++mt) {
+        const int px = 16 * mt + r;
+        oy[mt] = px < n_out ? oy0 + px / d.Wo : -(1 << 20);     // invalid output pixels gather nothing
+        ox[mt] = px - (px / d.Wo) * d.Wo;
+      }
     }
     // weight fragments RD - 1 steps ahead, ring indexed statically (RD steps per trip); surplus steps of the last trip
     // multiply zero fragments
@@ -202,14 +317,24 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
       for (int u = 0; u < RD; ++u) {
         load_w<P, NBW>(b[(u + RD - 1) % RD], w2, d.w2_plane, min(s + u + RD - 1, S - 1));
         const bool live = s + u < S;
-        const int dy = tap / d.kw, dx = tap - dy * d.kw;
+        if constexpr (BWD) {                                    // the table holds the transposed map: no division here
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const int iy = oy[mt] * d.sh - d.ph + dy * d.dh, ix = ox[mt] * d.sw - d.pw + dx * d.dw;
-          const bool in = live && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
-          bf16x8_t a[P];
-          gather_x<P>(a, H1s, prow1, ld1, in ? (iy - iy_lo) * d.W + ix : -1, ks, q);
-          mma_tile<P, NBW>(a, b[u], acc[mt]);
+          for (int mt = 0; mt < MT; ++mt) {
+            const int row = live ? (int)tab[tap * TM + 16 * mt + r] : -1;
+            bf16x8_t a[P];
+            gather_x<P>(a, H1s, prow1, ld1, row, ks, q);
+            mma_tile<P, NBW>(a, b[u], acc[mt]);
+          }
+        } else {
+          const int dy = tap / d.kw, dx = tap - dy * d.kw;
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const int iy = oy[mt] * d.sh - d.ph + dy * d.dh, ix = ox[mt] * d.sw - d.pw + dx * d.dw;
+            const bool in = live && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
+            bf16x8_t a[P];
+            gather_x<P>(a, H1s, prow1, ld1, in ? (iy - iy_lo) * d.W + ix : -1, ks, q);
+            mma_tile<P, NBW>(a, b[u], acc[mt]);
+          }
         }
         ks += 1;
         if (ks == KSR) { ks = 0; tap += 1; }
@@ -219,6 +344,10 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
     acc_to_lds<P, TM, NBW>(acc, H2s, TM, 0, ld2, wave * NBW * 16, d.R2, r, q);
   }
   __syncthreads();
+
+  if constexpr (SAVE)                                        // every pixel of the tile is this workgroup's alone
+    save_image<P, T>(H2s, TM, ld2, nullptr, oy0 * d.Wo, n_out, static_cast<T*>(d.S2) + (int64_t)img * d.r2t * hw_out, d.r2t,
+                     hw_out, oy0 * d.Wo, n_out, tid);
 
   // ---------------- product 3: Y = H2 W3^T + bias over the output pixels, straight into the NCHW tensor
   {
@@ -316,21 +445,33 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
   }
 }
 
-template <int P, int TM, int KC, int NBW, typename T>
-int launch_conv_nbw(const ConvChainDesc& d, hipStream_t s) {
-  auto kern = tt_conv_kernel<P, TM, KC, NBW, T>;
-  const size_t lds = ((size_t)2 * P * TM * (KC + kPad) + (size_t)P * TM * d.NT * (d.R1 + kPad) + (size_t)P * TM * (d.R2 + kPad)) * 2;
-  if (lds > 160 * 1024) return -1;
+template <int P, int KC> size_t conv_lds_bytes(const ConvChainDesc& d) {
+  return ((size_t)2 * P * d.TM * (KC + kPad) + (size_t)P * d.TM * d.NT * (d.R1 + kPad) + (size_t)P * d.TM * (d.R2 + kPad)) * 2 +
+         (d.transposed ? (size_t)d.kh * d.kw * d.TM * 2 : 0);                 // + the tap table of the data gradient
+}
+
+template <int P, int TM, int KC, int NBW, typename T, bool BWD, bool SAVE>
+int launch_conv_mode(const ConvChainDesc& d, hipStream_t s) {
+  auto kern = tt_conv_kernel<P, TM, KC, NBW, T, BWD, SAVE>;
+  const size_t lds = conv_lds_bytes<P, KC>(d);
+  if (lds > kConvMaxLds) return -1;
   static bool attr_done[64] = {false};
   int devi = 0;
   (void)hipGetDevice(&devi);
   if (!attr_done[devi & 63]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvMaxLds);
     (void)hipGetLastError();
     attr_done[devi & 63] = true;
   }
   hipLaunchKernelGGL(kern, dim3(d.B * d.tiles), dim3(256), lds, s, d);
   return 0;
+}
+
+template <int P, int TM, int KC, int NBW, typename T>
+int launch_conv_nbw(const ConvChainDesc& d, hipStream_t s) {
+  const bool save = d.S1 != nullptr;
+  if (d.transposed) return save ? launch_conv_mode<P, TM, KC, NBW, T, true, true>(d, s) : launch_conv_mode<P, TM, KC, NBW, T, true, false>(d, s);
+  return save ? launch_conv_mode<P, TM, KC, NBW, T, false, true>(d, s) : launch_conv_mode<P, TM, KC, NBW, T, false, false>(d, s);
 }
 
 template <int P, int TM, int KC, typename T>
@@ -342,6 +483,30 @@ int launch_conv_variant(const ConvChainDesc& d, hipStream_t s) {
 }
 
 }  // namespace
+
+// Pixels per workgroup: 64, or 32 when the intermediates of 64 do not fit the LDS; destination rows per workgroup: as
+// many as give <= TM destination pixels and a halo of <= 3 TM source pixels.  Reads the planes, ranks, geometry and
+// `transposed` of d (source plane d.H x d.W, destination plane d.Ho x d.Wo).
+bool plan_tt_conv(ConvChainDesc& d, int dtype, size_t* lds_bytes) {
+  if (d.Wo <= 0 || d.Ho <= 0 || d.Wo > 64) return false;
+  for (int tmx = 64; tmx >= 32; tmx /= 2) {
+    if (d.Wo > tmx) continue;
+    int tr = std::min(d.Ho, tmx / d.Wo), nt = 0;
+    for (; tr >= 1; --tr) {
+      const int64_t reach = (int64_t)(d.kh - 1) * d.dh;
+      const int64_t srows = std::min<int64_t>(d.H, d.transposed ? (tr - 1 + reach) / d.sh + 1 : (int64_t)(tr - 1) * d.sh + reach + 1);
+      nt = (int)std::min<int64_t>((srows * d.W + tmx - 1) / tmx, 4);
+      if (nt <= 3) break;
+    }
+    if (tr < 1) continue;
+    d.TM = tmx; d.TR = tr; d.tiles = (d.Ho + tr - 1) / tr; d.NT = nt;
+    const size_t lds = dtype == 1 ? conv_lds_bytes<1, 128>(d) : conv_lds_bytes<3, 64>(d);
+    if (lds > kConvMaxLds) continue;
+    if (lds_bytes) *lds_bytes = lds;
+    return true;
+  }
+  return false;
+}
 
 // dtype 0: fp32 through three bf16 planes; 1: bf16.  -1: the intermediates do not fit the LDS (the caller takes the
 // three-launch path).

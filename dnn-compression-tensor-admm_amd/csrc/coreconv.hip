@@ -45,34 +45,6 @@ struct CoreConvArgs {
   int32_t s_align;                        // source base: 2 = 16-byte aligned, 1 = 8-byte, 0 = element
 };
 
-// first and last source coordinate that destination coordinates [t0, t0 + n) reach over all taps of one axis
-__device__ __host__ inline void halo_range(int transposed, int t0, int n, int k, int s, int p, int dl, int lim, int& lo, int& hi) {
-  if (!transposed) {
-    lo = t0 * s - p;
-    hi = (t0 + n - 1) * s - p + (k - 1) * dl;
-  } else {
-    const int a = t0 + p - (k - 1) * dl, b = t0 + n - 1 + p;
-    lo = a <= 0 ? 0 : (a + s - 1) / s;
-    hi = b < 0 ? -1 : b / s;
-  }
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > lim - 1 ? lim - 1 : hi;
-}
-
-// source coordinate of destination coordinate t under tap j of one axis, or -1
-__device__ __forceinline__ int tap_src(int transposed, int t, int j, int s, int p, int dl, int lim) {
-  int v;
-  if (!transposed) {
-    v = t * s - p + j * dl;
-  } else {
-    const int num = t + p - j * dl;
-    if (num < 0) return -1;
-    v = num / s;
-    if (v * s != num) return -1;
-  }
-  return (v >= 0 && v < lim) ? v : -1;
-}
-
 // EPL consecutive elements from p; `n` of them exist.  vec 2: one 16-byte load, 1: two 8-byte loads, 0: elements
 template <typename T> __device__ __forceinline__ uint4 halo_fetch(const T* p, int vec, int n) {
   constexpr int EPL = 16 / sizeof(T);

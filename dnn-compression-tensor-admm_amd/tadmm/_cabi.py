@@ -79,6 +79,7 @@ class ConvChainDesc(C.Structure):
 
 
 CHAIN_F32, CHAIN_BF16 = 0, 1
+CONV_CHAIN_FWD, CONV_CHAIN_BWD = 0, 1
 
 
 class OrthDesc(C.Structure):
@@ -162,6 +163,12 @@ ABI = {
     "tadmm_chain_desc_bytes": (C.c_int, []),
     "tadmm_conv_chain_desc_bytes": (C.c_int, []),
     "tadmm_ttconv_fused": (C.c_int, [C.c_void_p, C.POINTER(ConvChainDesc), C.c_void_p]),
+    "tadmm_ttconv_fused_save": (C.c_int, [C.c_void_p, C.POINTER(ConvChainDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "tadmm_ttconv_fused_bwd": (C.c_int, [C.c_void_p, C.POINTER(ConvChainDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "tadmm_ttconv_fused_plan": (C.c_int, [C.POINTER(ConvChainDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "tadmm_ttlinear_fwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_ttlinear_bwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_ttconv_chain_in": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),

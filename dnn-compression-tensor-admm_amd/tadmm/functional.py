@@ -373,3 +373,146 @@ def core_conv_routed(layer, x: torch.Tensor):
         return None
     cache = None if grad else layer.__dict__.setdefault("_core_cache", {})
     return core_conv(x, core, layer.stride, layer.padding, layer.dilation, cache=cache)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The whole factorised convolution y = W3 conv_kxk(W1 x; Wc) + b of a small plane as ONE launch forward and ONE launch
+# for the data gradient (csrc/convchain.hip): both intermediates stay in LDS, and only a step that trains a factor
+# stores them (H1, H2 forward; dH1, dH2 backward) for the three weight gradients.
+# ---------------------------------------------------------------------------------------------------------------
+# dWc through `ops.core_conv_wgrad` (float32, deterministic) rather than the device library's weight gradient: the faster of
+# the two inside `conv_chain` at 25 of 30 bf16 and 18 of 22 fp32 layers (scripts/bench_conv_train.py)
+CONV_CHAIN_DWC_NATIVE = True
+
+
+def _core_wgrad_library(h1, dh2, core, stride, padding, dilation):
+    w = core.detach().to(h1.dtype)
+    return torch.ops.aten.convolution_backward(dh2, h1, w, None, list(stride), list(padding), list(dilation), False, [0, 0],
+                                               1, [False, True, False])[1]
+
+
+def _core_dgrad_library(dh2, h1_shape, core, stride, padding, dilation):
+    w = core.detach().to(dh2.dtype)
+    h1 = dh2.new_empty(h1_shape)                      # the data gradient reads the input's shape only
+    return torch.ops.aten.convolution_backward(dh2, h1, w, None, list(stride), list(padding), list(dilation), False, [0, 0],
+                                               1, [True, False, False])[0]
+
+
+def _conv_chain_planes(w_in, core, w_out, n, transposed):
+    if transposed:                                    # nothing is flipped: the kernel's transposed gather maps the taps
+        return (ops.weight_planes(w_out.detach().t(), n, pad_rows=32), ops.conv_core_planes(core.permute(1, 0, 2, 3), n),
+                ops.weight_planes(w_in.detach().t(), n))
+    return (ops.weight_planes(w_in.detach(), n, pad_rows=32), ops.conv_core_planes(core, n), ops.weight_planes(w_out.detach(), n))
+
+
+def _cached_conv_chain_planes(cache, w_in, core, w_out, n, device, transposed):
+    if cache is None:
+        return _conv_chain_planes(w_in, core, w_out, n, transposed)
+    tag = "tplanes_t" if transposed else "tplanes"
+    key = (n, device, param_key(w_in, core, w_out))
+    if cache.get(tag + "_key") != key:
+        cache[tag + "_key"], cache[tag] = key, _conv_chain_planes(w_in, core, w_out, n, transposed)
+    return cache[tag]
+
+
+class _ConvChain(torch.autograd.Function):
+    """y = W3 conv_kxk(W1 x; Wc) + bias on NCHW images; W1 (r1, C), Wc (r2, r1, kh, kw), W3 (O, r2)."""
+
+    @staticmethod
+    def forward(ctx, x, w_in, core, w_out, bias, stride, padding, dilation, cache):
+        if not x.is_cuda:
+            raise TadmmError(-1, "conv chain operands must live on the HIP device (no CPU fallback)")
+        n = _nplanes(x)
+        ksize = tuple(core.shape[2:])
+        r1, r2 = w_in.shape[0], w_out.shape[1]
+        train = any(ctx.needs_input_grad[1:4])      # a factor wants a gradient: the launch also stores H1 and H2
+        p1, p2, p3 = _cached_conv_chain_planes(None if train else cache, w_in, core, w_out, n, x.device, False)
+        if train:
+            y, h1, h2 = ops.conv_chain_save(x, p1, p2, p3, bias, w_out.shape[0], r1, r2, ksize, stride, padding, dilation)
+            ctx.save_for_backward(w_in, core, w_out, x, h1, h2)
+        else:
+            y = ops.conv_chain(x, p1, p2, p3, bias, w_out.shape[0], ksize, stride, padding, dilation, memo=cache is not None)
+            ctx.save_for_backward(w_in, core, w_out)
+        ctx.train, ctx.cache, ctx.x_shape, ctx.has_bias = train, cache, tuple(x.shape), bias is not None
+        ctx.geom = (ksize, stride, padding, dilation)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        w_in, core, w_out = ctx.saved_tensors[:3]
+        x, h1, h2 = ctx.saved_tensors[3:] if ctx.train else (None, None, None)
+        ksize, stride, padding, dilation = ctx.geom
+        need = ctx.needs_input_grad
+        g = g.contiguous()
+        n = _nplanes(g)
+        r1, r2 = w_in.shape[0], w_out.shape[1]
+        gx = gwi = gc = gwo = gb = None
+        want_h = need[1] or need[2]                     # dW_in reads dH1, dWc reads dH2
+        if need[0] or want_h:
+            if ops._conv_chain_bwd_plan(ctx.x_shape, g.dtype, r1, r2, ksize, stride, padding, dilation) is not None:
+                planes = _cached_conv_chain_planes(None if ctx.train else ctx.cache, w_in, core, w_out, n, g.device, True)
+                out = ops.conv_chain_bwd(g, *planes, ctx.x_shape, r1, r2, ksize, stride, padding, dilation, save=want_h)
+                gx, dh1, dh2 = out if want_h else (out, None, None)
+            else:                                       # the forward fitted, its data gradient does not: three launches
+                dh2 = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, r2, entry="tadmm_ttconv_chain_out",
+                                       image_out=True, memo=False)
+                dh1 = None
+                if need[0] or need[1]:
+                    h1_shape = (ctx.x_shape[0], r1, ctx.x_shape[2], ctx.x_shape[3])
+                    dh1 = _core_dgrad_library(dh2, h1_shape, core, stride, padding, dilation)
+                if need[0]:
+                    gx = ops.chain_single(dh1, planes_of(w_in, n, transpose=True), None, w_in.shape[1],
+                                          entry="tadmm_ttconv_chain_in", image_out=True, memo=False)
+            if not need[0]:
+                gx = None
+        if need[3]:                                     # dW_out = dY H2^T over batch and pixels
+            gwo = ops.wgrad(g, h2).to(w_out.dtype)
+        if need[1]:                                     # dW_in = dH1 X^T
+            gwi = ops.wgrad(dh1, x).to(w_in.dtype)
+        if need[2]:
+            if CONV_CHAIN_DWC_NATIVE:
+                gc = ops.core_conv_wgrad(dh2, h1, ksize, stride, padding, dilation).to(core.dtype)
+            else:
+                gc = _core_wgrad_library(h1, dh2, core, stride, padding, dilation).to(core.dtype)
+        if ctx.has_bias and need[4]:
+            gb = g.sum((0, 2, 3), dtype=torch.float32)
+        return gx, gwi, gc, gwo, gb, None, None, None, None
+
+
+def conv_chain(x: torch.Tensor, w_in: torch.Tensor, core: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None,
+               stride=1, padding=0, dilation=1, cache: dict = None):
+    """(B, C, H, W) -> (B, O, Ho, Wo): y = W3 conv_kxk(W1 x; Wc) + bias with w_in = W1 (r1, C), core = Wc (r2, r1, kh, kw),
+    w_out = W3 (O, r2), groups = 1, as one `tadmm_ttconv_fused` launch (`ops.conv_chain_fits` says where it applies).
+    Differentiable on the contracted factors: the data gradient is one `tadmm_ttconv_fused_bwd` launch (three launches
+    where `ops.conv_chain_bwd_fits` is False).  With only x (and bias) wanting a gradient nothing is saved; when a factor
+    wants one the two launches also store H1 / H2 and dH1 / dH2, and dW_out = `ops.wgrad(dY, H2)`, dW_in =
+    `ops.wgrad(dH1, x)`, dWc = the weight gradient of the core convolution on (H1, dH2).  `cache` (a dict owned by the
+    layer): packed planes of frozen factors are reused until their version counters or storage change (`param_key`)."""
+    if x.dim() != 4 or core.dim() != 4 or w_in.dim() != 2 or w_out.dim() != 2 or x.shape[1] != w_in.shape[1] \
+            or core.shape[1] != w_in.shape[0] or core.shape[0] != w_out.shape[1]:
+        raise ValueError("conv_chain expects an NCHW image, W1 (r1, C), a (r2, r1, kh, kw) core and W3 (O, r2)")
+    stride, padding, dilation = ops._pair(stride), ops._pair(padding), ops._pair(dilation)
+    ksize = tuple(core.shape[2:])
+    if not ops.conv_chain_fits(x, w_in.shape[0], w_out.shape[1], ksize, stride, padding, dilation):
+        raise TadmmError(-5, "conv_chain: the plane, halo or ranks do not fit the one-launch kernel (ops.conv_chain_fits)")
+    if _needs_grad(x, w_in, core, w_out, bias):
+        return _ConvChain.apply(x.contiguous(), w_in, core, w_out, bias, stride, padding, dilation, cache)
+    p1, p2, p3 = _cached_conv_chain_planes(cache, w_in, core, w_out, _nplanes(x), x.device, False)
+    return ops.conv_chain(x, p1, p2, p3, bias, w_out.shape[0], ksize, stride, padding, dilation, memo=cache is not None)
+
+
+def conv_chain_routed(layer, x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor):
+    """`conv_chain` of a factorised layer in grad mode where `ops.conv_chain_train_pays` routes it to the one-launch path,
+    else None: the caller keeps its three differentiable launches."""
+    core = layer.core_kernel
+    if layer.groups != 1 or not _needs_grad(x, w_in, core, w_out, layer.bias):
+        return None
+    geom = (layer.kernel_size, layer.stride, layer.padding, layer.dilation)
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or not ops.conv_chain_fits(x, w_in.shape[0], w_out.shape[1], *geom):
+        return None
+    training = _needs_grad(w_in, core, w_out)         # a factor wants a gradient: the intermediates are saved
+    if not ops.conv_chain_train_pays(x, w_in.shape[0], w_out.shape[1], *geom, training=training):
+        return None
+    cache = None if training else layer.__dict__.setdefault("_fused_cache", {})
+    return conv_chain(x, w_in, core, w_out, layer.bias, layer.stride, layer.padding, layer.dilation, cache=cache)
+

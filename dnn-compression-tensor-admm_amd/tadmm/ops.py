@@ -653,11 +653,100 @@ def conv_core_planes(core: torch.Tensor, planes: int) -> torch.Tensor:
     return weight_planes(m.reshape(r2, kh * kw * r1p), planes, pad_rows=32)
 
 
+def _conv_chain_bwd_plan(x_shape, dtype, r1: int, r2: int, kernel_size, stride, padding, dilation):
+    """(pixels per workgroup, dX rows per workgroup, halo tiles, workgroups per image) of the one-launch data gradient of
+    the factorised convolution of an input of shape x_shape, or None when it does not apply -- the rule
+    `tadmm_ttconv_fused_bwd` applies (`tadmm_ttconv_fused_plan` states it; tests/test_conv_chain_plan_cpu.py holds the
+    two together).  The tile is a run of dX rows, its halo the dY rows the taps reach, and the tap table joins the LDS."""
+    if len(x_shape) != 4 or dtype not in (torch.float32, torch.bfloat16):
+        return None
+    H, W = x_shape[2], x_shape[3]
+    ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
+    if ho <= 0 or wo <= 0 or H <= 0 or W <= 0 or W > 64:
+        return None
+    r1p, r2p = -(-r1 // 32) * 32, -(-r2 // 32) * 32
+    if r1p > 256 or r2p > 256:
+        return None
+    planes, kc = (3, 64) if dtype == torch.float32 else (1, 128)
+    for tm in (64, 32):
+        if W > tm:
+            continue
+        tr, nt = min(H, tm // W), 0
+        while tr >= 1:
+            srows = min(ho, (tr - 1 + (kernel_size[0] - 1) * dilation[0]) // stride[0] + 1)
+            nt = -(-(srows * wo) // tm)
+            if nt <= 3:
+                break
+            tr -= 1
+        if tr < 1:
+            continue
+        lds = (2 * planes * tm * (kc + 8) + planes * tm * nt * (r2p + 8) + planes * tm * (r1p + 8)) * 2 \
+            + kernel_size[0] * kernel_size[1] * tm * 2
+        if lds <= 160 * 1024:
+            return tm, tr, nt, -(-H // tr)
+    return None
+
+
+def conv_chain_bwd_fits(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation) -> bool:
+    """True when the one-launch data gradient (`conv_chain_bwd`) applies to the layer whose INPUT is x: input rows of at
+    most 64 pixels, a tile of dX rows whose dY halo is at most three pixel tiles, ranks at most 256 and the intermediates
+    plus the tap table inside the 160 KiB of LDS.  Host-only shape logic."""
+    return _conv_chain_bwd_plan(tuple(x.shape), x.dtype, r1, r2, kernel_size, stride, padding, dilation) is not None
+
+
+def conv_chain_train_pays(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation,
+                          training: bool) -> bool:
+    """True when a layer in grad mode routes to `functional.conv_chain` (one forward launch, one data-gradient launch)
+    instead of the three differentiable launches.  Two classes: `training` False is the FROZEN class (only x, or x and
+    the bias, want a gradient: nothing is saved), True the TRAINING class (a factor wants a gradient: the launches also
+    store H1 / H2 and dH1 / dH2, and three weight gradients follow).
+    Measured (scripts/bench_conv_train.py) on the 30 distinct 3 x 3 layers of resnet18_tt 2x,
+    resnet50_tt 3x, tk_resnet50 3x (batch 32) and tk_resnet32 3x (batch 128), forward + backward against the three-launch
+    path in the same process; "ahead" = the new median below the old path's fastest round:
+      frozen, bf16: ahead at 30 of 30 (1.23x - 3.31x): always.
+      frozen, fp32 (22 fit): ahead at all 19 layers of at most 1024 workgroups (batch x row tiles; 1.23x - 3.93x), behind
+        at the 3 of 1792 and more (56 x 56 planes at batch 32, 32 x 32 at batch 128: 0.81x - 0.87x, the recomputed halos
+        at six MFMA products per product): up to 1024 workgroups.  Nothing was measured between 1024 and 1792.
+      training, fp32: behind at 22 of 22 with either weight gradient of the core (0.64x - 1.11x): never.
+      training, bf16: with dWc through `core_conv_wgrad` ahead at all 21 layers whose input plane has at most 1024 pixels
+        (1.13x - 1.47x; through the device library's weight gradient 1.01x - 1.34x and ahead at 18 of them) and at 3 of the
+        9 on 56 x 56 inputs (0.82x - 1.20x): planes of at most 1024 pixels, dWc native."""
+    plan = _conv_chain_plan(x, r1, r2, kernel_size, stride, padding, dilation)
+    if plan is None:
+        return False
+    bf16 = x.dtype == torch.bfloat16
+    if not training:
+        return bf16 or x.shape[0] * plan[3] <= 1024
+    return bf16 and x.shape[2] * x.shape[3] <= 1024
+
+
+def _conv_chain_desc(B, Cc, H, W, n_out, w1p, w2p, w3p, bias, dtype, kernel_size, stride, padding, dilation, bwd=False):
+    d = _cabi.ConvChainDesc()
+    d.dtype = _cabi.CHAIN_F32 if dtype == torch.float32 else _cabi.CHAIN_BF16
+    ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
+    d.W1, d.W2, d.W3 = w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr()
+    d.bias = None if bias is None else bias.data_ptr()
+    d.w1_plane, d.w2_plane, d.w3_plane = w1p[0].numel(), w2p[0].numel(), w3p[0].numel()
+    # forward: W1 (R1 x C), W2 (R2 x taps*R1), W3 (Nout x R2); data gradient: W3^T (R2 x Nout), core^T (R1 x taps*R2), W1^T (C x R1)
+    ra, rb = w1p.shape[1] * 16, w2p.shape[1] * 16
+    d.R1, d.R2 = (rb, ra) if bwd else (ra, rb)
+    d.B, d.C, d.Nout = B, Cc, n_out
+    d.H, d.W, d.Ho, d.Wo, d.kh, d.kw = H, W, ho, wo, kernel_size[0], kernel_size[1]
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = (stride[0], stride[1], padding[0], padding[1],
+                                                                  dilation[0], dilation[1])
+    if (w2p.shape[2] * 32 != kernel_size[0] * kernel_size[1] * ra or w3p.shape[2] * 32 != rb
+            or w1p.shape[2] != -(-(n_out if bwd else Cc) // 32)):
+        raise TadmmError(-1, "conv chain: weight planes do not match each other")
+    return d, ho, wo
+
+
 def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch.Tensor, bias, n_out: int, kernel_size,
-               stride, padding, dilation) -> torch.Tensor:
+               stride, padding, dilation, save_ranks=None, memo: bool = True, out=None):
     """y (B, n_out, Ho, Wo) = W3 conv_kxk(W1 x; Wc) + bias for NCHW images in one launch (`tadmm_ttconv_fused`; see
     `conv_chain_fits` for what is eligible).
-    w1p = weight_planes(W1, P, pad_rows=32), w2p = conv_core_planes(core, P), w3p = weight_planes(W3, P)."""
+    w1p = weight_planes(W1, P, pad_rows=32), w2p = conv_core_planes(core, P), w3p = weight_planes(W3, P).
+    `save_ranks` = (r1, r2): see `conv_chain_save`.  `memo` False: planes packed for this call only stay out of the launch
+    memo.  `out`: contiguous tensors to write instead of fresh ones -- y, or (y, H1, H2) with `save_ranks`."""
     if not x.is_cuda:
         raise TadmmError(-1, "x must live on a HIP device; there is no CPU path")
     if not x.is_contiguous():
@@ -667,36 +756,88 @@ def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch
         bias_key = None
     else:
         bias_key = 0 if bias is None else bias.data_ptr()
+    if save_ranks is not None or not memo:
+        bias_key = None                                 # training: the planes are short-lived -- build, launch, forget
     key = ("conv", tuple(x.shape), x.dtype, x.device, w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr(), bias_key, n_out,
            tuple(kernel_size), tuple(stride), tuple(padding), tuple(dilation))
     memo = _CHAIN_MEMO.lookup(key) if bias_key is not None else None
     if memo is None:
         B, Cc, H, W = x.shape
-        d = _cabi.ConvChainDesc()
-        d.dtype = _cabi.CHAIN_F32 if x.dtype == torch.float32 else _cabi.CHAIN_BF16
-        ho = (H + 2 * padding[0] - dilation[0] * (kernel_size[0] - 1) - 1) // stride[0] + 1
-        wo = (W + 2 * padding[1] - dilation[1] * (kernel_size[1] - 1) - 1) // stride[1] + 1
-        d.W1, d.W2, d.W3 = w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr()
-        d.bias = None if bias is None else bias.data_ptr()
-        d.w1_plane, d.w2_plane, d.w3_plane = w1p[0].numel(), w2p[0].numel(), w3p[0].numel()
-        d.B, d.C, d.R1, d.R2, d.Nout = B, Cc, w1p.shape[1] * 16, w2p.shape[1] * 16, n_out
-        d.H, d.W, d.Ho, d.Wo, d.kh, d.kw = H, W, ho, wo, kernel_size[0], kernel_size[1]
-        d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = (stride[0], stride[1], padding[0], padding[1],
-                                                                      dilation[0], dilation[1])
-        if (w2p.shape[2] * 32 != kernel_size[0] * kernel_size[1] * d.R1 or w3p.shape[2] * 32 != d.R2
-                or w1p.shape[2] != -(-Cc // 32)):
-            raise TadmmError(-1, "conv chain: weight planes do not match each other")
+        d, ho, wo = _conv_chain_desc(B, Cc, H, W, n_out, w1p, w2p, w3p, bias, x.dtype, kernel_size, stride, padding, dilation)
         dev = x.device
         h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
         memo = (d, h.lib.tadmm_ttconv_fused, h, (B, n_out, ho, wo), (w1p, w2p, w3p, bias))
         if bias_key is not None:
             _CHAIN_MEMO.store(key, memo)
     d, fn, h, yshape, _ = memo
-    y = torch.empty(yshape, dtype=x.dtype, device=x.device)
+
+    def result(shape, given):
+        if given is None:
+            return torch.empty(shape, dtype=x.dtype, device=x.device)
+        if tuple(given.shape) != tuple(shape) or given.dtype != x.dtype or given.device != x.device or not given.is_contiguous():
+            raise TadmmError(-1, f"conv chain: `out` must be a contiguous {x.dtype} tensor of shape {tuple(shape)}")
+        return given
+
+    outs = (out,) if isinstance(out, torch.Tensor) else (tuple(out) if out is not None else ())
+    outs = outs + (None,) * (3 - len(outs))
+    y = result(yshape, outs[0])
     d.X, d.Y = x.data_ptr(), y.data_ptr()
-    if yshape[0] > 0:
-        h.check(fn(h.ptr, C.byref(d), _stream(x.device)))
-    return y
+    if save_ranks is None:
+        if yshape[0] > 0:
+            h.check(fn(h.ptr, C.byref(d), _stream(x.device)))
+        return y
+    r1, r2 = save_ranks
+    h1 = result((x.shape[0], r1, x.shape[2], x.shape[3]), outs[1])
+    h2 = result((yshape[0], r2, yshape[2], yshape[3]), outs[2])
+    h.check(h.lib.tadmm_ttconv_fused_save(h.ptr, C.byref(d), r1, r2, h1.data_ptr(), h2.data_ptr(), _stream(x.device)))
+    return y, h1, h2
+
+
+def conv_chain_save(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch.Tensor, bias, n_out: int, r1: int,
+                    r2: int, kernel_size, stride, padding, dilation, out=None):
+    """`conv_chain` that also returns its two intermediates, (y, H1 (B, r1, H, W), H2 (B, r2, Ho, Wo)), of x's dtype
+    (`tadmm_ttconv_fused_save`): what the weight gradients of a training step read.  r1, r2: the true ranks.  A pixel of
+    H1 that no tap of any output pixel reads is stored as zero."""
+    return conv_chain(x, w1p, w2p, w3p, bias, n_out, kernel_size, stride, padding, dilation, save_ranks=(r1, r2), out=out)
+
+
+def conv_chain_bwd(dy: torch.Tensor, w3tp: torch.Tensor, w2tp: torch.Tensor, w1tp: torch.Tensor, x_shape, r1: int, r2: int,
+                   kernel_size, stride, padding, dilation, save: bool = False, out=None):
+    """dX (x_shape) = W1^T conv^T_kxk(W3^T dY; Wc) of the one-launch factorised convolution, in one launch
+    (`tadmm_ttconv_fused_bwd`; `conv_chain_bwd_fits` says where).  w3tp = weight_planes(W3.t(), P, pad_rows=32), w2tp =
+    conv_core_planes(core.permute(1, 0, 2, 3), P), w1tp = weight_planes(W1.t(), P); nothing is flipped.  `save`: returns
+    (dX, dH1 (B, r1, H, W), dH2 (B, r2, Ho, Wo)), the gradients of the two intermediates.  `out`: contiguous tensors to
+    write instead of fresh ones -- dX, or (dX, dH1, dH2) with `save`."""
+    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
+        raise TadmmError(-1, "dy must live on a HIP device; there is no CPU path")
+    if dy.dim() != 4 or dy.dtype not in (torch.float32, torch.bfloat16):
+        raise TadmmError(-1, f"conv chain: a float32 or bfloat16 NCHW image is needed (got {dy.dim()}-D {dy.dtype})")
+    if not dy.is_contiguous():
+        dy = dy.contiguous()
+    B, Cc, H, W = x_shape
+    d, ho, wo = _conv_chain_desc(B, Cc, H, W, dy.shape[1], w3tp, w2tp, w1tp, None, dy.dtype, kernel_size, stride, padding,
+                                 dilation, bwd=True)
+    if tuple(dy.shape) != (B, dy.shape[1], ho, wo) or w1tp.shape[1] * 16 < Cc:
+        raise TadmmError(-1, f"conv chain: dy of shape {tuple(dy.shape)} is not the output of x {tuple(x_shape)}")
+    dev = dy.device
+    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    def result(shape, given):
+        if given is None:
+            return torch.empty(shape, dtype=dy.dtype, device=dev)
+        if tuple(given.shape) != tuple(shape) or given.dtype != dy.dtype or given.device != dev or not given.is_contiguous():
+            raise TadmmError(-1, f"conv chain: `out` must be a contiguous {dy.dtype} tensor of shape {tuple(shape)}")
+        return given
+
+    outs = (out,) if isinstance(out, torch.Tensor) else (tuple(out) if out is not None else ())
+    outs = outs + (None,) * (3 - len(outs))
+    dx = result(tuple(x_shape), outs[0])
+    dh1 = dh2 = None
+    if save:
+        dh1, dh2 = result((B, r1, H, W), outs[1]), result((B, r2, ho, wo), outs[2])
+    d.X, d.Y = dy.data_ptr(), dx.data_ptr()
+    h.check(h.lib.tadmm_ttconv_fused_bwd(h.ptr, C.byref(d), r1, r2, None if dh1 is None else dh1.data_ptr(),
+                                         None if dh2 is None else dh2.data_ptr(), _stream(dev)))
+    return (dx, dh1, dh2) if save else dx
 
 
 # ------------------------------------------------------------------ k x k core convolution (csrc/coreconv.hip)

@@ -120,6 +120,9 @@ class TKConv2dC(_TKConvBase):
 
     def _fused(self, x, w1, core, w3):
         """The whole layer in one launch when the planes are small (csrc/convchain.hip); None when it does not apply."""
+        y = HF.conv_chain_routed(self, x, w1, w3)              # grad mode, where ops.conv_chain_train_pays says so
+        if y is not None:
+            return y
         if torch.is_grad_enabled() or self.groups != 1 or not ops.conv_chain_pays(
                 x, w1.shape[0], w3.shape[1], self.kernel_size, self.stride, self.padding, self.dilation):
             return None

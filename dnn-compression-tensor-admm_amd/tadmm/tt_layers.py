@@ -201,6 +201,9 @@ class TTConv2dM(_TTConvBase):
             f1, f2, f3 = cache["fplanes"]
             return ops.conv_chain(x, f1, f2, f3, self.bias, self.out_channels, self.kernel_size, self.stride, self.padding,
                                   self.dilation)
+        y = HF.conv_chain_routed(self, x, w_in, w_out)           # grad mode, where ops.conv_chain_train_pays says so
+        if y is not None:
+            return y
         out = HF.pointwise(x, w_in, None, "tadmm_ttconv_chain_in", p_in)
         mid = HF.core_conv_routed(self, out)                    # the native k x k kernel where it pays (csrc/coreconv.hip)
         if mid is None:

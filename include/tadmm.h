@@ -349,6 +349,31 @@ typedef struct {
 } tadmm_conv_chain_desc;
 int tadmm_conv_chain_desc_bytes(void);
 int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* d, void* stream);
+/* Training on the one-launch path.  Both entries take the descriptor filled with the FORWARD geometry (H x W the input
+ * plane, Ho x Wo the output plane, C / Nout the input / output channels, R1 / R2 the padded ranks) plus the true ranks
+ * r1 in (0, R1], r2 in (0, R2] of the intermediates they store as contiguous NCHW tensors of `dtype`.
+ *   _save : tadmm_ttconv_fused that also writes H1 (B, r1, H, W) = W1 x and H2 (B, r2, Ho, Wo) = conv(H1; Wc).  A pixel
+ *           of H1 that no tap of any output pixel reads is written as zero (it contributes to no gradient).
+ *   _bwd  : the data gradient dX = W1^T conv^T(W3^T dY; Wc) in one launch (transposed gather, nothing flipped):
+ *           d->X = dY (B, Nout, Ho, Wo), d->Y = dX (B, C, H, W), d->W1 = planes of W3^T (R2 x Nout, rows padded to 32),
+ *           d->W2 = planes of the transposed core (R1 x kh*kw*R2, tap-major as for tadmm_core_conv_dgrad), d->W3 =
+ *           planes of W1^T (C x R1); d->bias is ignored.  Input pixels no tap reaches get exact zeros.  dH1 (B, r1, H, W)
+ *           and dH2 (B, r2, Ho, Wo) receive the two intermediates (what the weight gradients read), or both are NULL.
+ * Every element of the stored tensors is written by exactly one workgroup, chosen by the geometry alone: results are
+ * bitwise reproducible, and nothing outside the tensors is written.
+ * tadmm_ttconv_fused_plan is host only (no device): the tiling a launch of `mode` would use -- pixels and destination
+ * rows per workgroup, 64- or 32-pixel tiles of its halo, workgroups per image, LDS bytes (any pointer may be NULL;
+ * operand pointers of the descriptor are not read) -- and the one statement of the eligibility rule.
+ * TADMM_ERR_INVALID: a non-positive extent, stride or dilation, negative padding or B, Ho / Wo that are not the output
+ * size of the geometry, unknown dtype or mode, a null or misaligned operand with B > 0, weight planes too small or
+ * misaligned, r1 / r2 outside (0, R1] / (0, R2], exactly one of dH1 / dH2 NULL.  TADMM_ERR_UNSUPPORTED: the
+ * destination plane of the mode (Wo forward, W backward) wider than 64, a halo or intermediates beyond the LDS, a rank
+ * above 256.  Nothing is launched in any of these cases; B == 0 succeeds with nothing launched. */
+enum { TADMM_CONV_CHAIN_FWD = 0, TADMM_CONV_CHAIN_BWD = 1 };
+int tadmm_ttconv_fused_save(tadmm_handle h, const tadmm_conv_chain_desc* d, int r1, int r2, void* H1, void* H2, void* stream);
+int tadmm_ttconv_fused_bwd(tadmm_handle h, const tadmm_conv_chain_desc* d, int r1, int r2, void* dH1, void* dH2, void* stream);
+int tadmm_ttconv_fused_plan(const tadmm_conv_chain_desc* d, int mode, int* tile_pixels, int* tile_rows, int* halo_tiles,
+                            int* tiles_per_image, size_t* lds_bytes);
 
 /* ---- k x k core convolution of the factorised layers (csrc/coreconv.hip, csrc/wgrad.hip) ---------------------------
  * The convolution between the two 1x1 stages of TTConv2dM (TTConv.py:130-153) and TKConv2dC / TKConv2dM
