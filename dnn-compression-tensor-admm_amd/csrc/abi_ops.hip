@@ -146,7 +146,8 @@ static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, con
   }
   if (!c->X || !c->Y || !c->Win || (fused && !c->Wout)) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: null operand");
   if (c->T < 0 || c->Kin <= 0 || c->R <= 0 || (fused && c->Nout <= 0)) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: bad shape");
-  if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: bad dtype");
+  if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16 && c->dtype != TADMM_CHAIN_F16)
+    CTX_FAIL(h, TADMM_ERR_INVALID, "chain: bad dtype");
   const int epl = c->dtype == TADMM_CHAIN_F32 ? 4 : 8;          // elements per 16-byte load of X
   const int64_t ks1 = (c->Kin + 31) / 32, nt1 = (c->R + 15) / 16;
   if ((((uintptr_t)c->Win) & 15) || c->win_plane < nt1 * ks1 * 512 || (c->win_plane & 7))
@@ -195,7 +196,8 @@ int tadmm_conv_chain_desc_bytes(void) { return (int)sizeof(tadmm_conv_chain_desc
 // descriptor in the roles of `mode` (forward: source = X on H x W, destination = Y on Ho x Wo; data gradient: source = dY
 // on Ho x Wo, destination = dX on H x W, the ranks and channel counts swapped) without touching an operand.
 static int conv_chain_shape(tadmm_handle h, const tadmm_conv_chain_desc* c, int mode, ConvChainDesc& d, size_t* lds) {
-  if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: bad dtype");
+  if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16 && c->dtype != TADMM_CHAIN_F16)
+    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: bad dtype");
   if (c->B < 0 || c->C <= 0 || c->Nout <= 0 || c->H <= 0 || c->W <= 0 || c->kh <= 0 || c->kw <= 0 || c->stride_h <= 0 ||
       c->stride_w <= 0 || c->dil_h <= 0 || c->dil_w <= 0 || c->pad_h < 0 || c->pad_w < 0)
     CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: bad geometry");
@@ -260,6 +262,8 @@ static int conv_chain_train(tadmm_handle h, const tadmm_conv_chain_desc* c, int 
   DeviceGuard device_guard(h);
   if (!h) return TADMM_ERR_INVALID;
   if (!c) CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: null descriptor");
+  if (c->dtype == TADMM_CHAIN_F16)   // these outputs feed the weight gradients, which take float32 and bfloat16 only
+    CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: binary16 is inference only (tadmm_ttconv_fused)");
   ConvChainDesc d;
   const int rc = conv_chain_shape(h, c, mode, d, nullptr);
   if (rc != TADMM_OK) return rc;

@@ -8,7 +8,9 @@
 //            written in place (no NHWC copy).
 //
 // Two arithmetic modes, one code path (template parameter P = number of bf16 planes per operand):
-//   P = 1  bf16 in / bf16 out, fp32 accumulate.
+//   P = 1  bf16 in / bf16 out, fp32 accumulate.  The same path runs IEEE binary16 in / out (inference): the element
+//          type of the activations is the tag (chain_common.h) that swaps the MFMA (v_mfma_f32_16x16x32_f16) and the
+//          fp32 -> 16-bit conversions of the epilogue and of the LDS intermediate; weights are one binary16 plane.
 //   P = 3  fp32 in / fp32 out.  Every fp32 operand value is split EXACTLY into three bf16 terms x = x1 + x2 + x3
 //          (8 significant bits each); the six partial products whose weight is >= 2^-16 of the leading one
 //          (x1y1, x1y2, x2y1, x1y3, x3y1, x2y2) go through the bf16 matrix cores into one fp32 accumulator, smallest
@@ -40,6 +42,8 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
   // token fragments are double-buffered only in bf16 mode: with three planes a k-step is 6x as many MFMAs, the LDS
   // latency is a few percent of it, and the second fragment set would push the kernel into AGPR copies
   constexpr bool ADB = (P == 1);
+  constexpr bool F16 = kIsF16<TIn>;                            // binary16 instead of bfloat16 elements (P == 1 only)
+  static_assert(kIsF16<TIn> == kIsF16<TOut>, "one 16-bit element type per launch");
   constexpr int AS = ADB ? 2 : 1;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
         load_w<P, kNB1>(b[nxt], w1, d.win_plane, min(snext, KS1 - 1));
         if constexpr (ADB) {
           if (ks + 1 < SPC) load_x<P, TM>(a[nxt], Xc, LDX, ks + 1, r, q);
-          mma_step<P, MT, kNB1>(a[cur], b[cur], acc);
+          mma_step<P, MT, kNB1, F16>(a[cur], b[cur], acc);
         } else {
           if (ks + 1 < SPC) load_x3<TM>(a0[nxt], Xc, LDX, ks + 1, 0, r, q);
           mma_stream3<TM, kNB1>(Xc, LDX, ks, r, q, a0[cur], b[cur], acc);
@@ -128,8 +132,8 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
         const int f0 = (wave * kNB1 + j) * 16 + 4 * q;
         if (f0 >= d.R) continue;
         uint32_t s0[P], s1[P];
-        split2<P>(acc[mt][j][0], acc[mt][j][1], s0);
-        split2<P>(acc[mt][j][2], acc[mt][j][3], s1);
+        split2<P, F16>(acc[mt][j][0], acc[mt][j][1], s0);
+        split2<P, F16>(acc[mt][j][2], acc[mt][j][3], s1);
 #pragma unroll
         for (int p = 0; p < P; ++p)
           *reinterpret_cast<uint2*>(&Hs[(p * TM + 16 * mt + r) * ldh + f0]) = make_uint2(s0[p], s1[p]);
@@ -177,7 +181,7 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
         load_w<P, NB2>(b[1], w2, d.wout_plane, ks + 1);
         if constexpr (ADB) {
           load_x<P, TM>(a[1], Hs, ldh, ks + 1, r, q);
-          mma_step<P, MT, NB2>(a[0], b[0], acc2);
+          mma_step<P, MT, NB2, F16>(a[0], b[0], acc2);
         } else {
           load_x3<TM>(a0[1], Hs, ldh, ks + 1, 0, r, q);
           mma_stream3<TM, NB2>(Hs, ldh, ks, r, q, a0[0], b[0], acc2);
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
         else load_w<P, NB2>(b[0], w2, d.wout_plane, ks + 2);
         if constexpr (ADB) {
           load_x<P, TM>(a[0], Hs, ldh, last ? 0 : ks + 2, r, q);
-          mma_step<P, MT, NB2>(a[1], b[1], acc2);
+          mma_step<P, MT, NB2, F16>(a[1], b[1], acc2);
         } else {
           load_x3<TM>(a0[0], Hs, ldh, last ? 0 : ks + 2, 0, r, q);
           mma_stream3<TM, NB2>(Hs, ldh, ks + 1, r, q, a0[1], b[1], acc2);
@@ -253,6 +257,10 @@ int launch_fused(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) 
     if (tile_tokens == 64) return launch_variant<1, 64, 128, 6, KS2T, uint16_t, uint16_t, true, false, false>(d, s);
     return launch_variant<1, 32, 128, 6, KS2T, uint16_t, uint16_t, true, false, false>(d, s);
   }
+  if (dtype == 2) {
+    if (tile_tokens == 64) return launch_variant<1, 64, 128, 6, KS2T, _Float16, _Float16, true, false, false>(d, s);
+    return launch_variant<1, 32, 128, 6, KS2T, _Float16, _Float16, true, false, false>(d, s);
+  }
   if (tile_tokens == 32) return launch_variant<3, 32, 128, 6, KS2T, float, float, true, false, false>(d, s);
   return launch_variant<3, 64, 64, 3, KS2T, float, float, true, false, false>(d, s);
 }
@@ -275,6 +283,10 @@ int launch_fused_img(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t
     if (tile_tokens == 64) return launch_variant<1, 64, 128, 6, KS2T, uint16_t, uint16_t, true, true, true>(d, s);
     return launch_variant<1, 32, 128, 6, KS2T, uint16_t, uint16_t, true, true, true>(d, s);
   }
+  if (dtype == 2) {
+    if (tile_tokens == 64) return launch_variant<1, 64, 128, 6, KS2T, _Float16, _Float16, true, true, true>(d, s);
+    return launch_variant<1, 32, 128, 6, KS2T, _Float16, _Float16, true, true, true>(d, s);
+  }
   if (tile_tokens == 32) return launch_variant<3, 32, 128, 6, KS2T, float, float, true, true, true>(d, s);
   return launch_variant<3, 64, 64, 3, KS2T, float, float, true, true, true>(d, s);
 }
@@ -294,12 +306,14 @@ int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStre
   }
 }
 
-// dtype 0: fp32 in/out through three bf16 planes per operand; dtype 1: bf16 in/out.  Returns 0, or -1 when the shape
+// dtype 0: fp32 in/out through three bf16 planes per operand; dtype 1: bf16 in/out; dtype 2: binary16 in/out, the
+// one-plane kernels with the f16 MFMA and conversions.  Returns 0, or -1 when the shape
 // does not fit the kernel (the caller reports it; there is no other path inside the library).
 int launch_tt_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
   if (d.T <= 0) return 0;
   if (!d.fused) {
     if (dtype == 1) return launch_single<1, 64, 128, uint16_t>(d, s);
+    if (dtype == 2) return launch_single<1, 64, 128, _Float16>(d, s);
     return launch_single<3, 64, 64, float>(d, s);
   }
   if (d.x_hw > 0 || d.y_hw > 0 || d.R % 64 || d.R > 256) return -1;

@@ -2,11 +2,13 @@
 // loader, fragment loads, staged stores.  See chain.hip for the scheme.  Everything lives in an unnamed namespace: each
 // translation unit gets its own copy.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace tadmm {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float float4v_t __attribute__((ext_vector_type(4)));
 // weight pointers carry their address space: through arrays and selects hipcc otherwise degrades them to generic
 // pointers, and flat loads count on vmcnt AND lgkmcnt -- every wait behind them becomes a full drain
@@ -27,8 +29,34 @@ __device__ __forceinline__ uint32_t pack_bf16(float x, float y) {
 }
 __device__ __forceinline__ uint16_t bf16_rne(float f) { return (uint16_t)pack_bf16(f, 0.f); }
 
+// ---- the 16-bit element of single-plane mode.  The activation type is the tag: uint16_t = bfloat16 (the loaders move
+// 16-bit words without looking at them), _Float16 = IEEE binary16.  The tag selects the MFMA, the conversion of the
+// epilogues and the conversion of the intermediates kept in LDS; fragments stay in bf16x8_t registers either way (the
+// cast at the MFMA is free).  Conversions round to nearest even, binary16 overflows to +-inf (v_cvt_pk_f16_f32 /
+// v_cvt_f16_f32, no clamp) as Tensor.half() does.
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+template <typename T> constexpr bool kIsF16 = std::is_same<T, _Float16>::value;
+
+template <bool F16> __device__ __forceinline__ uint32_t pack16(float x, float y) {
+  if constexpr (F16) return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2v_t){x, y}, f16x2_t));
+  else return pack_bf16(x, y);
+}
+template <bool F16> __device__ __forceinline__ uint16_t rne16(float f) {
+  if constexpr (F16) return __builtin_bit_cast(uint16_t, (_Float16)f);
+  else return bf16_rne(f);
+}
+template <bool F16>
+__device__ __forceinline__ float4v_t mfma16(const bf16x8_t w, const bf16x8_t x, const float4v_t acc) {
+  if constexpr (F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, x), acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc, 0, 0, 0);
+}
+
 // (x, y) -> P packed pairs with x = sum_p plane_p exactly (P == 3), or its rounding (P == 1)
-template <int P> __device__ __forceinline__ void split2(float x, float y, uint32_t (&o)[P]) {
+// (F16: P == 1, the binary16 rounding)
+template <int P, bool F16 = false> __device__ __forceinline__ void split2(float x, float y, uint32_t (&o)[P]) {
+  static_assert(!F16 || P == 1, "binary16 is a single-plane mode");
+  if constexpr (F16) { o[0] = pack16<true>(x, y); return; }
   float2v_t v = {x, y};
 #pragma unroll
   for (int p = 0; p < P; ++p) {
@@ -39,14 +67,14 @@ template <int P> __device__ __forceinline__ void split2(float x, float y, uint32
 }
 
 // acc[mt][j] += sum over the kept plane pairs of  W-fragment(plane pb, tile j) x token-fragment(plane pa, tile mt)
-template <int P, int MT, int NB>
+template <int P, int MT, int NB, bool F16 = false>
 __device__ __forceinline__ void mma_step(const bf16x8_t (&a)[P][MT], const bf16x8_t (&b)[P][NB],
                                          float4v_t (&acc)[MT][NB]) {
   if constexpr (P == 1) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int j = 0; j < NB; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0][j], a[0][mt], acc[mt][j], 0, 0, 0);
+      for (int j = 0; j < NB; ++j) acc[mt][j] = mfma16<F16>(b[0][j], a[0][mt], acc[mt][j]);
   } else {
     constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
@@ -76,7 +104,7 @@ __device__ __forceinline__ void store4(TOut* Y, int64_t t, int f0, int N, int64_
     if constexpr (sizeof(TOut) == 4) {
       *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
     } else {
-      *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]));
+      *reinterpret_cast<uint2*>(p) = make_uint2(pack16<kIsF16<TOut>>(o[0], o[1]), pack16<kIsF16<TOut>>(o[2], o[3]));
     }
     return;
   }
@@ -85,7 +113,7 @@ __device__ __forceinline__ void store4(TOut* Y, int64_t t, int f0, int N, int64_
     if (f0 + e < N) {
       TOut* p = Y + elem_off(t, f0 + e, ldy, YIMG ? hw : 0, N);
       if constexpr (sizeof(TOut) == 4) *p = o[e];
-      else *p = bf16_rne(o[e]);
+      else *reinterpret_cast<uint16_t*>(p) = rne16<kIsF16<TOut>>(o[e]);
     }
 }
 
@@ -277,7 +305,7 @@ __device__ __forceinline__ void store_group(const ChainDesc& d, float4v_t (&acc)
                       o3 = acc[mt][j][3] + bq[j].w;
           if constexpr (SZ == 4) *reinterpret_cast<float4*>(p) = make_float4(o0, o1, o2, o3);
           else {
-            *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16(o0, o1), pack_bf16(o2, o3));
+            *reinterpret_cast<uint2*>(p) = make_uint2(pack16<kIsF16<TOut>>(o0, o1), pack16<kIsF16<TOut>>(o2, o3));
           }
         }
 #pragma unroll
@@ -309,7 +337,7 @@ __device__ __forceinline__ void store_group(const ChainDesc& d, float4v_t (&acc)
           for (int e = 0; e < 4; ++e) {
             uint8_t* p = stage + (16 * (j - j0) + 4 * q + e) * SLD + (16 * mt + r) * SZ;
             if constexpr (SZ == 4) *reinterpret_cast<float*>(p) = o[e];
-            else *reinterpret_cast<uint16_t*>(p) = bf16_rne(o[e]);
+            else *reinterpret_cast<uint16_t*>(p) = rne16<kIsF16<TOut>>(o[e]);
           }
         }
 #pragma unroll

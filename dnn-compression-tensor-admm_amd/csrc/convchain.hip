@@ -50,11 +50,11 @@ __device__ __forceinline__ void gather_x(bf16x8_t (&a)[P], const uint16_t* img, 
   }
 }
 
-template <int P, int NB>
+template <int P, int NB, bool F16 = false>
 __device__ __forceinline__ void mma_tile(const bf16x8_t (&a)[P], const bf16x8_t (&b)[P][NB], float4v_t (&acc)[NB]) {
   if constexpr (P == 1) {
 #pragma unroll
-    for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0][j], a[0], acc[j], 0, 0, 0);
+    for (int j = 0; j < NB; ++j) acc[j] = mfma16<F16>(b[0][j], a[0], acc[j]);
   } else {
     constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
@@ -65,7 +65,7 @@ __device__ __forceinline__ void mma_tile(const bf16x8_t (&a)[P], const bf16x8_t 
 }
 
 // acc (features 4q..4q+3 of token row0 + r, tile j) -> P planes of an LDS image [P][prow][ld]
-template <int P, int TM, int NB>
+template <int P, int TM, int NB, bool F16 = false>
 __device__ __forceinline__ void acc_to_lds(const float4v_t (&acc)[TM / 16][NB], uint16_t* img, int prow, int row0, int ld,
                                            int f_base, int nfeat, int r, int q) {
 #pragma unroll
@@ -75,8 +75,8 @@ __device__ __forceinline__ void acc_to_lds(const float4v_t (&acc)[TM / 16][NB], 
       const int f0 = f_base + 16 * j + 4 * q;
       if (f0 >= nfeat) continue;
       uint32_t s0[P], s1[P];
-      split2<P>(acc[mt][j][0], acc[mt][j][1], s0);
-      split2<P>(acc[mt][j][2], acc[mt][j][3], s1);
+      split2<P, F16>(acc[mt][j][0], acc[mt][j][1], s0);
+      split2<P, F16>(acc[mt][j][2], acc[mt][j][3], s1);
 #pragma unroll
       for (int p = 0; p < P; ++p)
         *reinterpret_cast<uint2*>(&img[(p * prow + row0 + 16 * mt + r) * ld + f0]) = make_uint2(s0[p], s1[p]);
@@ -173,6 +173,8 @@ template <int P, int TM, int KC, int NBW, typename T, bool BWD, bool SAVE>
 __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
   extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
   constexpr int MT = TM / 16, LDX = KC + kPad, SPC = KC / 32;
+  constexpr bool F16 = kIsF16<T>;                          // binary16 elements: inference forward only
+  static_assert(!F16 || (!BWD && !SAVE), "the binary16 convolution has no data gradient and saves nothing");
   constexpr int kStageBytes = 2 * P * TM * LDX * 2 / 4;    // per wave: a quarter of the chunk buffers (free after product 1)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,14 +250,14 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
 #pragma unroll
             for (int p = 0; p < P; ++p)
               a[p] = *reinterpret_cast<const bf16x8_t*>(&Xc[(p * TM + 16 * mt + r) * LDX + 32 * ks + 8 * q]);
-            mma_tile<P, NBW>(a, b[ks % RD1], acc[mt]);
+            mma_tile<P, NBW, F16>(a, b[ks % RD1], acc[mt]);
           }
         }
         static_assert(SPC % RD1 == 0, "fragment ring returns to slot 0 at every chunk boundary");
         ld.store(Xs + ((c + 1) & 1) * (P * TM * LDX), tid);
         __syncthreads();
       }
-      acc_to_lds<P, TM, NBW>(acc, H1s, prow1, TM * tt, ld1, wave * NBW * 16, d.R1, r, q);
+      acc_to_lds<P, TM, NBW, F16>(acc, H1s, prow1, TM * tt, ld1, wave * NBW * 16, d.R1, r, q);
     }
   }
   __syncthreads();
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
             const int row = live ? (int)tab[tap * TM + 16 * mt + r] : -1;
             bf16x8_t a[P];
             gather_x<P>(a, H1s, prow1, ld1, row, ks, q);
-            mma_tile<P, NBW>(a, b[u], acc[mt]);
+            mma_tile<P, NBW, F16>(a, b[u], acc[mt]);
           }
         } else {
           const int dy = tap / d.kw, dx = tap - dy * d.kw;
@@ -333,7 +335,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
             const bool in = live && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
             bf16x8_t a[P];
             gather_x<P>(a, H1s, prow1, ld1, in ? (iy - iy_lo) * d.W + ix : -1, ks, q);
-            mma_tile<P, NBW>(a, b[u], acc[mt]);
+            mma_tile<P, NBW, F16>(a, b[u], acc[mt]);
           }
         }
         ks += 1;
@@ -341,7 +343,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
         if (tap >= taps) { tap = taps - 1; }                  // keeps the surplus steps' addresses valid
       }
     }
-    acc_to_lds<P, TM, NBW>(acc, H2s, TM, 0, ld2, wave * NBW * 16, d.R2, r, q);
+    acc_to_lds<P, TM, NBW, F16>(acc, H2s, TM, 0, ld2, wave * NBW * 16, d.R2, r, q);
   }
   __syncthreads();
 
@@ -380,7 +382,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
           for (int mt = 0; mt < MT; ++mt) {
             bf16x8_t a[P];
             gather_x<P>(a, H2s, TM, ld2, t < KS3 ? 16 * mt + r : -1, min(t, KS3 - 1), q);
-            mma_tile<P, NB3>(a, b[u], acc[mt]);
+            mma_tile<P, NB3, F16>(a, b[u], acc[mt]);
           }
         }
       }
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
               if (px < n_out && fl < nf) {
                 const float v = acc[mt][j][e] + (d.bias ? d.bias[f_base + fl] : 0.f);
                 if constexpr (SZ == 4) st[fl * n_out + px] = v;
-                else st[fl * n_out + px] = bf16_rne(v);
+                else reinterpret_cast<uint16_t*>(st)[fl * n_out + px] = rne16<F16>(v);
               }
             }
         }
@@ -437,7 +439,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
               const float v = acc[mt][j][e] + (d.bias ? d.bias[f] : 0.f);
               T* p = Y + ((int64_t)img * d.Nout + f) * hw_out + oy0 * d.Wo + px;
               if constexpr (SZ == 4) *p = v;
-              else *p = bf16_rne(v);
+              else *reinterpret_cast<uint16_t*>(p) = rne16<F16>(v);
             }
         }
       }
@@ -470,8 +472,13 @@ int launch_conv_mode(const ConvChainDesc& d, hipStream_t s) {
 template <int P, int TM, int KC, int NBW, typename T>
 int launch_conv_nbw(const ConvChainDesc& d, hipStream_t s) {
   const bool save = d.S1 != nullptr;
-  if (d.transposed) return save ? launch_conv_mode<P, TM, KC, NBW, T, true, true>(d, s) : launch_conv_mode<P, TM, KC, NBW, T, true, false>(d, s);
-  return save ? launch_conv_mode<P, TM, KC, NBW, T, false, true>(d, s) : launch_conv_mode<P, TM, KC, NBW, T, false, false>(d, s);
+  if constexpr (kIsF16<T>) {                                   // forward without intermediates is all binary16 has
+    if (save || d.transposed) return -1;
+    return launch_conv_mode<P, TM, KC, NBW, T, false, false>(d, s);
+  } else {
+    if (d.transposed) return save ? launch_conv_mode<P, TM, KC, NBW, T, true, true>(d, s) : launch_conv_mode<P, TM, KC, NBW, T, true, false>(d, s);
+    return save ? launch_conv_mode<P, TM, KC, NBW, T, false, true>(d, s) : launch_conv_mode<P, TM, KC, NBW, T, false, false>(d, s);
+  }
 }
 
 template <int P, int TM, int KC, typename T>
@@ -500,7 +507,7 @@ bool plan_tt_conv(ConvChainDesc& d, int dtype, size_t* lds_bytes) {
     }
     if (tr < 1) continue;
     d.TM = tmx; d.TR = tr; d.tiles = (d.Ho + tr - 1) / tr; d.NT = nt;
-    const size_t lds = dtype == 1 ? conv_lds_bytes<1, 128>(d) : conv_lds_bytes<3, 64>(d);
+    const size_t lds = dtype != 0 ? conv_lds_bytes<1, 128>(d) : conv_lds_bytes<3, 64>(d);   // both 16-bit types: one plane
     if (lds > kConvMaxLds) continue;
     if (lds_bytes) *lds_bytes = lds;
     return true;
@@ -508,15 +515,17 @@ bool plan_tt_conv(ConvChainDesc& d, int dtype, size_t* lds_bytes) {
   return false;
 }
 
-// dtype 0: fp32 through three bf16 planes; 1: bf16.  -1: the intermediates do not fit the LDS (the caller takes the
+// dtype 0: fp32 through three bf16 planes; 1: bf16; 2: binary16 (forward only, nothing saved).  -1: the intermediates do not fit the LDS (the caller takes the
 // three-launch path).
 int launch_tt_conv(const ConvChainDesc& d, int dtype, hipStream_t s) {
   if (d.B <= 0) return 0;
   if (d.TM == 32) {
     if (dtype == 1) return launch_conv_variant<1, 32, 128, uint16_t>(d, s);
+    if (dtype == 2) return launch_conv_variant<1, 32, 128, _Float16>(d, s);
     return launch_conv_variant<3, 32, 64, float>(d, s);
   }
   if (dtype == 1) return launch_conv_variant<1, 64, 128, uint16_t>(d, s);
+  if (dtype == 2) return launch_conv_variant<1, 64, 128, _Float16>(d, s);
   return launch_conv_variant<3, 64, 64, float>(d, s);
 }
 

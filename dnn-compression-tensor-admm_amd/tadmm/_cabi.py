@@ -78,7 +78,7 @@ class ConvChainDesc(C.Structure):
     ]
 
 
-CHAIN_F32, CHAIN_BF16 = 0, 1
+CHAIN_F32, CHAIN_BF16, CHAIN_F16 = 0, 1, 2    # F16: inference entries only (include/tadmm.h)
 CONV_CHAIN_FWD, CONV_CHAIN_BWD = 0, 1
 
 

@@ -77,21 +77,25 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor = None) -> 
 # ---------------------------------------------------------------------------------------------------------------
 # Forward chains on the bf16 matrix cores (csrc/chain.hip): one launch per chain, the per-token intermediate of the
 # fused TT-linear chain stays in LDS.  float32 tensors go through the exact three-plane bf16 split (fp32-GEMM
-# accuracy), bfloat16 tensors through one plane.
+# accuracy), bfloat16 tensors through one plane.  float16 tensors (inference only: what the reference's evaluate() under
+# autocast hands a layer) run the one-plane kernels with ONE binary16 plane.
 # ---------------------------------------------------------------------------------------------------------------
 def planes_of(w: torch.Tensor, nplanes: int, pad_rows: int = 16, pad_cols: int = 32, transpose: bool = False,
-              cache: dict = None, tag=None):
-    """Fragment-major bf16 planes of a 2-D weight (`ops.weight_planes`).  With `cache` (a dict owned by the layer) the
-    packing is reused until the weight's version counter or storage address changes -- inference packs a layer once
-    (`param_key` for what that cannot see)."""
+              cache: dict = None, tag=None, like: torch.Tensor = None):
+    """Fragment-major planes of a 2-D weight (`ops.weight_planes`): bfloat16, or binary16 when `like` -- the activations
+    the planes will multiply -- is float16.  With `cache` (a dict owned by the layer) the packing is reused until the
+    weight's version counter or storage address changes -- inference packs a layer once (`param_key` for what that
+    cannot see); the plane dtype is part of the key, so bfloat16 and float16 planes of one weight are kept side by side here
+    (the layers' contracted-factor caches hold one entry and repack when the activation dtype changes)."""
+    pdt = plane_dtype(like)
     key = None
     if cache is not None:
-        key = (tag, (w._version, w.data_ptr()), tuple(w.shape), nplanes, pad_rows, pad_cols, transpose)
+        key = (tag, (w._version, w.data_ptr()), tuple(w.shape), nplanes, pad_rows, pad_cols, transpose, pdt)
         hit = cache.get(key)
         if hit is not None:
             return hit
     src = w.detach()
-    wp = ops.weight_planes(src.t() if transpose else src, nplanes, pad_rows, pad_cols)
+    wp = ops.weight_planes(src.t() if transpose else src, nplanes, pad_rows, pad_cols, dtype=pdt)
     if cache is not None:
         for k in [k for k in cache if k[0] == tag and k[3:] == key[3:]]:
             del cache[k]                                            # older versions of the same weight
@@ -132,9 +136,29 @@ class InferenceCacheMixin:
 def _nplanes(x: torch.Tensor) -> int:
     if x.dtype == torch.float32:
         return 3
-    if x.dtype == torch.bfloat16:
+    if x.dtype in (torch.bfloat16, torch.float16):
         return 1
-    raise TadmmError(-1, f"chain kernels take float32 or bfloat16 activations (got {x.dtype})")
+    raise TadmmError(-1, f"chain kernels take float32, bfloat16 or (inference) float16 activations (got {x.dtype})")
+
+
+def plane_dtype(x: torch.Tensor = None) -> torch.dtype:
+    """dtype of the weight planes that multiply activations x: binary16 for float16, bfloat16 otherwise (float32
+    activations read three bfloat16 planes)."""
+    return torch.float16 if x is not None and x.dtype == torch.float16 else torch.bfloat16
+
+
+def chain_dtype_ok(x: torch.Tensor, *params) -> bool:
+    """True when the chain kernels take x on behalf of a layer with these parameters: float32 and bfloat16 always,
+    float16 for inference only -- nothing among x and the parameters may want a gradient (there is no float16 weight
+    gradient; grad mode keeps the per-core route)."""
+    if x.dtype in (torch.float32, torch.bfloat16):
+        return True
+    return x.dtype == torch.float16 and not _needs_grad(x, *params)
+
+
+def _inference_only(x: torch.Tensor):
+    if x.dtype == torch.float16:
+        raise TadmmError(-1, "float16 activations are inference only: nothing they meet may require a gradient")
 
 
 def _needs_grad(*tensors) -> bool:
@@ -153,6 +177,7 @@ class _ChainSingle(torch.autograd.Function):
     def forward(ctx, x, w, bias, entry, wp):
         if not x.is_cuda:
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
+        _inference_only(x)
         image = x.dim() == 4
         fresh = wp is None                          # planes packed for this call only: keep them out of the launch memo
         if fresh:
@@ -185,7 +210,7 @@ def pointwise(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor = None, entry
     if not _needs_grad(x, w, bias):                   # inference: straight to the C ABI, no autograd node
         fresh = planes is None
         if fresh:
-            planes = planes_of(w, _nplanes(x))
+            planes = planes_of(w, _nplanes(x), like=x)
         if x.dim() == 4:
             return ops.chain_single(x, planes, bias, w.shape[0], entry=entry, image_out=True, memo=not fresh)
         lead = x.shape[:-1]
@@ -204,6 +229,7 @@ class _ChainFused(torch.autograd.Function):
     def forward(ctx, x, w_in, w_out, bias, planes):
         if not x.is_cuda:
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
+        _inference_only(x)
         n = _nplanes(x)
         fresh = planes is None
         if fresh:
@@ -244,7 +270,7 @@ def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias:
         fresh = planes is None
         if fresh:
             n = _nplanes(x)
-            planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
+            planes = (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x))
         return ops.chain_fused(x.reshape(-1, x.shape[-1]), planes[0], planes[1], bias, w_out.shape[0],
                                memo=not fresh).reshape(*lead, w_out.shape[0])
     return _ChainFused.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes).reshape(*lead, w_out.shape[0])
@@ -257,6 +283,7 @@ class _Conv1x1Chain(torch.autograd.Function):
     def forward(ctx, x, w_in, w_out, bias, planes):
         if not x.is_cuda:
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
+        _inference_only(x)
         n = _nplanes(x)
         fresh = planes is None
         if fresh:
@@ -302,7 +329,7 @@ def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias
         fresh = planes is None
         if fresh:
             n = _nplanes(x)
-            planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
+            planes = (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x))
         return ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
     return _Conv1x1Chain.apply(x.contiguous(), w_in, w_out, bias, planes)
 
@@ -398,20 +425,21 @@ def _core_dgrad_library(dh2, h1_shape, core, stride, padding, dilation):
                                                1, [True, False, False])[0]
 
 
-def _conv_chain_planes(w_in, core, w_out, n, transposed):
+def _conv_chain_planes(w_in, core, w_out, n, transposed, pdt=torch.bfloat16):
     if transposed:                                    # nothing is flipped: the kernel's transposed gather maps the taps
-        return (ops.weight_planes(w_out.detach().t(), n, pad_rows=32), ops.conv_core_planes(core.permute(1, 0, 2, 3), n),
-                ops.weight_planes(w_in.detach().t(), n))
-    return (ops.weight_planes(w_in.detach(), n, pad_rows=32), ops.conv_core_planes(core, n), ops.weight_planes(w_out.detach(), n))
+        return (ops.weight_planes(w_out.detach().t(), n, pad_rows=32, dtype=pdt),
+                ops.conv_core_planes(core.permute(1, 0, 2, 3), n, dtype=pdt), ops.weight_planes(w_in.detach().t(), n, dtype=pdt))
+    return (ops.weight_planes(w_in.detach(), n, pad_rows=32, dtype=pdt), ops.conv_core_planes(core, n, dtype=pdt),
+            ops.weight_planes(w_out.detach(), n, dtype=pdt))
 
 
-def _cached_conv_chain_planes(cache, w_in, core, w_out, n, device, transposed):
+def _cached_conv_chain_planes(cache, w_in, core, w_out, n, device, transposed, pdt=torch.bfloat16):
     if cache is None:
-        return _conv_chain_planes(w_in, core, w_out, n, transposed)
+        return _conv_chain_planes(w_in, core, w_out, n, transposed, pdt)
     tag = "tplanes_t" if transposed else "tplanes"
-    key = (n, device, param_key(w_in, core, w_out))
+    key = (n, pdt, device, param_key(w_in, core, w_out))
     if cache.get(tag + "_key") != key:
-        cache[tag + "_key"], cache[tag] = key, _conv_chain_planes(w_in, core, w_out, n, transposed)
+        cache[tag + "_key"], cache[tag] = key, _conv_chain_planes(w_in, core, w_out, n, transposed, pdt)
     return cache[tag]
 
 
@@ -422,6 +450,7 @@ class _ConvChain(torch.autograd.Function):
     def forward(ctx, x, w_in, core, w_out, bias, stride, padding, dilation, cache):
         if not x.is_cuda:
             raise TadmmError(-1, "conv chain operands must live on the HIP device (no CPU fallback)")
+        _inference_only(x)
         n = _nplanes(x)
         ksize = tuple(core.shape[2:])
         r1, r2 = w_in.shape[0], w_out.shape[1]
@@ -497,7 +526,7 @@ def conv_chain(x: torch.Tensor, w_in: torch.Tensor, core: torch.Tensor, w_out: t
         raise TadmmError(-5, "conv_chain: the plane, halo or ranks do not fit the one-launch kernel (ops.conv_chain_fits)")
     if _needs_grad(x, w_in, core, w_out, bias):
         return _ConvChain.apply(x.contiguous(), w_in, core, w_out, bias, stride, padding, dilation, cache)
-    p1, p2, p3 = _cached_conv_chain_planes(cache, w_in, core, w_out, _nplanes(x), x.device, False)
+    p1, p2, p3 = _cached_conv_chain_planes(cache, w_in, core, w_out, _nplanes(x), x.device, False, plane_dtype(x))
     return ops.conv_chain(x, p1, p2, p3, bias, w_out.shape[0], ksize, stride, padding, dilation, memo=cache is not None)
 
 

@@ -428,20 +428,26 @@ def wgrad(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, 
 
 
 # ------------------------------------------------------------------ forward chains (csrc/chain.hip)
-def weight_planes(w: torch.Tensor, planes: int, pad_rows: int = 16, pad_cols: int = 32) -> torch.Tensor:
+def weight_planes(w: torch.Tensor, planes: int, pad_rows: int = 16, pad_cols: int = 32,
+                  dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """(N, K) weight -> (planes, Np/16, Kp/32, 64, 8) bfloat16 in the fragment-major order of csrc/chain.hip
     (Kp = K rounded up to `pad_cols`, a multiple of 32; Np = N rounded up to `pad_rows`, a multiple of 16; zero
     padded).  The fused chain wants its middle rank padded to 64: `pad_rows=64` for Win, `pad_cols=64` for Wout.
-    planes == 3: the exact three-term split w = w1 + w2 + w3 of a float32 weight; planes == 1: its bf16 rounding."""
+    planes == 3: the exact three-term split w = w1 + w2 + w3 of a float32 weight; planes == 1: its bf16 rounding.
+    `dtype=torch.float16` (planes == 1 only): the binary16 rounding of w in the same order, for float16 activations."""
     assert w.dim() == 2 and planes in (1, 3) and pad_rows % 16 == 0 and pad_cols % 32 == 0
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TadmmError(-1, f"weight planes are bfloat16 or float16 (got {dtype})")
+    if dtype == torch.float16 and planes != 1:
+        raise TadmmError(-1, "float16 weights are ONE plane: the three-plane split belongs to float32 activations")
     if not w.is_cuda:
         raise TadmmError(-1, "weights must live on a HIP device; there is no CPU path")
     N, K = w.shape
     Np, Kp = -(-N // pad_rows) * pad_rows, -(-K // pad_cols) * pad_cols
-    flat = torch.zeros(planes, Np, Kp, dtype=torch.bfloat16, device=w.device)
+    flat = torch.zeros(planes, Np, Kp, dtype=dtype, device=w.device)
     r = w.detach().float()
     for p in range(planes):
-        t = r.to(torch.bfloat16)
+        t = r.to(dtype)
         flat[p, :N, :K] = t
         if p + 1 < planes:
             r = r - t.float()
@@ -477,6 +483,21 @@ class _LruMemo(collections.OrderedDict):
 
 _CHAIN_MEMO = _LruMemo()
 
+# activation dtypes whose one 16-bit weight plane runs the single-plane kernels (float16: inference entries only)
+HALF_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def _chain_dtype(xdtype, who: str):
+    """(C ABI dtype, plane count, plane dtype) of an activation dtype.  The library sees `void*` planes and cannot tell
+    a bfloat16 plane from a binary16 one, so the callers compare the plane tensors' dtype with the third element."""
+    if xdtype == torch.float32:
+        return _cabi.CHAIN_F32, 3, torch.bfloat16
+    if xdtype == torch.bfloat16:
+        return _cabi.CHAIN_BF16, 1, torch.bfloat16
+    if xdtype == torch.float16:
+        return _cabi.CHAIN_F16, 1, torch.float16
+    raise TadmmError(-1, f"{who}: unsupported dtype {xdtype}")
+
 
 def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin: int, n1: int, n_out: int,
                 image_out: bool, tile_tokens: int, prepare_only: bool = False, use_memo: bool = True):
@@ -495,18 +516,14 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
     if not use_memo:
         bias_key = None                                 # short-lived planes (training): build, launch, forget
     # geometry + weight identity -> validated descriptor; only the activation pointers change between calls
-    key = (entry, tuple(x.shape), x.stride(0), x.dtype, x.device, win.data_ptr(), 0 if wout is None else wout.data_ptr(),
-           bias_key, kin, n1, n_out, image_out, tile_tokens)
+    # (the planes' dtype is part of their identity: a bfloat16 view of a binary16 plane shares its address)
+    key = (entry, tuple(x.shape), x.stride(0), x.dtype, x.device, win.data_ptr(), win.dtype,
+           (0, None) if wout is None else (wout.data_ptr(), wout.dtype), bias_key, kin, n1, n_out, image_out, tile_tokens)
     memo = _CHAIN_MEMO.lookup(key) if bias_key is not None else None
     if memo is None:
-        if x.dtype == torch.float32:
-            dtype, planes = _cabi.CHAIN_F32, 3
-        elif x.dtype == torch.bfloat16:
-            dtype, planes = _cabi.CHAIN_BF16, 1
-        else:
-            raise TadmmError(-1, f"chain: unsupported dtype {x.dtype}")
-        if win.dtype != torch.bfloat16 or win.dim() != 5 or win.shape[0] != planes or not win.is_contiguous():
-            raise TadmmError(-1, f"chain: weights must be {planes} contiguous bf16 plane(s) (ops.weight_planes)")
+        dtype, planes, pdt = _chain_dtype(x.dtype, "chain")
+        if win.dtype != pdt or win.dim() != 5 or win.shape[0] != planes or not win.is_contiguous():
+            raise TadmmError(-1, f"chain: weights must be {planes} contiguous {pdt} plane(s) (ops.weight_planes)")
         d = _cabi.ChainDesc()
         if x.dim() == 4:
             B, Cc, H, W = x.shape
@@ -533,8 +550,8 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
             raise TadmmError(-1, "chain: weight planes do not match the operand shape")
         d.win_plane = win[0].numel()
         if wout is not None:
-            if wout.dtype != torch.bfloat16 or wout.dim() != 5 or wout.shape[0] != planes or not wout.is_contiguous():
-                raise TadmmError(-1, f"chain: weights must be {planes} contiguous bf16 plane(s) (ops.weight_planes)")
+            if wout.dtype != pdt or wout.dim() != 5 or wout.shape[0] != planes or not wout.is_contiguous():
+                raise TadmmError(-1, f"chain: weights must be {planes} contiguous {pdt} plane(s) (ops.weight_planes)")
             if wout.shape[2] * 32 != n1 or wout.shape[1] * 16 < n_out:
                 raise TadmmError(-1, "chain: output weight planes do not match the middle rank / output size")
             d.wout_plane = wout[0].numel()
@@ -592,14 +609,15 @@ def svd_conv_pays(x: torch.Tensor, rank: int) -> bool:
     launch is faster on all 56 single-rank layers of svd_mobilenetv2_cifar / tk_resnet50 (1.06x - 2.3x); in fp32 (three
     planes, six MFMA products per product, the rank padded to 64) the second product's padded work costs more than the
     intermediate's round trip saves, and two launches are 4 - 17 % faster over each table.  Ranks above 256 never fit
-    the LDS of the fused kernel."""
-    return x.dtype == torch.bfloat16 and 0 < rank <= 256
+    the LDS of the fused kernel.  float16 (inference) runs the bf16 kernel with the f16 MFMA and takes bf16's rule: it times
+    as bf16 does on the chain kernels (the SVD tables themselves were not re-timed in float16)."""
+    return x.dtype in HALF_DTYPES and 0 < rank <= 256
 
 
 def _conv_chain_plan(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation):
     """(pixels per workgroup, output rows per workgroup, halo tiles, workgroups per image) of the one-launch factorised
     convolution, or None when it does not apply -- the rule tadmm_ttconv_fused applies."""
-    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return None
     H, W = x.shape[2], x.shape[3]
     ho = (H + 2 * padding[0] - dilation[0] * (kernel_size[0] - 1) - 1) // stride[0] + 1
@@ -640,17 +658,17 @@ def conv_chain_pays(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padd
     MFMA products per product) only while an image is at most two workgroups -- with more row tiles the recomputed halos
     cost more than the two launches and the round trip of the intermediates they save."""
     plan = _conv_chain_plan(x, r1, r2, kernel_size, stride, padding, dilation)
-    return plan is not None and (x.dtype == torch.bfloat16 or plan[3] <= 2)
+    return plan is not None and (x.dtype in HALF_DTYPES or plan[3] <= 2)     # float16: bf16's rule (DESIGN.md 12: times as bf16; three f16 launches are ~14 % ahead at 28x28 and 56x56, left open)
 
 
-def conv_core_planes(core: torch.Tensor, planes: int) -> torch.Tensor:
+def conv_core_planes(core: torch.Tensor, planes: int, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """(r2, r1, kh, kw) core kernel -> fragment-major planes of the (r2 x kh*kw*r1p) tap-major matrix convchain.hip
-    multiplies with (r1p = r1 rounded up to 32, rows rounded up to 32)."""
+    multiplies with (r1p = r1 rounded up to 32, rows rounded up to 32).  `dtype`: as for `weight_planes`."""
     r2, r1, kh, kw = core.shape
     r1p = -(-r1 // 32) * 32
     m = torch.zeros(r2, kh * kw, r1p, dtype=torch.float32, device=core.device)
     m[:, :, :r1] = core.detach().float().permute(0, 2, 3, 1).reshape(r2, kh * kw, r1)
-    return weight_planes(m.reshape(r2, kh * kw * r1p), planes, pad_rows=32)
+    return weight_planes(m.reshape(r2, kh * kw * r1p), planes, pad_rows=32, dtype=dtype)
 
 
 def _conv_chain_bwd_plan(x_shape, dtype, r1: int, r2: int, kernel_size, stride, padding, dilation):
@@ -712,7 +730,7 @@ def conv_chain_train_pays(x: torch.Tensor, r1: int, r2: int, kernel_size, stride
         (1.13x - 1.47x; through the device library's weight gradient 1.01x - 1.34x and ahead at 18 of them) and at 3 of the
         9 on 56 x 56 inputs (0.82x - 1.20x): planes of at most 1024 pixels, dWc native."""
     plan = _conv_chain_plan(x, r1, r2, kernel_size, stride, padding, dilation)
-    if plan is None:
+    if plan is None or x.dtype == torch.float16:         # float16 is inference only: no saved intermediates, no dX
         return False
     bf16 = x.dtype == torch.bfloat16
     if not training:
@@ -722,7 +740,10 @@ def conv_chain_train_pays(x: torch.Tensor, r1: int, r2: int, kernel_size, stride
 
 def _conv_chain_desc(B, Cc, H, W, n_out, w1p, w2p, w3p, bias, dtype, kernel_size, stride, padding, dilation, bwd=False):
     d = _cabi.ConvChainDesc()
-    d.dtype = _cabi.CHAIN_F32 if dtype == torch.float32 else _cabi.CHAIN_BF16
+    d.dtype, nplanes, pdt = _chain_dtype(dtype, "conv chain")
+    for wp in (w1p, w2p, w3p):
+        if wp.dtype != pdt or wp.dim() != 5 or wp.shape[0] != nplanes or not wp.is_contiguous():
+            raise TadmmError(-1, f"conv chain: weights must be {nplanes} contiguous {pdt} plane(s) for {dtype} images")
     ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
     d.W1, d.W2, d.W3 = w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr()
     d.bias = None if bias is None else bias.data_ptr()
@@ -758,10 +779,14 @@ def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch
         bias_key = 0 if bias is None else bias.data_ptr()
     if save_ranks is not None or not memo:
         bias_key = None                                 # training: the planes are short-lived -- build, launch, forget
-    key = ("conv", tuple(x.shape), x.dtype, x.device, w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr(), bias_key, n_out,
-           tuple(kernel_size), tuple(stride), tuple(padding), tuple(dilation))
+    key = ("conv", tuple(x.shape), x.dtype, x.device, w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr(),
+           (w1p.dtype, w2p.dtype, w3p.dtype), bias_key, n_out, tuple(kernel_size), tuple(stride), tuple(padding), tuple(dilation))
     memo = _CHAIN_MEMO.lookup(key) if bias_key is not None else None
     if memo is None:
+        if x.dim() != 4:
+            raise TadmmError(-1, "conv chain: x must be an NCHW image")
+        if x.dtype == torch.float16 and save_ranks is not None:
+            raise TadmmError(-1, "conv chain: float16 is inference only; the saved intermediates feed the weight gradients")
         B, Cc, H, W = x.shape
         d, ho, wo = _conv_chain_desc(B, Cc, H, W, n_out, w1p, w2p, w3p, bias, x.dtype, kernel_size, stride, padding, dilation)
         dev = x.device

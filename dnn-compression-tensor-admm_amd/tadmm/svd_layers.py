@@ -8,10 +8,11 @@
 runs for these layers): core 0 of the plan is U (O x r), core 1 carries the singular values, diag(s) V^T (r x I).  The
 reference's CPU LAPACK SVD gives the same factors up to the sign of each singular pair.
 
-C and M run on the chain kernels, on the NCHW tensors in place, for float32 / bfloat16 inputs: bfloat16 with a rank up
-to 256 as one launch of the fused chain (`tadmm_svdconv_fwd`, the r-vector of a pixel stays in LDS), float32 and larger
-ranks as two `tadmm_tucker_1x1` launches (`ops.svd_conv_pays`, measured: DESIGN.md section 7).  Other dtypes, and
-SVDConv2dC with padding != 0, take the reference composition.
+C and M run on the chain kernels, on the NCHW tensors in place, for float32 / bfloat16 inputs and, in inference, float16
+ones (what `evaluate()` under autocast sends): the 16-bit types with a rank up to 256 as one launch of the fused chain
+(`tadmm_svdconv_fwd`, the r-vector of a pixel stays in LDS), float32 and larger ranks as two `tadmm_tucker_1x1` launches
+(`ops.svd_conv_pays`, measured: DESIGN.md section 7).  Other dtypes, float16 in grad mode, and SVDConv2dC with
+padding != 0, take the reference composition.
 
 Reference quirks kept on purpose (they are part of the contract of the state_dicts and model files):
   - SVDConv2dR checks `kernel_size != 1` / `stride != 1` on the RAW arguments, so `kernel_size=(1, 1)` raises.
@@ -100,19 +101,19 @@ class _SVDConvBase(HF.InferenceCacheMixin, nn.Module):
         r = w_in.shape[0]
         grad = torch.is_grad_enabled()
         cache = None if grad else self.__dict__.setdefault("_plane_cache", {})
-        n = 1 if x.dtype == torch.bfloat16 else 3
+        n = HF._nplanes(x)                            # (the plane cache keys on the plane dtype: planes_of)
         if ops.svd_conv_pays(x, r):
-            planes = None if grad else (HF.planes_of(w_in, n, pad_rows=64, cache=cache, tag="in"),
-                                        HF.planes_of(w_out, n, pad_cols=64, cache=cache, tag="out"))
+            planes = None if grad else (HF.planes_of(w_in, n, pad_rows=64, cache=cache, tag="in", like=x),
+                                        HF.planes_of(w_out, n, pad_cols=64, cache=cache, tag="out", like=x))
             return HF.conv1x1_chain(x, w_in, w_out, self.bias, planes)
-        p1 = None if grad else HF.planes_of(w_in, n, cache=cache, tag="in1")
+        p1 = None if grad else HF.planes_of(w_in, n, cache=cache, tag="in1", like=x)
         h = HF.pointwise(x, w_in, None, "tadmm_tucker_1x1", p1)
-        p2 = None if grad else HF.planes_of(w_out, n, cache=cache, tag="out1")
+        p2 = None if grad else HF.planes_of(w_out, n, cache=cache, tag="out1", like=x)
         return HF.pointwise(h, w_out, self.bias, "tadmm_tucker_1x1", p2)
 
-    @staticmethod
-    def _kernel_ok(x):
-        return x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
+    def _kernel_ok(self, x):
+        """float32 / bfloat16 images, and float16 ones for inference (grad mode keeps the reference composition)."""
+        return x.is_cuda and x.dim() == 4 and HF.chain_dtype_ok(x, *self.parameters(recurse=False))
 
 
 class SVDConv2dR(_SVDConvBase):

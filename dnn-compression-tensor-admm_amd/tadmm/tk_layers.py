@@ -106,15 +106,15 @@ class TKConv2dC(_TKConvBase):
         cache = None if grad else self.__dict__.setdefault("_plane_cache", {})
         w1 = self.first_kernel.reshape(self.in_rank, self.in_channels)
         w3 = self.last_kernel.reshape(self.out_channels, self.out_rank)
-        n = 1 if x.dtype == torch.bfloat16 else 3
+        n = HF._nplanes(x)
         p1 = None if grad else HF.planes_of(self.first_kernel.reshape(self.in_rank, self.in_channels), n, cache=cache,
-                                            tag="first")
+                                            tag="first", like=x)
         f1 = HF.pointwise(x, w1, None, "tadmm_tucker_1x1", p1)
         f2 = HF.core_conv_routed(self, f1)                      # the native k x k kernel where it pays (csrc/coreconv.hip)
         if f2 is None:
             core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
             f2 = F.conv2d(f1, core, None, self.stride, self.padding, self.dilation, self.groups)
-        p3 = None if grad else HF.planes_of(w3, n, cache=cache, tag="last")
+        p3 = None if grad else HF.planes_of(w3, n, cache=cache, tag="last", like=x)
         f3 = HF.pointwise(f2, w3, self.bias, "tadmm_tucker_1x1", p3)
         return f1, f2, f3
 
@@ -126,12 +126,13 @@ class TKConv2dC(_TKConvBase):
         if torch.is_grad_enabled() or self.groups != 1 or not ops.conv_chain_pays(
                 x, w1.shape[0], w3.shape[1], self.kernel_size, self.stride, self.padding, self.dilation):
             return None
-        n = 1 if x.dtype == torch.bfloat16 else 3
+        n, pdt = HF._nplanes(x), HF.plane_dtype(x)
         cache = self.__dict__.setdefault("_fused_cache", {})
-        key = (n, x.device, HF.param_key(w1, core, w3))
+        key = (x.dtype, x.device, HF.param_key(w1, core, w3))    # the dtype, not n: bf16 and f16 planes differ
         if cache.get("key") != key:
-            cache.update(key=key, planes=(ops.weight_planes(w1.detach(), n, pad_rows=32), ops.conv_core_planes(core, n),
-                                          ops.weight_planes(w3.detach(), n)))
+            cache.update(key=key, planes=(ops.weight_planes(w1.detach(), n, pad_rows=32, dtype=pdt),
+                                          ops.conv_core_planes(core, n, dtype=pdt),
+                                          ops.weight_planes(w3.detach(), n, dtype=pdt)))
         p1, p2, p3 = cache["planes"]
         return ops.conv_chain(x, p1, p2, p3, self.bias, self.out_channels, self.kernel_size, self.stride, self.padding,
                               self.dilation)
@@ -197,15 +198,15 @@ class TKConv2dM(_TKConvBase):
             return y
         grad = torch.is_grad_enabled()
         cache = None if grad else self.__dict__.setdefault("_plane_cache", {})
-        n = 1 if x.dtype == torch.bfloat16 else 3
-        p1 = None if grad else HF.planes_of(self.first_factor, n, cache=cache, tag="first")
+        n = HF._nplanes(x)
+        p1 = None if grad else HF.planes_of(self.first_factor, n, cache=cache, tag="first", like=x)
         out = HF.pointwise(x, self.first_factor, None, "tadmm_tucker_1x1", p1)
         mid = HF.core_conv_routed(self, out)
         if mid is None:
             core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
             mid = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
         out = mid
-        p3 = None if grad else HF.planes_of(self.last_factor, n, cache=cache, tag="last")
+        p3 = None if grad else HF.planes_of(self.last_factor, n, cache=cache, tag="last", like=x)
         return HF.pointwise(out, self.last_factor, self.bias, "tadmm_tucker_1x1", p3)
 
 
@@ -297,10 +298,11 @@ class TKLinearM(_TKLinearBase):
         """Three products in the reference; here the small core is contracted into the input factor and the layer is one
         launch of the fused chain (`tadmm_ttlinear_fwd`: y = last (core first) x + bias, the out_rank-vector of a token in
         LDS) whenever out_rank fits it; otherwise three strided GEMMs."""
-        align = 8 if x.dtype == torch.bfloat16 else 4
+        align = 8 if x.dtype in ops.HALF_DTYPES else 4
         params = (self.first_factor, self.core_tensor, self.last_factor)
-        # (the backward runs the fused kernel with the gradient as X: its row length out_features must be aligned too)
-        if (x.dtype in (torch.float32, torch.bfloat16) and HF.fused_rank_ok(self.out_rank) and x.is_cuda
+        # (the backward runs the fused kernel with the gradient as X: its row length out_features must be aligned too;
+        # float16 is inference only -- in grad mode it keeps the three products below)
+        if (HF.chain_dtype_ok(x, self.bias, *params) and HF.fused_rank_ok(self.out_rank) and x.is_cuda
                 and self.in_features % align == 0
                 and (self.out_features % align == 0 or not HF._needs_grad(x, self.bias, *params))):
             grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
@@ -308,14 +310,14 @@ class TKLinearM(_TKLinearBase):
                 w_in = HF.mm(self.core_tensor, self.first_factor)             # (out_rank, in_features), differentiable
                 return HF.linear_chain(x, w_in, self.last_factor, self.bias)
             if not grad:
-                n = 1 if x.dtype == torch.bfloat16 else 3
+                n = HF._nplanes(x)
                 cache = self.__dict__.setdefault("_chain_cache", {})
-                key = (n, x.device, HF.param_key(*params))
+                key = (x.dtype, x.device, HF.param_key(*params))     # the dtype, not n: bf16 and f16 planes differ
                 if cache.get("key") != key:
                     with torch.no_grad():
                         w_in = HF.mm(self.core_tensor, self.first_factor)
-                    cache.update(key=key, w_in=w_in, planes=(HF.planes_of(w_in, n, pad_rows=64),
-                                                             HF.planes_of(self.last_factor, n, pad_cols=64)))
+                    cache.update(key=key, w_in=w_in, planes=(HF.planes_of(w_in, n, pad_rows=64, like=x),
+                                                             HF.planes_of(self.last_factor, n, pad_cols=64, like=x)))
                 return HF.linear_chain(x, cache["w_in"], self.last_factor, self.bias, cache["planes"])
         out = HF.linear(x, self.first_factor)
         out = HF.linear(out, self.core_tensor)

@@ -172,21 +172,24 @@ class TTConv2dM(_TTConvBase):
     def forward(self, x):
         """TTConv.py:130-153 as three launches: `tadmm_ttconv_chain_in` on the NCHW input in place (input cores
         contracted), the k x k core convolution, `tadmm_ttconv_chain_out` + bias (output cores contracted)."""
-        if x.dtype not in (torch.float32, torch.bfloat16) or not self.in_tt_order or not self.out_tt_order:
-            return self._chains(x)[0]
         params = list(self.in_tt_cores) + list(self.out_tt_cores)
+        # float16 (what evaluate() under autocast sends) is inference only: in grad mode it keeps the per-core route
+        if (not HF.chain_dtype_ok(x, *params, self.core_kernel, self.bias) or not self.in_tt_order
+                or not self.out_tt_order):
+            return self._chains(x)[0]
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        n = 1 if x.dtype == torch.bfloat16 else 3
+        n, pdt = HF._nplanes(x), HF.plane_dtype(x)
         if grad:
             w_in, w_out = self._factors()
             p_in = p_out = None
         else:
             cache = self.__dict__.setdefault("_chain_cache", {})
-            key = (n, x.device, HF.param_key(*params, self.core_kernel))
+            # keyed on the activation dtype: one plane means bfloat16 OR float16, and their planes differ
+            key = (x.dtype, x.device, HF.param_key(*params, self.core_kernel))
             if cache.get("key") != key:
                 with torch.no_grad():
                     w_in, w_out = self._factors()
-                cache.update(key=key, w=(w_in, w_out), planes=(HF.planes_of(w_in, n), HF.planes_of(w_out, n)))
+                cache.update(key=key, w=(w_in, w_out), planes=(HF.planes_of(w_in, n, like=x), HF.planes_of(w_out, n, like=x)))
             (w_in, w_out), (p_in, p_out) = cache["w"], cache["planes"]
         # the one-launch path builds no autograd node: only when NOTHING it reads wants a gradient (frozen cores with a
         # trainable input / core kernel / bias keep the three differentiable launches below)
@@ -196,8 +199,9 @@ class TTConv2dM(_TTConvBase):
             # small planes (<= 64 pixels): the whole layer in ONE launch, both intermediates in LDS (csrc/convchain.hip)
             fkey = (key, "fused")
             if cache.get("fkey") != fkey:
-                cache.update(fkey=fkey, fplanes=(ops.weight_planes(w_in, n, pad_rows=32), ops.conv_core_planes(self.core_kernel, n),
-                                                 ops.weight_planes(w_out, n)))
+                cache.update(fkey=fkey, fplanes=(ops.weight_planes(w_in, n, pad_rows=32, dtype=pdt),
+                                                 ops.conv_core_planes(self.core_kernel, n, dtype=pdt),
+                                                 ops.weight_planes(w_out, n, dtype=pdt)))
             f1, f2, f3 = cache["fplanes"]
             return ops.conv_chain(x, f1, f2, f3, self.bias, self.out_channels, self.kernel_size, self.stride, self.padding,
                                   self.dilation)
@@ -346,8 +350,8 @@ class TTLinearM(_TTLinearBase):
 
     def _fused_ok(self, x):
         q = self.out_tt_order
-        align = 8 if x.dtype == torch.bfloat16 else 4
-        if not (x.dtype in (torch.float32, torch.bfloat16) and 0 < q < self.tt_order
+        align = 8 if x.dtype in ops.HALF_DTYPES else 4
+        if not (HF.chain_dtype_ok(x, self.bias, *self.tt_cores) and 0 < q < self.tt_order
                 and HF.fused_rank_ok(self.tt_ranks[q]) and self.in_features % align == 0):
             return False
         # the backward runs the same kernels with the gradient as X (row length out_features): a head whose width is
@@ -355,12 +359,12 @@ class TTLinearM(_TTLinearBase):
         return self.out_features % align == 0 or not HF._needs_grad(x, self.bias, *self.tt_cores)
 
     def _dense_pays(self, x, r_q: int) -> bool:
-        """bf16 inference only.  The contracted chain costs r_q (in + out) multiply-adds per token, the dense layer in * out:
+        """bf16 / float16 inference only (float16 runs bf16's kernel on bf16's rule; measured at the four DeiT-small shapes: DESIGN.md section 12).  The contracted chain costs r_q (in + out) multiply-adds per token, the dense layer in * out:
         the recovered weight is used when the chain saves nothing (ratio >= 1: DeiT-small `proj`, 384 -> 384 through rank
         256 -- 12.5 us against 10.5 for the dense product under graph replay) or saves little over a long reduction
         (ratio >= 0.8 and in_features >= 1024: `fc2`).  `qkv` / `fc1` (ratio 0.89 / 0.83, K = 384) keep the chain kernel:
         1.4 - 1.65x the dense product."""
-        if x.dtype != torch.bfloat16:
+        if x.dtype not in ops.HALF_DTYPES:
             return False
         chain, dense = r_q * (self.in_features + self.out_features), self.in_features * self.out_features
         return chain >= dense or (self.in_features >= 1024 and chain >= 0.8 * dense)
@@ -383,14 +387,14 @@ class TTLinearM(_TTLinearBase):
                 w_in, w_out = self._factors()
                 return HF.linear_chain(x, w_in, w_out, self.bias)
             if not grad:
-                n = 1 if x.dtype == torch.bfloat16 else 3
+                n = HF._nplanes(x)
                 cache = self.__dict__.setdefault("_chain_cache", {})
-                key = (n, x.device, HF.param_key(*self.tt_cores))
+                key = (x.dtype, x.device, HF.param_key(*self.tt_cores))      # the dtype, not n: bf16 and f16 planes differ
                 if cache.get("key") != key:
                     with torch.no_grad():
                         w_in, w_out = self._factors()
-                    cache.update(key=key, w=(w_in, w_out), planes=(HF.planes_of(w_in, n, pad_rows=64),
-                                                                   HF.planes_of(w_out, n, pad_cols=64)), dense=None)
+                    cache.update(key=key, w=(w_in, w_out), planes=(HF.planes_of(w_in, n, pad_rows=64, like=x),
+                                                                   HF.planes_of(w_out, n, pad_cols=64, like=x)), dense=None)
                 w_in, w_out = cache["w"]
                 if self._dense_pays(x, w_in.shape[0]) and not HF._needs_grad(x, self.bias):
                     # long-K bf16 layers whose chain saves (almost) no arithmetic (DeiT-small fc2: 983 k of 1 180 k flop per

@@ -260,16 +260,21 @@ int tadmm_gemm_bf16_nt(tadmm_handle h, const void* A, const void* Bt, void* C, i
  * dtype TADMM_CHAIN_F32: X, Y float32; weights as THREE bf16 planes (w = w1 + w2 + w3 exactly, plane p at
  *   W + p * plane_stride); six bf16 products per fp32 product, fp32 accumulate: fp32-GEMM accuracy.
  * dtype TADMM_CHAIN_BF16: X, Y bfloat16; one weight plane.
+ * dtype TADMM_CHAIN_F16 (inference): X, Y IEEE binary16; the weights are ONE plane of binary16 in the same
+ *   fragment-major order as a bf16 plane; fp32 accumulate, float32 bias; results round to nearest even and overflow to
+ *   +-inf.  Every alignment, padding and size rule is TADMM_CHAIN_BF16's.  The library cannot tell a binary16 plane
+ *   from a bfloat16 one: the caller pairs planes and dtype.  All seven entries below take all three dtypes (the _bwd
+ *   entries are the forward kernels on transposed planes).
  * Layouts: x_hw / y_hw == 0: token rows of ldx / ldy elements.  x_hw / y_hw > 0: channels-first images
  *   (batch, channel, pixel) of that many pixels -- the NCHW tensors of TTConv.py:131 / TKConv.py:94 in place.
  * Weights are FRAGMENT-MAJOR (one MFMA operand = one contiguous KiB): element (row n, col k) of plane p of an
  *   N x K weight lives at W[p*plane + (((n/16)*KS + k/32)*64 + (k%32/8)*16 + n%16)*8 + k%8], KS = ceil(K/32), rows
  *   padded to 16 and columns to 32 with zeros (tadmm.ops.weight_planes builds it).  Token rows: Kin % 8 == 0
  *   (% 4 for float32) and 16-byte aligned rows.  bias: float32[N], 16-byte aligned, or NULL.  tile_tokens: 0 (default), 32 or 64. */
-enum { TADMM_CHAIN_F32 = 0, TADMM_CHAIN_BF16 = 1 };
+enum { TADMM_CHAIN_F32 = 0, TADMM_CHAIN_BF16 = 1, TADMM_CHAIN_F16 = 2 };
 typedef struct {
   const void* X; void* Y;
-  const void* Win; const void* Wout;          /* bf16 planes */
+  const void* Win; const void* Wout;          /* bf16 planes (binary16 for TADMM_CHAIN_F16) */
   const float* bias;
   int64_t T;                                   /* tokens (rows, or batch * pixels) */
   int32_t Kin, R, Nout;
@@ -279,31 +284,35 @@ typedef struct {
 } tadmm_chain_desc;
 /* sizeof(tadmm_chain_desc) as the library was built (bindings check their struct layout against it) */
 int tadmm_chain_desc_bytes(void);
-/* TTLinearM forward (TTLinear.py:75-93), fused. */
+/* TTLinearM forward (TTLinear.py:75-93), fused.  dtype: F32 | BF16 | F16. */
 int tadmm_ttlinear_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 /* TTLinearM data gradient dX = (dY Wout) Win: the same fused kernel with X = dY, Win = Wout^T planes (R x Nout),
- * Wout = Win^T planes (Kin x R); weight gradients are plain products (tadmm_gemm). */
+ * Wout = Win^T planes (Kin x R); weight gradients are plain products (tadmm_gemm).  dtype: F32 | BF16 | F16. */
 int tadmm_ttlinear_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
-/* TTConv2dM input-core chain (TTConv.py:131-137): image (B, C, H, W) -> (B, r, H, W), single product. */
+/* TTConv2dM input-core chain (TTConv.py:131-137): image (B, C, H, W) -> (B, r, H, W), single product.
+ * dtype: F32 | BF16 | F16. */
 int tadmm_ttconv_chain_in(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
-/* TTConv2dM output-core chain + bias (TTConv.py:141-151): (B, r, H', W') -> (B, O, H', W'), single product. */
+/* TTConv2dM output-core chain + bias (TTConv.py:141-151): (B, r, H', W') -> (B, O, H', W'), single product.
+ * dtype: F32 | BF16 | F16. */
 int tadmm_ttconv_chain_out(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
-/* TKConv2dC first / last 1x1 stage (TKConv.py:93-98): per-pixel channel mixing, single product. */
+/* TKConv2dC first / last 1x1 stage (TKConv.py:93-98): per-pixel channel mixing, single product.
+ * dtype: F32 | BF16 | F16. */
 int tadmm_tucker_1x1(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 /* SVDConv2dC / SVDConv2dM forward (SVDConv.py: two 1x1 convolutions / two per-pixel linears, padding 0):
  * y[b,:,p] = Wout (Win x[b,:,p]) + bias on NCHW images in place, one launch, the R-vector of a pixel in LDS.
  * x_hw = y_hw = H*W, T = B*H*W, Kin = C_in, Nout = C_out; Win (R x C_in) / Wout (C_out x R) planes with the rank padded
- * to R (multiple of 64, <= 256) as for tadmm_ttlinear_fwd.  Ranks above 256 are not served (two tadmm_tucker_1x1). */
+ * to R (multiple of 64, <= 256) as for tadmm_ttlinear_fwd.  Ranks above 256 are not served (two tadmm_tucker_1x1).
+ * dtype: F32 | BF16 | F16. */
 int tadmm_svdconv_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 /* Its data gradient dX = Win^T (Wout^T dY): the same kernel with X = dY, Win = Wout^T planes (R x C_out),
- * Wout = Win^T planes (C_in x R), bias NULL. */
+ * Wout = Win^T planes (C_in x R), bias NULL.  dtype: F32 | BF16 | F16. */
 int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 
 /* ---- weight gradients of the factorised layers (csrc/wgrad.hip) ---------------------------------------------------
  * C[m][n] = alpha * sum_{t < T} A[t][m] * B[t][n], float32 C with row stride ldc: dW = dY^T X and its kin, a small
  * output (a rank times a channel count) over a long reduction (tokens or batch * pixels).  A and B are read in place,
  * both of `dtype` (TADMM_CHAIN_F32: exact three-plane bf16 split, six products per product, fp32-GEMM accuracy;
- * TADMM_CHAIN_BF16: one plane, products exact), both in one layout:
+ * TADMM_CHAIN_BF16: one plane, products exact; TADMM_CHAIN_F16 is refused with TADMM_ERR_INVALID), both in one layout:
  *   hw == 0: token rows, A (T, M) with row stride lda >= M, B (T, N) with row stride ldb >= N (elements);
  *   hw  > 0: channels-first images, A contiguous (T / hw, M, hw), B contiguous (T / hw, N, hw); lda / ldb ignored.
  * Any alignment the element type allows: 16-byte loads where base and stride (lda / ldb, or hw) permit, 8-byte or
@@ -337,7 +346,11 @@ int tadmm_wgrad(tadmm_handle h, const tadmm_wgrad_desc* d, void* workspace, size
  * (TTConv.py:130-153), TKConv2dC / TKConv2dM (TKConv.py:93-98, :210-214).  W1 (R1 x C), W2 (R2 x kh*kw*R1, tap-major:
  * column (dy*kw + dx)*R1 + c) and W3 (Nout x R2) are fragment-major bf16 planes as for tadmm_chain_desc, R1 and R2
  * multiples of 32 (zero padded), both <= 256; groups = 1.  Returns TADMM_ERR_UNSUPPORTED when the image or the
- * intermediates do not fit (the caller then uses tadmm_ttconv_chain_in / conv2d / tadmm_ttconv_chain_out). */
+ * intermediates do not fit (the caller then uses tadmm_ttconv_chain_in / conv2d / tadmm_ttconv_chain_out).
+ * dtype: tadmm_ttconv_fused and tadmm_ttconv_fused_plan take F32 | BF16 | F16 (F16: one binary16 plane per weight, the
+ * BF16 kernel with the f16 MFMA and conversions; its plan equals the BF16 plan field for field).  tadmm_ttconv_fused_save
+ * and tadmm_ttconv_fused_bwd take F32 | BF16 and refuse F16 with TADMM_ERR_INVALID: what they store feeds the weight
+ * gradients, which have no binary16 form. */
 typedef struct {
   const void* X; void* Y;
   const void* W1; const void* W2; const void* W3;
@@ -345,7 +358,7 @@ typedef struct {
   int64_t w1_plane, w2_plane, w3_plane;
   int32_t B, C, R1, R2, Nout;
   int32_t H, W, Ho, Wo, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
-  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 */
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (see above) */
 } tadmm_conv_chain_desc;
 int tadmm_conv_chain_desc_bytes(void);
 int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* d, void* stream);
@@ -382,7 +395,7 @@ int tadmm_ttconv_fused_plan(const tadmm_conv_chain_desc* d, int mode, int* tile_
  *   dgrad  X (B, R1, H, W)   = the data gradient for Y = dY                      reads Y, Wc planes; writes X
  *   wgrad  dW (R2, R1, kh, kw) float32, contiguous = the weight gradient         reads X and Y = dY; Wc is ignored
  * X and Y are both of `dtype` (TADMM_CHAIN_F32: exact three-plane bf16 split, fp32-GEMM accuracy; TADMM_CHAIN_BF16: one
- * plane), element aligned: 16-byte, 8-byte or element accesses as base and run length allow.
+ * plane; TADMM_CHAIN_F16 is refused with TADMM_ERR_INVALID by all three), element aligned: 16-byte, 8-byte or element accesses as base and run length allow.
  * Wc: fragment-major bf16 planes (3 for float32, 1 for bfloat16; plane p at Wc + p * wc_plane elements, 16-byte aligned)
  * of the tap-major matrix, as for W2 of tadmm_conv_chain_desc: fwd takes the (R2 x kh*kw*R1p) matrix with column
  * (ky*kw + kx)*R1p + c, R1p = R1 rounded up to 32 and rows rounded up to 32; dgrad takes the same packing of the
