@@ -156,6 +156,9 @@ static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, con
     CTX_FAIL(h, TADMM_ERR_INVALID, "chain: X rows must be 16-byte aligned with Kin a whole number of 16-byte vectors");
   if (c->y_hw == 0 && c->ldy < (fused ? c->Nout : c->R)) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: ldy too small");
   if (c->x_hw < 0 || c->y_hw < 0) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: negative image size");
+  // the vector image epilogue masks a 16-byte unit by its first pixel: a partial last plane would be overrun
+  if ((c->x_hw > 0 && c->T % c->x_hw) || (c->y_hw > 0 && c->T % c->y_hw))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "chain: T must be a whole number of image planes (T % x_hw == 0 and T % y_hw == 0)");
   if (((uintptr_t)c->bias) & 15) CTX_FAIL(h, TADMM_ERR_INVALID, "chain: bias must be 16-byte aligned");
   if (fused) {
     if (c->R % 64 || c->R > 256) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "chain: fused middle rank must be a multiple of 64, at most 256");

@@ -266,7 +266,9 @@ int tadmm_gemm_bf16_nt(tadmm_handle h, const void* A, const void* Bt, void* C, i
  *   from a bfloat16 one: the caller pairs planes and dtype.  All seven entries below take all three dtypes (the _bwd
  *   entries are the forward kernels on transposed planes).
  * Layouts: x_hw / y_hw == 0: token rows of ldx / ldy elements.  x_hw / y_hw > 0: channels-first images
- *   (batch, channel, pixel) of that many pixels -- the NCHW tensors of TTConv.py:131 / TKConv.py:94 in place.
+ *   (batch, channel, pixel) of that many pixels -- the NCHW tensors of TTConv.py:131 / TKConv.py:94 in place.  With an
+ *   image on either side T must be a whole number of its planes (T % x_hw == 0, T % y_hw == 0): every entry returns
+ *   TADMM_ERR_INVALID otherwise and launches nothing.
  * Weights are FRAGMENT-MAJOR (one MFMA operand = one contiguous KiB): element (row n, col k) of plane p of an
  *   N x K weight lives at W[p*plane + (((n/16)*KS + k/32)*64 + (k%32/8)*16 + n%16)*8 + k%8], KS = ceil(K/32), rows
  *   padded to 16 and columns to 32 with zeros (tadmm.ops.weight_planes builds it).  Token rows: Kin % 8 == 0

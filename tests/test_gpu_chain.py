@@ -3,7 +3,11 @@ TTConv2dM / TKConv2dC chains, fp32 (three-plane bf16 split) and bf16, against fp
 
 Tolerances: the fp32 mode must be as accurate as an fp32 GEMM -- error <= 2e-6 of the largest |output| at K <= 1536
 (measured ~3e-7; an fp32 `torch.mm` on the CPU gives ~6e-7 on the same data); the bf16 mode is bounded by the bf16
-rounding of inputs, the intermediate and the output (2^-8 each): 2e-2 of the largest |output|."""
+rounding of inputs, the intermediate and the output (2^-8 each): 2e-2 of the largest |output|.
+
+These are the layer-sized cases at the default token tile, judged norm-wise.  The instantiation matrix -- every dtype x
+token tile x padded rank x layout of chain.hip, judged elementwise against derived bounds, with strided and guarded
+operands -- is tests/test_gpu_chain_variants.py."""
 import pytest
 import torch
 
