@@ -133,10 +133,20 @@ int tadmm_gemm_bf16_nt(tadmm_handle h, const void* A, const void* Bt, void* C, i
 }
 
 // ---- forward chains of the factorised layers (chain.hip) ----
+// `save`: the _save entries, which also store the true-rank columns [0, rt) of the middle-rank vector to h_out
 static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, const char* who, void* stream_,
-                       bool svdconv = false) {
+                       bool svdconv = false, bool save = false, int rt = 0, void* h_out = nullptr, int64_t ldh = 0) {
   DeviceGuard device_guard(h);
   if (!h || !c) return TADMM_ERR_INVALID;
+  if (save) {
+    if (c->dtype != TADMM_CHAIN_F32 && c->dtype != TADMM_CHAIN_BF16)
+      CTX_FAIL(h, TADMM_ERR_INVALID, "chain save: float32 or bfloat16 only (binary16 is inference only: the weight gradients have no binary16 form)");
+    if (!h_out) CTX_FAIL(h, TADMM_ERR_INVALID, "chain save: null h_out");
+    if (rt <= 0 || rt > c->R) CTX_FAIL(h, TADMM_ERR_INVALID, "chain save: true rank %d outside (0, %d]", rt, c->R);
+    if (ldh < rt) CTX_FAIL(h, TADMM_ERR_INVALID, "chain save: ldh %lld below the true rank %d", (long long)ldh, rt);
+    if (((uintptr_t)h_out) % (c->dtype == TADMM_CHAIN_F32 ? 4 : 2))
+      CTX_FAIL(h, TADMM_ERR_INVALID, "chain save: h_out must be aligned to its element");
+  }
   if (svdconv) {   // 1x1 SVD convolution: NCHW in, NCHW out, one plane size, T = batch * plane
     if (c->x_hw <= 0 || c->y_hw != c->x_hw)
       CTX_FAIL(h, TADMM_ERR_INVALID, "svdconv: x_hw and y_hw must both equal the pixels of one image plane (H*W > 0)");
@@ -178,6 +188,10 @@ static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, con
   const int nfeat = fused ? c->Nout : c->R;
   if (c->y_hw > 0) d.y_vec = (c->y_hw % epl == 0 && (((uintptr_t)c->Y) & 15) == 0) ? 1 : 0;
   else d.y_vec = (c->ldy % epl == 0 && nfeat % epl == 0 && (((uintptr_t)c->Y) & 15) == 0) ? 1 : 0;
+  if (save) {   // 16-byte stores where every unit is aligned and, on images, lies within one plane
+    d.H = h_out; d.ldh = ldh; d.rt = rt;
+    d.h_vec = ((svdconv ? c->x_hw % epl : ldh % epl) == 0 && (((uintptr_t)h_out) & 15) == 0) ? 1 : 0;
+  }
   const int rc = svdconv ? launch_svdconv_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_)
                          : launch_tt_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_);
   if (rc != 0) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "chain: token tile does not fit the LDS");
@@ -192,6 +206,18 @@ int tadmm_ttconv_chain_out(tadmm_handle h, const tadmm_chain_desc* d, void* s) {
 int tadmm_tucker_1x1(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 0, "tucker_1x1", s); }
 int tadmm_svdconv_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 1, "svdconv_fwd", s, true); }
 int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* s) { return chain_entry(h, d, 1, "svdconv_bwd", s, true); }
+int tadmm_ttlinear_fwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* h_out, int64_t ldh, void* s) {
+  return chain_entry(h, d, 1, "ttlinear_fwd_save", s, false, true, r, h_out, ldh);
+}
+int tadmm_ttlinear_bwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* dh_out, int64_t ldh, void* s) {
+  return chain_entry(h, d, 1, "ttlinear_bwd_save", s, false, true, r, dh_out, ldh);
+}
+int tadmm_svdconv_fwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* h_out, int64_t ldh, void* s) {
+  return chain_entry(h, d, 1, "svdconv_fwd_save", s, true, true, r, h_out, ldh);
+}
+int tadmm_svdconv_bwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* dh_out, int64_t ldh, void* s) {
+  return chain_entry(h, d, 1, "svdconv_bwd_save", s, true, true, r, dh_out, ldh);
+}
 
 int tadmm_conv_chain_desc_bytes(void) { return (int)sizeof(tadmm_conv_chain_desc); }
 

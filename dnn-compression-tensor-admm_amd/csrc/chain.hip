@@ -34,8 +34,10 @@
 namespace tadmm {
 namespace {
 
-template <int P, int TM, int KC, int NB2, int KS2T, typename TIn, typename TOut, bool FUSED, bool XIMG, bool YIMG>
+template <int P, int TM, int KC, int NB2, int KS2T, typename TIn, typename TOut, bool FUSED, bool XIMG, bool YIMG,
+          bool SAVE = false>
 __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
+  static_assert(!SAVE || (FUSED && !kIsF16<TIn>), "the saving launches are fused, float32 or bfloat16");
   extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
   constexpr int MT = TM / 16, LDX = KC + kPad, SPC = KC / 32;  // k-steps per chunk
   constexpr int XS_BYTES = 2 * P * TM * LDX * 2;               // both chunk buffers; reused as store staging
@@ -138,6 +140,9 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
         for (int p = 0; p < P; ++p)
           *reinterpret_cast<uint2*>(&Hs[(p * TM + 16 * mt + r) * ldh + f0]) = make_uint2(s0[p], s1[p]);
       }
+    // training: the same values also go to global memory (the weight gradients read them), through this wave's
+    // staging area -- the chunk buffers, which nobody reads any more
+    if constexpr (SAVE) save_group<TM, kNB1, TIn, XIMG, XS_BYTES / 4>(d, acc, m0, wave * kNB1 * 16, stage, lane);
     __syncthreads();
     STAMP();
 
@@ -206,9 +211,10 @@ __global__ __launch_bounds__(256) void tt_chain_kernel(const ChainDesc d) {
   }
 }
 
-template <int P, int TM, int KC, int NB2, int KS2T, typename TIn, typename TOut, bool FUSED, bool XIMG, bool YIMG>
+template <int P, int TM, int KC, int NB2, int KS2T, typename TIn, typename TOut, bool FUSED, bool XIMG, bool YIMG,
+          bool SAVE = false>
 int launch_variant(const ChainDesc& d, hipStream_t s) {
-  auto kern = tt_chain_kernel<P, TM, KC, NB2, KS2T, TIn, TOut, FUSED, XIMG, YIMG>;
+  auto kern = tt_chain_kernel<P, TM, KC, NB2, KS2T, TIn, TOut, FUSED, XIMG, YIMG, SAVE>;
   size_t lds = (size_t)2 * P * TM * (KC + kPad) * 2;
   if (FUSED) lds += (size_t)P * TM * (d.R + kPad) * 2;
   if (lds > 160 * 1024) return -1;
@@ -291,6 +297,28 @@ int launch_fused_img(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t
   return launch_variant<3, 64, 64, 3, KS2T, float, float, true, true, true>(d, s);
 }
 
+// The saving launches (d.H set): the fused variants above with the SAVE flag, on token rows or on images.  float32 and
+// bfloat16 only: what they store feeds the weight gradients, which have no binary16 form.
+template <int KS2T, bool IMG>
+int launch_fused_save(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
+  if (dtype == 1) {
+    if (tile_tokens == 64) return launch_variant<1, 64, 128, 6, KS2T, uint16_t, uint16_t, true, IMG, IMG, true>(d, s);
+    return launch_variant<1, 32, 128, 6, KS2T, uint16_t, uint16_t, true, IMG, IMG, true>(d, s);
+  }
+  if (dtype != 0) return -1;
+  if (tile_tokens == 32) return launch_variant<3, 32, 128, 6, KS2T, float, float, true, IMG, IMG, true>(d, s);
+  return launch_variant<3, 64, 64, 3, KS2T, float, float, true, IMG, IMG, true>(d, s);
+}
+template <bool IMG>
+int launch_fused_save_ks(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
+  switch (d.R / 32) {
+    case 2: return launch_fused_save<2, IMG>(d, dtype, tile_tokens, s);
+    case 4: return launch_fused_save<4, IMG>(d, dtype, tile_tokens, s);
+    case 6: return launch_fused_save<6, IMG>(d, dtype, tile_tokens, s);
+    default: return launch_fused_save<8, IMG>(d, dtype, tile_tokens, s);
+  }
+}
+
 }  // namespace
 
 // Fused chain with image input and image output of the same plane size (tadmm_svdconv_fwd / _bwd).  -1 when the shape
@@ -298,6 +326,7 @@ int launch_fused_img(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t
 int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
   if (d.T <= 0) return 0;
   if (!d.fused || d.x_hw <= 0 || d.y_hw != d.x_hw || d.R % 64 || d.R > 256) return -1;
+  if (d.H) return launch_fused_save_ks<true>(d, dtype, tile_tokens, s);
   switch (d.R / 32) {
     case 2: return launch_fused_img<2>(d, dtype, tile_tokens, s);
     case 4: return launch_fused_img<4>(d, dtype, tile_tokens, s);
@@ -317,6 +346,7 @@ int launch_tt_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t 
     return launch_single<3, 64, 64, float>(d, s);
   }
   if (d.x_hw > 0 || d.y_hw > 0 || d.R % 64 || d.R > 256) return -1;
+  if (d.H) return launch_fused_save_ks<false>(d, dtype, tile_tokens, s);
   return launch_fused_ks(d, dtype, tile_tokens, s);
 }
 

@@ -352,6 +352,102 @@ __device__ __forceinline__ void store_group(const ChainDesc& d, float4v_t (&acc)
   }
 }
 
+// The middle-rank tile of one wave (NB feature tiles x TM tokens of product 1) -> d.H, for the weight gradients of a
+// training step.  What is stored is what product 2 reads from LDS: the bf16 rounding of the accumulator, or (float32)
+// the accumulator itself, whose three planes are an exact split.  Only features below d.rt, the true rank, and tokens
+// below d.T are written.  The tile always goes through the wave-private staging area, so that one instruction writes
+// contiguous rows: whole 16-byte units with d.h_vec (a partial last unit of a token row falls back to elements), single
+// elements otherwise.  IMG: (T / hw, ldh, hw) images of which channels [0, rt) are written (ldh == rt: a contiguous NCHW
+// tensor); a 16-byte unit never straddles a plane because d.h_vec implies hw % (16 / sizeof(T)) == 0, and T is a whole
+// number of planes.
+template <int TM, int NB, typename T, bool IMG, int STAGE_BYTES>
+__device__ __forceinline__ void save_group(const ChainDesc& d, const float4v_t (&acc)[TM / 16][NB], int64_t m0, int f_base,
+                                           uint8_t* stage, int lane) {
+  constexpr int MT = TM / 16, SZ = sizeof(T), EPU = 16 / SZ;
+  const int r = lane & 15, q = lane >> 4;
+  const int N = d.rt;
+  if (f_base >= N) return;                                          // wave-uniform: this wave holds padding only
+  T* Hg = static_cast<T*>(d.H);
+  const bool vec = d.h_vec != 0;
+  if constexpr (!IMG) {
+    constexpr int ROWB = NB * 16 * SZ, SLD = ROWB + 16;            // staged token row, padded
+    constexpr int TS0 = (STAGE_BYTES / SLD) / 16 * 16;
+    constexpr int TS = TS0 > TM ? TM : TS0;                         // tokens per staging pass
+    static_assert(TS >= 16, "staging area too small");
+    constexpr int UPR = ROWB / 16, TPI = 64 / UPR;                  // 16-byte units per row, token rows per instruction
+    const int tl = lane / UPR, u = lane - tl * UPR;
+#pragma unroll
+    for (int t0 = 0; t0 < TM; t0 += TS) {
+#pragma unroll
+      for (int mt = t0 / 16; mt < (t0 + TS) / 16 && mt < MT; ++mt)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          uint8_t* p = stage + (16 * mt - t0 + r) * SLD + (16 * j + 4 * q) * SZ;
+          if constexpr (SZ == 4) *reinterpret_cast<float4*>(p) = make_float4(acc[mt][j][0], acc[mt][j][1], acc[mt][j][2], acc[mt][j][3]);
+          else *reinterpret_cast<uint2*>(p) = make_uint2(pack16<false>(acc[mt][j][0], acc[mt][j][1]), pack16<false>(acc[mt][j][2], acc[mt][j][3]));
+        }
+#pragma unroll
+      for (int tt = 0; tt < TS && t0 + tt < TM; tt += TPI) {
+        const int tok = tt + tl;
+        const int64_t t = m0 + t0 + tok;
+        const int f = f_base + u * EPU;
+        if (tl < TPI && tok < TS && t0 + tok < TM && t < d.T && f < N) {
+          const uint8_t* s = stage + tok * SLD + u * 16;
+          T* g = Hg + t * d.ldh + f;
+          if (vec && f + EPU <= N) *reinterpret_cast<uint4*>(g) = *reinterpret_cast<const uint4*>(s);
+          else {
+#pragma unroll
+            for (int e = 0; e < EPU; ++e)
+              if (f + e < N) g[e] = reinterpret_cast<const T*>(s)[e];
+          }
+        }
+      }
+    }
+  } else {
+    // image layout: staged as [feature][TM pixels]; one instruction writes 64 / (TM*SZ/16) feature rows of TM pixels
+    constexpr int ROWB = TM * SZ, SLD = ROWB + 16;
+    constexpr int FS0 = (STAGE_BYTES / SLD) / 16 * 16;
+    constexpr int FS = FS0 > NB * 16 ? NB * 16 : FS0;               // features per staging pass (whole tiles)
+    static_assert(FS >= 16, "staging area too small");
+    constexpr int UPR = ROWB / 16, FPI = 64 / UPR;
+    const int fl = lane / UPR, u = lane - fl * UPR;
+    const int hw = d.x_hw, nch = (int)d.ldh;
+#pragma unroll
+    for (int j0 = 0; j0 < NB; j0 += FS / 16) {
+#pragma unroll
+      for (int j = j0; j < j0 + FS / 16 && j < NB; ++j)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            uint8_t* p = stage + (16 * (j - j0) + 4 * q + e) * SLD + (16 * mt + r) * SZ;
+            if constexpr (SZ == 4) *reinterpret_cast<float*>(p) = acc[mt][j][e];
+            else *reinterpret_cast<uint16_t*>(p) = rne16<false>(acc[mt][j][e]);
+          }
+#pragma unroll
+      for (int ff = 0; ff < FS && 16 * j0 + ff < NB * 16; ff += FPI) {
+        const int fi = ff + fl;
+        const int f = f_base + 16 * j0 + fi;
+        const int64_t t = m0 + u * EPU;
+        if (fl < FPI && fi < FS && 16 * j0 + fi < NB * 16 && f < N && t < d.T) {
+          const uint8_t* s = stage + fi * SLD + u * 16;
+          if (vec) *reinterpret_cast<uint4*>(Hg + elem_off(t, f, 0, hw, nch)) = *reinterpret_cast<const uint4*>(s);
+          else {
+            int64_t b = t / hw;                                     // one division per unit: the pixels are walked
+            int pix = (int)(t - b * hw);
+#pragma unroll
+            for (int e = 0; e < EPU; ++e)
+              if (t + e < d.T) {
+                Hg[(b * nch + f) * hw + pix] = reinterpret_cast<const T*>(s)[e];
+                if (++pix == hw) { pix = 0; ++b; }
+              }
+          }
+        }
+      }
+    }
+  }
+}
+
 // ---- three-plane mode: token fragments stream through a two-slot ring, one 16-token tile (3 planes) at a time, so
 // that only 24 registers of token fragments are live instead of 12 per tile of the workgroup's token block
 template <int TM>

@@ -177,6 +177,11 @@ struct ChainDesc {
   int64_t ldx, ldy, win_plane, wout_plane;
   int32_t x_hw, y_hw, x_vec, y_vec, fused;
   long long* stamps;                            // debugging: per-workgroup cycle stamps (nullable)
+  // saving launches (fused only): H receives product 1, the true-rank columns [0, rt) of the middle-rank vector, of
+  // X's dtype -- token rows of ldh elements, or (T / x_hw, rt, x_hw) images; h_vec: 16-byte stores allowed
+  void* H;
+  int64_t ldh;
+  int32_t rt, h_vec;
 };
 int launch_tt_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s);
 int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s);   // fused, image in / out

@@ -176,6 +176,10 @@ ABI = {
     "tadmm_tucker_1x1": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_svdconv_fwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
     "tadmm_svdconv_bwd": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_void_p]),
+    "tadmm_ttlinear_fwd_save": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "tadmm_ttlinear_bwd_save": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "tadmm_svdconv_fwd_save": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "tadmm_svdconv_bwd_save": (C.c_int, [C.c_void_p, C.POINTER(ChainDesc), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "tadmm_wgrad_desc_bytes": (C.c_int, []),
     "tadmm_wgrad_workspace_bytes": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "tadmm_wgrad": (C.c_int, [C.c_void_p, C.POINTER(WgradDesc), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -222,11 +222,23 @@ def pointwise(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor = None, entry
     return _ChainSingle.apply(x.reshape(-1, x.shape[-1]), w, bias, entry, planes).reshape(*lead, w.shape[0])
 
 
+def _saved_route(ctx, x, w_in, w_out, save, image: bool) -> bool:
+    """True when this step of a fused chain stores its middle-rank intermediates (`save`: None = `ops.chain_train_pays`
+    decides, True / False = the caller does).  With no factor gradient wanted there is nothing to save either way."""
+    factor_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+    if not factor_grad or save is False:
+        return False
+    return True if save else ops.chain_train_pays(x, w_in.shape[0], w_in.shape[1], w_out.shape[0], image)
+
+
 class _ChainFused(torch.autograd.Function):
-    """y = (x Win^T) Wout^T + bias in one launch; Win (R, K), Wout (N, R), R <= 256."""
+    """y = (x Win^T) Wout^T + bias in one launch; Win (R, K), Wout (N, R), R <= 256.  On the saved route
+    (`_saved_route`) the forward launch also stores H = x Win^T and the data-gradient launch dH = dY Wout, and the two
+    weight gradients read them: four launches a step and no recomputation, for T x R elements (H) kept alive from
+    forward to backward that the other route does not keep."""
 
     @staticmethod
-    def forward(ctx, x, w_in, w_out, bias, planes):
+    def forward(ctx, x, w_in, w_out, bias, planes, save):
         if not x.is_cuda:
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
         _inference_only(x)
@@ -234,17 +246,42 @@ class _ChainFused(torch.autograd.Function):
         fresh = planes is None
         if fresh:
             planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
-        y = ops.chain_fused(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
-        ctx.save_for_backward(x, w_in, w_out)
+        ctx.saved_route = _saved_route(ctx, x, w_in, w_out, save, False)
+        h = None
+        if ctx.saved_route and ctx.needs_input_grad[2]:              # H feeds dWout alone
+            y, h = ops.chain_fused_save(x, planes[0], planes[1], bias, w_out.shape[0], w_in.shape[0])
+        else:
+            y = ops.chain_fused(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
+        ctx.save_for_backward(x, w_in, w_out, h)
         ctx.has_bias = bias is not None
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, w_in, w_out = ctx.saved_tensors
+        x, w_in, w_out, h = ctx.saved_tensors
         g = g.contiguous()
         n = _nplanes(g)
         gx = gwi = gwo = gb = None
+        if ctx.saved_route:
+            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:  # dX and dH = dY Wout from one launch
+                gx, gr = ops.chain_fused_save(g, planes_of(w_out, n, pad_rows=64, transpose=True),
+                                              planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
+                                              w_in.shape[0], entry="tadmm_ttlinear_bwd_save")
+                gwi = ops.wgrad(gr, x)
+                del gr
+            elif ctx.needs_input_grad[0]:
+                gx = ops.chain_fused(g, planes_of(w_out, n, pad_rows=64, transpose=True),
+                                     planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
+                                     entry="tadmm_ttlinear_bwd", memo=False)
+            elif ctx.needs_input_grad[1]:           # no dX wanted: product 1 alone
+                gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], memo=False)
+                gwi = ops.wgrad(gr, x)
+                del gr
+            if ctx.needs_input_grad[2]:             # dWout = dY^T H, H from the forward launch
+                gwo = ops.wgrad(g, h)
+            if ctx.has_bias and ctx.needs_input_grad[3]:
+                gb = g.sum(0)
+            return gx, gwi, gwo, gb, None, None
         if ctx.needs_input_grad[0]:                 # dX = (dY Wout) Win: the fused kernel on the transposed factors
             gx = ops.chain_fused(g, planes_of(w_out, n, pad_rows=64, transpose=True),
                                  planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
@@ -258,13 +295,20 @@ class _ChainFused(torch.autograd.Function):
             gwo = ops.wgrad(g, h)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(0)
-        return gx, gwi, gwo, gb, None
+        return gx, gwi, gwo, gb, None, None
 
 
-def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None, planes=None):
+def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None, planes=None,
+                 save=None):
     """(..., K) -> (..., N): x Win^T Wout^T + bias through the fused chain kernel (TTLinear.py:75-93 with the input
     cores contracted into Win and the output cores into Wout).  Differentiable.  `planes`: prebuilt
-    (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))."""
+    (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64)).
+    `save` picks the route of a training step in which a factor wants a gradient.  True: the forward launch stores
+    H = x Win^T (`tadmm_ttlinear_fwd_save`), the data-gradient launch stores dH = dY Wout (`tadmm_ttlinear_bwd_save`), and
+    the weight gradients are `ops.wgrad(dH, x)` and `ops.wgrad(dY, H)`: four launches, nothing recomputed, at the price of
+    T x R elements of x's dtype (H, rows padded to 16 bytes) alive from forward to backward.  False: both intermediates
+    are recomputed in the backward by two `ops.chain_single` launches and nothing extra is kept.  None:
+    `ops.chain_train_pays` decides.  dX is bit-identical on both routes."""
     lead = x.shape[:-1]
     if not _needs_grad(x, w_in, w_out, bias):         # inference: straight to the C ABI, no autograd node
         fresh = planes is None
@@ -273,14 +317,15 @@ def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias:
             planes = (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x))
         return ops.chain_fused(x.reshape(-1, x.shape[-1]), planes[0], planes[1], bias, w_out.shape[0],
                                memo=not fresh).reshape(*lead, w_out.shape[0])
-    return _ChainFused.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes).reshape(*lead, w_out.shape[0])
+    return _ChainFused.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes, save).reshape(*lead, w_out.shape[0])
 
 
 class _Conv1x1Chain(torch.autograd.Function):
-    """y[b,:,p] = Wout (Win x[b,:,p]) + bias on NCHW images in one launch; Win (R, C), Wout (N, R), R <= 256."""
+    """y[b,:,p] = Wout (Win x[b,:,p]) + bias on NCHW images in one launch; Win (R, C), Wout (N, R), R <= 256.  The saved
+    route is `_ChainFused`'s on images: H and dH are (B, R, H, W) tensors."""
 
     @staticmethod
-    def forward(ctx, x, w_in, w_out, bias, planes):
+    def forward(ctx, x, w_in, w_out, bias, planes, save):
         if not x.is_cuda:
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
         _inference_only(x)
@@ -288,17 +333,43 @@ class _Conv1x1Chain(torch.autograd.Function):
         fresh = planes is None
         if fresh:
             planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
-        y = ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
-        ctx.save_for_backward(x, w_in, w_out)
+        ctx.saved_route = _saved_route(ctx, x, w_in, w_out, save, True)
+        h = None
+        if ctx.saved_route and ctx.needs_input_grad[2]:              # H feeds dWout alone
+            y, h = ops.svd_conv_save(x, planes[0], planes[1], bias, w_out.shape[0], w_in.shape[0])
+        else:
+            y = ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
+        ctx.save_for_backward(x, w_in, w_out, h)
         ctx.has_bias = bias is not None
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, w_in, w_out = ctx.saved_tensors
+        x, w_in, w_out, h = ctx.saved_tensors
         g = g.contiguous()
         n = _nplanes(g)
         gx = gwi = gwo = gb = None
+        if ctx.saved_route:
+            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:  # dX and dH = Wout^T dY from one launch
+                gx, gr = ops.svd_conv_save(g, planes_of(w_out, n, pad_rows=64, transpose=True),
+                                           planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
+                                           w_in.shape[0], entry="tadmm_svdconv_bwd_save")
+                gwi = ops.wgrad(gr, x).to(w_in.dtype)
+                del gr
+            elif ctx.needs_input_grad[0]:
+                gx = ops.svd_conv(g, planes_of(w_out, n, pad_rows=64, transpose=True),
+                                  planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
+                                  entry="tadmm_svdconv_bwd", memo=False)
+            elif ctx.needs_input_grad[1]:           # no dX wanted: product 1 alone
+                gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1],
+                                      entry="tadmm_tucker_1x1", image_out=True, memo=False)
+                gwi = ops.wgrad(gr, x).to(w_in.dtype)
+                del gr
+            if ctx.needs_input_grad[2]:             # dWout = dY H^T over all pixels, H from the forward launch
+                gwo = ops.wgrad(g, h).to(w_out.dtype)
+            if ctx.has_bias and ctx.needs_input_grad[3]:
+                gb = g.sum((0, 2, 3))
+            return gx, gwi, gwo, gb, None, None
         if ctx.needs_input_grad[0]:                 # dX = Win^T (Wout^T dY): the fused kernel on the transposed factors
             gx = ops.svd_conv(g, planes_of(w_out, n, pad_rows=64, transpose=True),
                               planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
@@ -314,13 +385,17 @@ class _Conv1x1Chain(torch.autograd.Function):
             gwo = ops.wgrad(g, h).to(w_out.dtype)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum((0, 2, 3))
-        return gx, gwi, gwo, gb, None
+        return gx, gwi, gwo, gb, None, None
 
 
-def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None, planes=None):
+def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None, planes=None,
+                  save=None):
     """(B, C, H, W) -> (B, N, H, W): the 1x1 convolution with the rank-R factorisation Wout Win (SVDConv.py) as one launch
     of the fused chain on the NCHW tensors in place (`tadmm_svdconv_fwd`).  Differentiable; the data gradient is one
-    `tadmm_svdconv_bwd` launch.  `planes`: prebuilt (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))."""
+    `tadmm_svdconv_bwd` launch.  `planes`: prebuilt (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64)).
+    `save` as for `linear_chain`: True stores H = Win x in the forward launch and dH = Wout^T dY in the data-gradient
+    launch (`tadmm_svdconv_fwd_save` / `_bwd_save`) for the two weight gradients, keeping B x R x H x W elements of x's
+    dtype alive from forward to backward; False recomputes both; None: `ops.chain_train_pays` decides."""
     if x.dim() != 4:
         raise ValueError("conv1x1_chain expects an NCHW image")
     if not fused_rank_ok(w_in.shape[0]):
@@ -331,7 +406,7 @@ def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias
             n = _nplanes(x)
             planes = (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x))
         return ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
-    return _Conv1x1Chain.apply(x.contiguous(), w_in, w_out, bias, planes)
+    return _Conv1x1Chain.apply(x.contiguous(), w_in, w_out, bias, planes, save)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -500,7 +500,11 @@ def _chain_dtype(xdtype, who: str):
 
 
 def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin: int, n1: int, n_out: int,
-                image_out: bool, tile_tokens: int, prepare_only: bool = False, use_memo: bool = True):
+                image_out: bool, tile_tokens: int, prepare_only: bool = False, use_memo: bool = True, save_rank: int = 0):
+    """`save_rank` > 0: `entry` is one of the `_save` entries; the launch also stores the first `save_rank` columns of the
+    middle-rank vector and the result is (y, h).  Such a launch never enters the memo."""
+    if save_rank:
+        use_memo = False
     if not x.is_cuda:
         raise TadmmError(-1, "x must live on a HIP device; there is no CPU path")
     if x.dim() == 4:                                   # (B, C, H, W) read in place
@@ -563,12 +567,25 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
             _CHAIN_MEMO.store(key, memo)
     d, fn, h, yshape, T, _ = memo
     y = torch.empty(yshape, dtype=x.dtype, device=x.device)
+    hbuf, ldh = None, 0
+    if save_rank:
+        if not 0 < save_rank <= n1:
+            raise TadmmError(-1, f"chain: true rank {save_rank} outside (0, {n1}]")
+        if x.dim() == 4:                               # one contiguous NCHW tensor: the image layout of `wgrad`
+            ldh = save_rank
+            hbuf = torch.empty((x.shape[0], save_rank, x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device)
+        else:                                          # rows padded to whole 16-byte units: every store is a vector
+            epl = 16 // x.element_size()
+            ldh = -(-save_rank // epl) * epl
+            hbuf = torch.empty((T, ldh), dtype=x.dtype, device=x.device)[:, :save_rank]
 
     def launch():
         d.X, d.Y = x.data_ptr(), y.data_ptr()
-        if T > 0:
+        if T > 0 and save_rank:
+            h.check(fn(h.ptr, C.byref(d), save_rank, hbuf.data_ptr(), ldh, _stream(x.device)))
+        elif T > 0:
             h.check(fn(h.ptr, C.byref(d), _stream(x.device)))
-        return y
+        return (y, hbuf) if save_rank else y
 
     if prepare_only:
         return launch
@@ -581,6 +598,19 @@ def chain_fused(x, win_planes, wout_planes, bias, n_out: int, entry: str = "tadm
     padded to the middle rank R, a multiple of 64, <= 256) and `wout_planes` come from `weight_planes`."""
     return _chain_call(entry, x, win_planes, wout_planes, bias, x.shape[-1], win_planes.shape[1] * 16, n_out, False,
                        tile_tokens, prepare_only, memo)
+
+
+def chain_fused_save(x, win_planes, wout_planes, bias, n_out: int, r: int, entry: str = "tadmm_ttlinear_fwd_save",
+                     tile_tokens: int = 0):
+    """`chain_fused` that also returns the middle-rank vector of every token: (y (T, n_out), h (T, r)) with
+    h = x @ Win^T -- what the launch keeps in LDS between its two products, stored in x's dtype (bfloat16: the rounding
+    product 2 reads; float32: the fp32 accumulator).  `r` is the true middle rank, at most the planes' padded one; y is
+    bit-identical to `chain_fused`'s.  `entry="tadmm_ttlinear_bwd_save"` with the transposed planes of the data gradient:
+    (dX, dH = dY @ Wout).  h is a (T, r) view of rows padded to whole 16-byte units (`ops.wgrad` reads it in place); it
+    lives as long as the caller keeps it: T x r elements the plain launch never materialises.  float32 and bfloat16
+    only; no launch memo (training packs its planes every step)."""
+    return _chain_call(entry, x, win_planes, wout_planes, bias, x.shape[-1], win_planes.shape[1] * 16, n_out, False,
+                       tile_tokens, save_rank=r)
 
 
 def chain_single(x, w_planes, bias, n_out: int, entry: str = "tadmm_ttconv_chain_in", image_out: bool = False,
@@ -601,6 +631,33 @@ def svd_conv(x, win_planes, wout_planes, bias, n_out: int, entry: str = "tadmm_s
         raise TadmmError(-1, "svd_conv: x must be an NCHW image")
     return _chain_call(entry, x, win_planes, wout_planes, bias, x.shape[1], win_planes.shape[1] * 16, n_out, True,
                        tile_tokens, prepare_only, memo)
+
+
+def svd_conv_save(x, win_planes, wout_planes, bias, n_out: int, r: int, entry: str = "tadmm_svdconv_fwd_save",
+                  tile_tokens: int = 0):
+    """`svd_conv` that also returns the rank-r image between its two products: (y (B, n_out, H, W), h (B, r, H, W)),
+    h = Win x per pixel, contiguous NCHW in x's dtype (see `chain_fused_save`).  `entry="tadmm_svdconv_bwd_save"` with the
+    transposed planes: (dX, dH = Wout^T dY).  Keeps B x r x H x W elements alive that the plain launch does not."""
+    if x.dim() != 4:
+        raise TadmmError(-1, "svd_conv_save: x must be an NCHW image")
+    return _chain_call(entry, x, win_planes, wout_planes, bias, x.shape[1], win_planes.shape[1] * 16, n_out, True,
+                       tile_tokens, save_rank=r)
+
+
+def chain_train_pays(x: torch.Tensor, r: int, n_in: int, n_out: int, image: bool, factor_grad: bool = True) -> bool:
+    """True when a training step of the fused chain -- token rows (T, n_in), or with `image` an NCHW tensor
+    (B, n_in, H, W), through middle rank `r` to `n_out` features -- should store its middle-rank intermediates
+    (`chain_fused_save` / `svd_conv_save`: four launches, H kept from forward to backward) instead of recomputing them in
+    the backward (two extra `chain_single` launches, nothing kept).  A pure function of its arguments: dtype, shape, the
+    numbers given.  Always False where the saving entries do not exist or nothing would read what they store: float16,
+    ranks above 256 (or below 1), and `factor_grad=False` -- no factor wants a gradient.
+    The rule proper is set by `scripts/bench_linear_train.py`: True only for a dtype / shape
+    class in which the saved route is ahead of the recomputing one by more than the min..max spread of both.  No class
+    has been shown to be: the rule is False everywhere, today's route stays the default, and the saving entries are
+    reached with `save=True`."""
+    if not factor_grad or x.dtype not in (torch.float32, torch.bfloat16) or not 0 < r <= 256:
+        return False
+    return False
 
 
 def svd_conv_pays(x: torch.Tensor, rank: int) -> bool:

@@ -309,6 +309,24 @@ int tadmm_svdconv_fwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
 /* Its data gradient dX = Win^T (Wout^T dY): the same kernel with X = dY, Win = Wout^T planes (R x C_out),
  * Wout = Win^T planes (C_in x R), bias NULL.  dtype: F32 | BF16 | F16. */
 int tadmm_svdconv_bwd(tadmm_handle h, const tadmm_chain_desc* d, void* stream);
+/* Training on the fused chains: the four entries above that also store the middle-rank vector -- product 1, which the
+ * plain entries keep in LDS and drop -- for the two weight gradients (tadmm_wgrad).  The descriptor is the plain
+ * entry's; r in (0, R] is the true middle rank (R its padding), and only columns [0, r) are stored:
+ *   _fwd_save : h_out  = H  = X Win^T          (dWout = dY^T H)
+ *   _bwd_save : dh_out = dH = dY Wout          (dWin  = dH^T X), with the transposed planes of the _bwd entries.
+ * The stored value is what product 2 reads: the bfloat16 rounding of the fp32 accumulator (TADMM_CHAIN_BF16), or the
+ * accumulator itself (TADMM_CHAIN_F32).  Y is bit-identical to the plain entry's: the save adds stores, nothing else.
+ * Layout, of the descriptor's dtype: tadmm_ttlinear_*: token rows (T, r) with row stride ldh >= r elements;
+ * tadmm_svdconv_*: channels [0, r) of images (T / x_hw, ldh, x_hw), ldh >= r channels per image (ldh == r: one contiguous
+ * NCHW tensor, the image layout of tadmm_wgrad).  Nothing else of the buffer is written.  Stores are 16-byte units where
+ * h_out is 16-byte aligned and ldh (rows) or x_hw (images) is a whole number of them, single elements otherwise.
+ * TADMM_ERR_INVALID, with nothing launched: TADMM_CHAIN_F16 (there is no binary16 weight gradient), a null h_out, r
+ * outside (0, R], ldh < r, an h_out that is not aligned to its element; and whatever the plain entry refuses, with the
+ * plain entry's status. */
+int tadmm_ttlinear_fwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* h_out, int64_t ldh, void* stream);
+int tadmm_ttlinear_bwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* dh_out, int64_t ldh, void* stream);
+int tadmm_svdconv_fwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* h_out, int64_t ldh, void* stream);
+int tadmm_svdconv_bwd_save(tadmm_handle h, const tadmm_chain_desc* d, int r, void* dh_out, int64_t ldh, void* stream);
 
 /* ---- weight gradients of the factorised layers (csrc/wgrad.hip) ---------------------------------------------------
  * C[m][n] = alpha * sum_{t < T} A[t][m] * B[t][n], float32 C with row stride ldc: dW = dY^T X and its kin, a small
