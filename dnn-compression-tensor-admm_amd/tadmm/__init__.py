@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -22,6 +22,9 @@ def __getattr__(name):
         "SVDConv2dR": ("svd_layers", "SVDConv2dR"), "SVDConv2dC": ("svd_layers", "SVDConv2dC"),
         "SVDConv2dM": ("svd_layers", "SVDConv2dM"),
         "append_double_l2_loss": ("orthogonal", "append_double_l2_loss"),
+        "StfTKConv2dC": ("stf_layers", "StfTKConv2dC"), "StiefelParameter": ("stf_layers", "StiefelParameter"),
+        "StiefelSGD": ("riemannian", "StiefelSGD"),
+        "stiefel_step": ("ops", "stiefel_step"), "stiefel_project_": ("ops", "stiefel_project_"),
     }
     if name in table:
         mod, attr = table[name]

@@ -89,6 +89,13 @@ class OrthDesc(C.Structure):
     ]
 
 
+class StiefelDesc(C.Structure):
+    _fields_ = [
+        ("X", C.c_void_p), ("G", C.c_void_p), ("M", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32),
+        ("ld", C.c_int64),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -154,6 +161,14 @@ ABI = {
                                          C.c_void_p, C.POINTER(C.c_void_p)]),
     "tadmm_orth_l2": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tadmm_orth_plan_destroy": (C.c_int, [C.c_void_p]),
+    "tadmm_stiefel_desc_bytes": (C.c_int, []),
+    "tadmm_stiefel_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(StiefelDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_stiefel_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(StiefelDesc), C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.POINTER(C.c_void_p)]),
+    "tadmm_stiefel_step": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
+    "tadmm_stiefel_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tadmm_stiefel_plan_destroy": (C.c_int, [C.c_void_p]),
     "tadmm_gemm_pack_bytes": (C.c_size_t, [C.c_int, C.POINTER(GemmDesc)]),
     "tadmm_gemm_pack": (C.c_int, [C.c_int, C.POINTER(GemmDesc), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "tadmm_gemm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -262,6 +277,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_conv_chain_desc layout mismatch")
         if lib.tadmm_orth_desc_bytes() != C.sizeof(OrthDesc):
             raise TadmmLibraryError(f"{path}: tadmm_orth_desc layout mismatch")
+        if lib.tadmm_stiefel_desc_bytes() != C.sizeof(StiefelDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_stiefel_desc layout mismatch")
         if lib.tadmm_wgrad_desc_bytes() != C.sizeof(WgradDesc):
             raise TadmmLibraryError(f"{path}: tadmm_wgrad_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import weakref
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -14,7 +15,7 @@ import torch
 
 from . import _cabi
 from ._cabi import (FLAG_SKIP_ROTATIONS, KIND_SVD, KIND_TT_CONV, KIND_TT_LINEAR, KIND_TUCKER2, GemmDesc, Handle,
-                    LayerDesc, TadmmError, make_layer_desc)
+                    LayerDesc, StiefelDesc, TadmmError, make_layer_desc)
 
 
 def _require_cuda(t: torch.Tensor, what: str):
@@ -1175,3 +1176,199 @@ def cholqr_(yt: torch.Tensor) -> bool:
     h.check(h.lib.tadmm_cholqr_f64(h.ptr, yt.data_ptr(), n, ncols, yt.stride(0), scratch.data_ptr(), sb, C.byref(bad),
                                    _stream(yt.device)))
     return bad.value == 0
+
+
+# ------------------------------------------------------------------ Stiefel manifold (csrc/stiefel.hip)
+STIEFEL_LDS_BYTES = 160 * 1024
+STIEFEL_PIVOT_FLOOR = 4e-14      # kStfPivotFloor of csrc/stiefel.hip
+STIEFEL_SECOND_PASS = 1e4       # kStfSecondPass: pivot spread above which the kernel runs a second Cholesky-QR pass
+
+
+def _align16(v: int) -> int:
+    return (v + 15) & ~15
+
+
+def stiefel_lds_bytes(n: int, p: int) -> int:
+    """LDS of the resident step for one n x p factor, as csrc/stiefel.hip sizes it: three fp32 tiles and two fp64 p x p
+    matrices at a row pitch of p|1, two fp64 p-vectors, each carve rounded up to 16 bytes."""
+    pitch = p | 1
+    return 3 * _align16(n * pitch * 4) + 2 * _align16(p * pitch * 8) + 2 * _align16(p * 8)
+
+
+def stiefel_fits(n: int, p: int) -> bool:
+    """True when an n x p factor takes the one-launch LDS-resident route (64 x 64 and 123 x 64 do, 124 x 64 does not);
+    the others take the composed device route of `StiefelPlan`.  Pure host logic."""
+    return 1 <= p <= n and p <= 128 and stiefel_lds_bytes(n, p) <= STIEFEL_LDS_BYTES
+
+
+def stiefel_desc(x: torch.Tensor, g: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None) -> StiefelDesc:
+    """`tadmm_stiefel_desc` of a factor, its gradient and its momentum buffer (either may be None).  Host only: raises,
+    before anything is launched, for a factor that is not a float32 row-major n x p matrix with n >= p, and for a
+    gradient or buffer that is not laid out like the factor."""
+    if x.dim() != 2:
+        raise TadmmError(-1, f"a Stiefel factor is a matrix (got shape {tuple(x.shape)})")
+    n, p = int(x.shape[0]), int(x.shape[1])
+    if p < 1 or n < p:
+        raise TadmmError(-1, f"a Stiefel factor is n x p with n >= p >= 1 (got {n} x {p})")
+    ld = int(x.stride(0)) if n > 1 else max(int(x.stride(0)), p)
+    for what, t in (("factor", x), ("gradient", g), ("momentum buffer", m)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TadmmError(-1, f"the Stiefel {what} must be float32 (got {t.dtype})")
+        if tuple(t.shape) != (n, p) or t.device != x.device:
+            raise TadmmError(-1, f"the Stiefel {what} must match its {n} x {p} factor on {x.device} "
+                                 f"(got {tuple(t.shape)} on {t.device})")
+        if (p > 1 and t.stride(1) != 1) or (n > 1 and (t.stride(0) < p or t.stride(0) != ld)):
+            raise TadmmError(-1, f"the Stiefel {what} must be stored row-major with the factor's row stride {ld} "
+                                 f"(strides {tuple(t.stride())})")
+    d = StiefelDesc()
+    d.X = x.data_ptr()
+    d.G = g.data_ptr() if g is not None else None
+    d.M = m.data_ptr() if m is not None else None
+    d.rows, d.cols, d.ld = n, p, ld
+    return d
+
+
+def _sym(a: torch.Tensor) -> torch.Tensor:
+    return 0.5 * (a + a.t())
+
+
+def _cholqr_composed(y: torch.Tensor):
+    """Q factor (positive diagonal of R) of a float64 device matrix by two Cholesky-QR passes of library calls; returns
+    (Q, ok) with ok a 0-dim bool tensor -- nothing synchronises."""
+    ok = None
+    for _ in range(2):
+        s = y.t() @ y
+        l, info = torch.linalg.cholesky_ex(s)                                # Y^T Y = L L^T, R = L^T
+        y = torch.linalg.solve_triangular(l, y.t(), upper=False).t()         # Y R^-1 = (L^-1 Y^T)^T
+        # the kernel's rule: every squared pivot above STIEFEL_PIVOT_FLOOR times its column's squared norm, and finite
+        floor = (torch.diagonal(l) ** 2 > STIEFEL_PIVOT_FLOOR * torch.diagonal(s)).all()
+        good = (info == 0) & floor & torch.isfinite(y).all()
+        ok = good if ok is None else ok & good
+    return y, ok
+
+
+class StiefelPlan:
+    """One set of Stiefel factors updated together (`tadmm_stiefel_plan`): `factors` is a list of (X, G, M) float32
+    row-major device matrices, G and M laid out like X or None (G None: the factor is skipped by `step`; M None: only
+    with momentum == 0 and for `project_`).  The factors that fit the LDS (`stiefel_fits`) go through ONE native launch
+    per call; the others take the composed device route, a few float64 library calls per factor (products,
+    `torch.linalg.cholesky_ex`, `solve_triangular`) with the same arithmetic.  Neither route synchronises: a factor whose
+    Cholesky pivot broke down keeps X and M and has its word of `status` (int32, sticky) set; `failed()` reads them.
+    Both routes refuse a factor by the same rule (a squared pivot not above 4e-14 times its column's squared norm, or a
+    non-finite value); the composed route always runs two Cholesky-QR passes where the kernel runs the second only for
+    a pivot spread above 1e4, so the two agree to fp32 rounding, not bit for bit.
+    `native=False` sends every factor through the composed route (the comparator of scripts/bench_stiefel.py)."""
+
+    def __init__(self, factors: Sequence, native: bool = True):
+        if not factors:
+            raise TadmmError(-1, "StiefelPlan: no factors")
+        dev = factors[0][0].device
+        if dev.type != "cuda":
+            raise TadmmError(-1, f"Stiefel factors must live on a HIP device (got {dev}); there is no CPU path")
+        descs = []
+        for x, g, m in factors:
+            if x.device != dev:
+                raise TadmmError(-1, f"Stiefel factors of one plan share a device (got {x.device} and {dev})")
+            descs.append(stiefel_desc(x, g, m))
+        self.device = dev
+        self.factors = [tuple(f) for f in factors]
+        self.native = [i for i, d in enumerate(descs) if native and stiefel_fits(d.rows, d.cols)]
+        self.composed = [i for i in range(len(descs)) if i not in set(self.native)]
+        self.order = self.native + self.composed                  # status word k belongs to factor order[k]
+        self.status = torch.zeros(len(descs), dtype=torch.int32, device=dev)
+        self._plan = None
+        if self.native:
+            self.h = Handle.get(dev.index)
+            lib = self.h.lib
+            n = len(self.native)
+            arr = (StiefelDesc * n)(*[descs[i] for i in self.native])
+            size = C.c_size_t()
+            self.h.check(lib.tadmm_stiefel_workspace_bytes(n, arr, C.byref(size)))
+            self.workspace = torch.empty(int(size.value), dtype=torch.uint8, device=dev)
+            plan = C.c_void_p()
+            self.h.check(lib.tadmm_stiefel_plan_create(self.h.ptr, n, arr, self.workspace.data_ptr(), int(size.value),
+                                                       _stream(dev), C.byref(plan)))
+            self._plan = plan
+            self._fin = weakref.finalize(self, lib.tadmm_stiefel_plan_destroy, plan)
+
+    def _touched(self, with_m: bool, skipped_too: bool):
+        # the launches write through raw pointers: tell autograd and the layers' inference caches (`param_key`);
+        # a factor skipped for a null G was not written and keeps its caches
+        for x, g, m in self.factors:
+            if g is None and not skipped_too:
+                continue
+            torch.autograd.graph.increment_version(x)
+            if with_m and m is not None:
+                torch.autograd.graph.increment_version(m)
+
+    def step(self, lr: float, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+             nesterov: bool = False):
+        if momentum < 0:
+            raise TadmmError(-1, f"Stiefel step: momentum {momentum} < 0")
+        if momentum > 0 and any(m is None for _, _, m in self.factors):
+            raise TadmmError(-1, "Stiefel step: momentum > 0 needs a momentum buffer for every factor")
+        if self._plan is not None:
+            self.h.check(self.h.lib.tadmm_stiefel_step(self._plan, float(lr), float(momentum), float(dampening),
+                                                       float(weight_decay), int(bool(nesterov)), self.status.data_ptr(),
+                                                       _stream(self.device)))
+        with torch.no_grad():
+            for k, i in enumerate(self.composed, start=len(self.native)):
+                x, g, m = self.factors[i]
+                if g is None:
+                    continue
+                x64 = x.double()
+                g64 = g.double() + weight_decay * x64
+                r = g64 - x64 @ _sym(x64.t() @ g64)
+                if momentum > 0:
+                    m64 = momentum * m.double() + (1.0 - dampening) * r
+                    d = r + momentum * m64 if nesterov else m64
+                else:
+                    d = r
+                q, ok = _cholqr_composed(x64 - lr * d)
+                if momentum > 0:
+                    m64 = m64 - q @ _sym(q.t() @ m64)
+                    ok = ok & torch.isfinite(m64).all()
+                    m.copy_(torch.where(ok, m64.float(), m))
+                x.copy_(torch.where(ok, q.float(), x))
+                self.status[k:k + 1] |= (~ok).to(torch.int32)
+        self._touched(momentum > 0, False)
+
+    def project_(self):
+        """Replaces every X by the Q factor (positive diagonal of R) of its QR decomposition."""
+        if self._plan is not None:
+            self.h.check(self.h.lib.tadmm_stiefel_project(self._plan, self.status.data_ptr(), _stream(self.device)))
+        with torch.no_grad():
+            for k, i in enumerate(self.composed, start=len(self.native)):
+                x = self.factors[i][0]
+                q, ok = _cholqr_composed(x.double())
+                x.copy_(torch.where(ok, q.float(), x))
+                self.status[k:k + 1] |= (~ok).to(torch.int32)
+        self._touched(False, True)
+
+    def status_of(self, i: int) -> torch.Tensor:
+        """The status word of factor i as a one-element device view (no synchronisation)."""
+        k = self.order.index(i)
+        return self.status[k:k + 1]
+
+    def failed(self) -> List[int]:
+        """Indices (into `factors`) of the factors whose status word is set; one synchronisation."""
+        flags = self.status.cpu().tolist()
+        return sorted(self.order[k] for k, f in enumerate(flags) if f)
+
+
+def stiefel_step(factors: Sequence, lr: float, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False) -> StiefelPlan:
+    """One Riemannian SGD step on a list of (X, G, M) (see `StiefelPlan`), in place; returns the plan, whose `failed()`
+    names the factors that were left untouched.  Callers that step repeatedly keep a `StiefelPlan`."""
+    plan = StiefelPlan(factors)
+    plan.step(lr, momentum, dampening, weight_decay, nesterov)
+    return plan
+
+
+def stiefel_project_(*xs: torch.Tensor) -> StiefelPlan:
+    """Puts every given matrix on the Stiefel manifold in place (Q factor of its QR decomposition, diag(R) > 0)."""
+    plan = StiefelPlan([(x, None, None) for x in xs])
+    plan.project_()
+    return plan

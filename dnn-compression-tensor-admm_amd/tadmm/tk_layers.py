@@ -99,16 +99,18 @@ class TKConv2dC(_TKConvBase):
         for p in (self.first_kernel, self.core_kernel, self.last_kernel):
             init.xavier_uniform_(p)
 
-    def _stages(self, x):
+    def _stages(self, x, w1=None, w3=None):
         # a 1x1 conv is a per-pixel channel mix: one chain-kernel launch on the NCHW tensor as it stands
-        # (`tadmm_tucker_1x1`: no NHWC copies, bias in the epilogue)
+        # (`tadmm_tucker_1x1`: no NHWC copies, bias in the epilogue).  w1 (in_rank, in_channels) / w3 (out_channels,
+        # out_rank): given by layers that store the two factors in another layout (stf_layers.StfTKConv2dC)
         grad = torch.is_grad_enabled()
         cache = None if grad else self.__dict__.setdefault("_plane_cache", {})
-        w1 = self.first_kernel.reshape(self.in_rank, self.in_channels)
-        w3 = self.last_kernel.reshape(self.out_channels, self.out_rank)
+        if w1 is None:
+            w1 = self.first_kernel.reshape(self.in_rank, self.in_channels)
+        if w3 is None:
+            w3 = self.last_kernel.reshape(self.out_channels, self.out_rank)
         n = HF._nplanes(x)
-        p1 = None if grad else HF.planes_of(self.first_kernel.reshape(self.in_rank, self.in_channels), n, cache=cache,
-                                            tag="first", like=x)
+        p1 = None if grad else HF.planes_of(w1, n, cache=cache, tag="first", like=x)
         f1 = HF.pointwise(x, w1, None, "tadmm_tucker_1x1", p1)
         f2 = HF.core_conv_routed(self, f1)                      # the native k x k kernel where it pays (csrc/coreconv.hip)
         if f2 is None:

@@ -222,6 +222,41 @@ int tadmm_orth_plan_create(tadmm_handle h, int n, const tadmm_orth_desc* descs, 
 int tadmm_orth_l2(tadmm_orth_plan p, double rho, float* grad, double* loss_dev, void* stream);
 int tadmm_orth_plan_destroy(tadmm_orth_plan p);
 
+/* ---- Riemannian SGD on the Stiefel manifold (StfTKConv.py + geoopt.optim.RiemannianSGD) --------------------------
+ * Every factor X (rows x cols float32, rows >= cols, row stride ld >= cols, 4-byte aligned, columns orthonormal) of a
+ * model is updated in place by ONE launch, one workgroup per factor, its tiles resident in LDS (csrc/stiefel.hip).
+ * With G the gradient and M the momentum buffer (both laid out like X), sym(A) = (A + A^T) / 2:
+ *   g = G + weight_decay X;   r = g - X sym(X^T g);
+ *   momentum > 0:  M <- momentum M + (1 - dampening) r,   d = nesterov ? r + momentum M : M;      else d = r
+ *   X <- Q factor (positive diagonal of R) of X - lr d;   momentum > 0:  M <- M - X sym(X^T M)
+ * Inner products are accumulated in fp64 from the fp32 tiles, the QR is a Cholesky QR in fp64 (a second pass when the
+ * pivots spread by more than 1e4), every stored entry is rounded to fp32 once.
+ * G == NULL: the factor is skipped by tadmm_stiefel_step (X and M untouched).  M may be NULL when momentum == 0 and
+ * for plans used by tadmm_stiefel_project only, which replaces every X by the Q factor of X (any full-rank X).
+ * A factor whose Cholesky pivot is not positive and finite (rank-deficient or non-finite input) keeps X and M and gets
+ * status_dev[i] = 1 (int32 per factor, never cleared by the library, may be NULL); nothing synchronises.
+ * tadmm_stiefel_workspace_bytes / _plan_create return TADMM_ERR_INVALID for n <= 0, rows < cols, cols <= 0, ld < cols,
+ * a null or misaligned X, and TADMM_ERR_UNSUPPORTED for a factor whose tiles do not fit the LDS
+ * (12 rows (cols|1) + 16 cols (cols|1) + 16 cols bytes <= 160 KiB; 64 x 64 and 123 x 64 fit).  The plan uploads its
+ * table once, ordered on `stream` (the call waits for the copy); step / project copy nothing. */
+typedef struct {
+  float* X;
+  const float* G;
+  float* M;
+  int32_t rows, cols;
+  int64_t ld;
+} tadmm_stiefel_desc;
+typedef struct tadmm_stiefel_plan_s* tadmm_stiefel_plan;
+/* sizeof(tadmm_stiefel_desc) as the library was built */
+int tadmm_stiefel_desc_bytes(void);
+int tadmm_stiefel_workspace_bytes(int n, const tadmm_stiefel_desc* descs, size_t* bytes);
+int tadmm_stiefel_plan_create(tadmm_handle h, int n, const tadmm_stiefel_desc* descs, void* workspace,
+                              size_t workspace_bytes, void* stream, tadmm_stiefel_plan* out);
+int tadmm_stiefel_step(tadmm_stiefel_plan p, double lr, double momentum, double dampening, double weight_decay,
+                       int nesterov, int32_t* status_dev, void* stream);
+int tadmm_stiefel_project(tadmm_stiefel_plan p, int32_t* status_dev, void* stream);
+int tadmm_stiefel_plan_destroy(tadmm_stiefel_plan p);
+
 /* ---- building blocks (also used by the factorised layers) -------------- */
 /* C[i,j] = alpha * sum_k A(i,k) B(k,j) (+ beta*C) with arbitrary element strides; one of the two
  * strides of each operand must be 1.  Replaces the torch.mm / F.linear chains of
