@@ -9,6 +9,17 @@
 //   5. X+ = Q factor of Y = Q R with diag(R) > 0    the QR retraction with geoopt's sign "unflip"
 //   6. momentum > 0:  M+ = M - X+ sym(X+^T M)       vector transport by projection
 // `project` mode is step 5 alone on an arbitrary full-rank X.
+// Riemannian Adam (geoopt.optim.RiemannianAdam) is a second instantiation of the same body, `stiefel_adam_kernel`.  M is
+// exp_avg; v (ONE float32 second moment per factor), vmax (its running maximum, amsgrad) and t (int32 counter) live in
+// per-factor device arrays:
+//   3'. t' = t + 1,  s = sum r^2,  M' = beta1 M + (1 - beta1) r,  v' = beta2 v + (1 - beta2) s,  u = amsgrad ? max(vmax, v') : v'
+//   4'. Y = X - lr / ((1 - beta1^t') (sqrt(u / (1 - beta2^t')) + eps)) M'
+// then steps 5 and 6.  The scale of step 4' needs s over the whole factor, so Y cannot be formed in the epilogue of the
+// tangent-projection product as the SGD mode does: the epilogue stores M' and keeps per-thread fp64 partial sums of r^2,
+// a fixed-order reduction follows (a butterfly inside each wave, the four waves' sums added in order from LDS that is
+// idle at that point: the fp64 carves, 64 contiguous bytes even at p = 1), and one elementwise pass forms Y -- two
+// barriers more than the SGD mode.  The bias corrections come from the factor's own counter, in fp64, on the device.
+// v', u and t' are written by thread 0 in the last phase, like X and M, so a failed factor keeps all five.
 //
 // Arithmetic.  HBM is read once (X, G, M) and written once (X, M); everything between lives in LDS: three fp32 tiles
 // (row pitch p|1) and two fp64 p x p matrices (row pitch p|1) plus two fp64 p-vectors.  Every inner product (X^T g, the
@@ -160,13 +171,23 @@ __device__ bool stf_cholqr(const float* __restrict__ Y, float* __restrict__ Q, d
   return true;
 }
 
-// mode 0: one optimiser step, mode 1: project
-__global__ __launch_bounds__(kStfThreads) void stiefel_kernel(const tadmm_stiefel_desc* __restrict__ descs, int mode,
-                                                              double lr, double mom, double damp, double wd, int nesterov,
-                                                              int32_t* __restrict__ status) {
+// what the Adam instantiation needs on top of the SGD arguments; v, vmax, t hold one entry per factor in descriptor order
+struct StfAdam {
+  double b1, b2, eps;
+  int amsgrad;
+  float* v;
+  float* vmax;
+  int32_t* t;
+};
+
+// mode 0: one optimiser step, mode 1: project.  kAdam: the Adam step (always mode 0; mom, damp, nesterov unused).
+template <bool kAdam>
+__device__ __forceinline__ void stf_body(const tadmm_stiefel_desc* __restrict__ descs, int mode, double lr, double mom,
+                                         double damp, double wd, int nesterov, const StfAdam& ad,
+                                         int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const tadmm_stiefel_desc d = descs[blockIdx.x];
-  const bool step = mode == 0;
+  const bool step = kAdam || mode == 0;
   if (step && !d.G) return;                 // no gradient this step: the factor is skipped
   const int tid = threadIdx.x;
   const int n = d.rows, p = d.cols, pt = p | 1, ps = p | 1;
@@ -178,7 +199,15 @@ __global__ __launch_bounds__(kStfThreads) void stiefel_kernel(const tadmm_stiefe
   double* W = (double*)((char*)S + stf_mat_bytes(p));
   double* d0 = (double*)((char*)W + stf_mat_bytes(p));
   double* inv = (double*)((char*)d0 + stf_vec_bytes(p));
-  const bool use_m = step && mom > 0.0;
+  const bool use_m = kAdam || (step && mom > 0.0);
+  // Adam: the factor's counter and bias corrections, read and computed while the tiles load
+  int32_t tnew = 0;
+  double c1 = 1.0, c2 = 1.0, vnew = 0.0, vtop = 0.0;
+  if constexpr (kAdam) {
+    tnew = ad.t[blockIdx.x] + 1;
+    c1 = 1.0 - pow(ad.b1, (double)tnew);
+    c2 = 1.0 - pow(ad.b2, (double)tnew);
+  }
 
   float* Yt = tB;     // the matrix to orthonormalise
   float* Qt = tA;     // where its Q factor goes
@@ -195,19 +224,48 @@ __global__ __launch_bounds__(kStfThreads) void stiefel_kernel(const tadmm_stiefe
     __syncthreads();
     stf_sym(S, W, p, ps);
     __syncthreads();
-    const double keep = 1.0 - damp;
-    stf_aw(tA, W, n, p, pt, ps, [&](int i, int j, double acc) {
-      const int o = i * pt + j;
-      const double r = (double)tB[o] - acc;
-      double dir = r;
-      if (use_m) {
-        const double m = fma(mom, (double)tC[o], keep * r);
-        tC[o] = (float)m;
-        dir = nesterov ? fma(mom, m, r) : m;
+    if constexpr (kAdam) {
+      // the step's scale needs s = sum r^2 over the whole factor: the epilogue stores M' and keeps a partial sum, a
+      // fixed-order reduction (butterfly in the wave, then the four waves in order) follows, one more pass forms Y
+      const double keep = 1.0 - ad.b1;
+      double part = 0.0;
+      stf_aw(tA, W, n, p, pt, ps, [&](int i, int j, double acc) {
+        const int o = i * pt + j;
+        const double r = (double)tB[o] - acc;
+        tC[o] = (float)fma(ad.b1, (double)tC[o], keep * r);
+        part = fma(r, r, part);
+      });
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+      __syncthreads();                      // W has been read: the four fp64 carves (>= 64 contiguous bytes) are free
+      double* red = S;
+      if ((tid & 63) == 0) red[tid >> 6] = part;
+      __syncthreads();
+      static_assert(kStfThreads == 4 * 64, "the reduction below adds four waves");
+      const double s = ((red[0] + red[1]) + red[2]) + red[3];
+      vnew = fma(ad.b2, (double)ad.v[blockIdx.x], (1.0 - ad.b2) * s);
+      vtop = ad.amsgrad ? fmax((double)ad.vmax[blockIdx.x], vnew) : vnew;
+      const double scale = lr / (c1 * (sqrt(vtop / c2) + ad.eps));
+      for (int e = tid; e < n * p; e += kStfThreads) {
+        const int o = (e / p) * pt + e % p;
+        tB[o] = (float)fma(-scale, (double)tC[o], (double)tA[o]);
       }
-      tB[o] = (float)fma(-lr, dir, (double)tA[o]);
-    });
-    __syncthreads();
+      __syncthreads();
+    } else {
+      const double keep = 1.0 - damp;
+      stf_aw(tA, W, n, p, pt, ps, [&](int i, int j, double acc) {
+        const int o = i * pt + j;
+        const double r = (double)tB[o] - acc;
+        double dir = r;
+        if (use_m) {
+          const double m = fma(mom, (double)tC[o], keep * r);
+          tC[o] = (float)m;
+          dir = nesterov ? fma(mom, m, r) : m;
+        }
+        tB[o] = (float)fma(-lr, dir, (double)tA[o]);
+      });
+      __syncthreads();
+    }
   } else {
     for (int e = tid; e < n * p; e += kStfThreads) {
       const int i = e / p, j = e - i * p;
@@ -222,6 +280,7 @@ __global__ __launch_bounds__(kStfThreads) void stiefel_kernel(const tadmm_stiefe
     ok = stf_cholqr(Qt, Yt, S, W, d0, inv, n, p, pt, ps, &spread);
     Qt = Yt;
   }
+  if constexpr (kAdam) ok = ok && vnew >= 0.0 && vnew < __builtin_huge_val();     // a non-finite second moment fails too
   if (!ok) {
     if (tid == 0 && status) status[blockIdx.x] = 1;
     return;
@@ -242,6 +301,24 @@ __global__ __launch_bounds__(kStfThreads) void stiefel_kernel(const tadmm_stiefe
     d.X[i * ld + j] = Qt[i * pt + j];
     if (use_m) d.M[i * ld + j] = tC[i * pt + j];
   }
+  if constexpr (kAdam) {
+    if (tid == 0) {                         // written in the last phase, like X and M: a failed factor keeps them
+      ad.v[blockIdx.x] = (float)vnew;
+      if (ad.amsgrad) ad.vmax[blockIdx.x] = (float)vtop;
+      ad.t[blockIdx.x] = tnew;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kStfThreads) void stiefel_kernel(const tadmm_stiefel_desc* __restrict__ descs, int mode,
+                                                              double lr, double mom, double damp, double wd, int nesterov,
+                                                              int32_t* __restrict__ status) {
+  stf_body<false>(descs, mode, lr, mom, damp, wd, nesterov, StfAdam{}, status);
+}
+
+__global__ __launch_bounds__(kStfThreads) void stiefel_adam_kernel(const tadmm_stiefel_desc* __restrict__ descs, double lr,
+                                                                   double wd, StfAdam ad, int32_t* __restrict__ status) {
+  stf_body<true>(descs, 0, lr, 0.0, 0.0, wd, 0, ad, status);
 }
 
 }  // namespace tadmm
@@ -283,19 +360,35 @@ int stiefel_check(tadmm_handle h, int n, const tadmm_stiefel_desc* descs, size_t
   return TADMM_OK;
 }
 
+// raises the kernel's dynamic-LDS limit once per device
+int stiefel_allow_lds(tadmm_handle h, const void* kernel, bool* done) {
+  int devi = 0;
+  (void)hipGetDevice(&devi);
+  if (!done[devi & 63]) {
+    HIP_OK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStfMaxLds));
+    done[devi & 63] = true;
+  }
+  return TADMM_OK;
+}
+
 int stiefel_launch(tadmm_stiefel_plan p, int mode, double lr, double mom, double damp, double wd, int nesterov,
                    int32_t* status, hipStream_t s) {
   tadmm_handle h = p->h;
   static bool attr_done[64] = {false};
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (!attr_done[devi & 63]) {
-    HIP_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(stiefel_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStfMaxLds));
-    attr_done[devi & 63] = true;
-  }
+  const int rc = stiefel_allow_lds(h, reinterpret_cast<const void*>(stiefel_kernel), attr_done);
+  if (rc != TADMM_OK) return rc;
   hipLaunchKernelGGL(stiefel_kernel, dim3(p->n), dim3(kStfThreads), p->lds, s, p->descs, mode, lr, mom, damp, wd,
                      nesterov, status);
+  HIP_OK(h, hipGetLastError());
+  return TADMM_OK;
+}
+
+int stiefel_adam_launch(tadmm_stiefel_plan p, double lr, double wd, const StfAdam& ad, int32_t* status, hipStream_t s) {
+  tadmm_handle h = p->h;
+  static bool attr_done[64] = {false};
+  const int rc = stiefel_allow_lds(h, reinterpret_cast<const void*>(stiefel_adam_kernel), attr_done);
+  if (rc != TADMM_OK) return rc;
+  hipLaunchKernelGGL(stiefel_adam_kernel, dim3(p->n), dim3(kStfThreads), p->lds, s, p->descs, lr, wd, ad, status);
   HIP_OK(h, hipGetLastError());
   return TADMM_OK;
 }
@@ -347,6 +440,24 @@ int tadmm_stiefel_step(tadmm_stiefel_plan p, double lr, double momentum, double 
   if (momentum > 0.0 && !p->has_m)
     CTX_FAIL(h, TADMM_ERR_INVALID, "stiefel step: momentum %g needs a momentum buffer for every factor", momentum);
   return stiefel_launch(p, 0, lr, momentum, dampening, weight_decay, nesterov ? 1 : 0, status_dev, (hipStream_t)stream);
+}
+
+int tadmm_stiefel_adam_step(tadmm_stiefel_plan p, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            int amsgrad, float* v_dev, float* vmax_dev, int32_t* step_dev, int32_t* status_dev,
+                            void* stream) {
+  if (!p) return TADMM_ERR_INVALID;
+  tadmm_handle h = p->h;
+  DeviceGuard device_guard(h);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "stiefel adam step: betas (%g, %g) outside [0, 1)", beta1, beta2);
+  if (!(eps >= 0.0) || !(lr >= 0.0) || !(weight_decay >= 0.0))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "stiefel adam step: eps %g, lr %g, weight_decay %g must not be negative", eps, lr,
+             weight_decay);
+  if (!v_dev || !step_dev) CTX_FAIL(h, TADMM_ERR_INVALID, "stiefel adam step: v_dev or step_dev is NULL");
+  if (amsgrad && !vmax_dev) CTX_FAIL(h, TADMM_ERR_INVALID, "stiefel adam step: amsgrad needs vmax_dev");
+  if (!p->has_m) CTX_FAIL(h, TADMM_ERR_INVALID, "stiefel adam step: every factor needs M (exp_avg)");
+  const StfAdam ad = {beta1, beta2, eps, amsgrad ? 1 : 0, v_dev, vmax_dev, step_dev};
+  return stiefel_adam_launch(p, lr, weight_decay, ad, status_dev, (hipStream_t)stream);
 }
 
 int tadmm_stiefel_project(tadmm_stiefel_plan p, int32_t* status_dev, void* stream) {

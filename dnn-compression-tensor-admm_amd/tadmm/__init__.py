@@ -23,7 +23,7 @@ def __getattr__(name):
         "SVDConv2dM": ("svd_layers", "SVDConv2dM"),
         "append_double_l2_loss": ("orthogonal", "append_double_l2_loss"),
         "StfTKConv2dC": ("stf_layers", "StfTKConv2dC"), "StiefelParameter": ("stf_layers", "StiefelParameter"),
-        "StiefelSGD": ("riemannian", "StiefelSGD"),
+        "StiefelSGD": ("riemannian", "StiefelSGD"), "StiefelAdam": ("riemannian", "StiefelAdam"),
         "stiefel_step": ("ops", "stiefel_step"), "stiefel_project_": ("ops", "stiefel_project_"),
     }
     if name in table:

@@ -167,6 +167,8 @@ ABI = {
                                             C.c_void_p, C.POINTER(C.c_void_p)]),
     "tadmm_stiefel_step": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
                                      C.c_void_p]),
+    "tadmm_stiefel_adam_step": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tadmm_stiefel_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tadmm_stiefel_plan_destroy": (C.c_int, [C.c_void_p]),
     "tadmm_gemm_pack_bytes": (C.c_size_t, [C.c_int, C.POINTER(GemmDesc)]),

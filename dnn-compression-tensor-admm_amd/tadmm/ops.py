@@ -1251,8 +1251,8 @@ def _cholqr_composed(y: torch.Tensor):
 
 class StiefelPlan:
     """One set of Stiefel factors updated together (`tadmm_stiefel_plan`): `factors` is a list of (X, G, M) float32
-    row-major device matrices, G and M laid out like X or None (G None: the factor is skipped by `step`; M None: only
-    with momentum == 0 and for `project_`).  The factors that fit the LDS (`stiefel_fits`) go through ONE native launch
+    row-major device matrices, G and M laid out like X or None (G None: the factor is skipped by `step` and `adam_step`;
+    M None: only with momentum == 0 and for `project_`).  The factors that fit the LDS (`stiefel_fits`) go through ONE native launch
     per call; the others take the composed device route, a few float64 library calls per factor (products,
     `torch.linalg.cholesky_ex`, `solve_triangular`) with the same arithmetic.  Neither route synchronises: a factor whose
     Cholesky pivot broke down keeps X and M and has its word of `status` (int32, sticky) set; `failed()` reads them.
@@ -1335,6 +1335,68 @@ class StiefelPlan:
                 self.status[k:k + 1] |= (~ok).to(torch.int32)
         self._touched(momentum > 0, False)
 
+    def adam_step(self, lr: float, betas, eps: float, weight_decay: float, amsgrad: bool, v: torch.Tensor,
+                  vmax: Optional[torch.Tensor], steps: torch.Tensor):
+        """One Riemannian Adam step (`tadmm_stiefel_adam_step`): M of every factor is `exp_avg`; `v` (float32, the second
+        moment, ONE number per factor), `vmax` (float32, its running maximum; needed with amsgrad only) and `steps` (int32
+        counters) are contiguous 1-D device tensors with one entry per factor in the order of `order` -- entry k belongs
+        to factor `order[k]`, as the status words do (`slot_of`).  A skipped (G None) or failed factor keeps X, M and its
+        three entries.  The composed route computes the same arithmetic with float64 library calls."""
+        b1, b2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise TadmmError(-1, f"Stiefel Adam step: betas {tuple(betas)} outside [0, 1)")
+        if not (eps >= 0 and lr >= 0 and weight_decay >= 0):
+            raise TadmmError(-1, f"Stiefel Adam step: eps {eps}, lr {lr}, weight_decay {weight_decay} must not be negative")
+        if any(m is None for _, _, m in self.factors):
+            raise TadmmError(-1, "Stiefel Adam step: every factor needs M (exp_avg)")
+        n = len(self.factors)
+        for what, t, dt in (("v", v, torch.float32), ("vmax", vmax, torch.float32), ("steps", steps, torch.int32)):
+            if t is None and what == "vmax" and not amsgrad:
+                continue
+            if t is None or t.dtype != dt or t.device != self.device or t.dim() != 1 or t.numel() != n \
+                    or not t.is_contiguous():
+                raise TadmmError(-1, f"Stiefel Adam step: {what} must be a contiguous 1-D {dt} tensor of {n} entries on "
+                                     f"{self.device}")
+        if not amsgrad:
+            vmax = None
+        if self._plan is not None:
+            self.h.check(self.h.lib.tadmm_stiefel_adam_step(
+                self._plan, float(lr), b1, b2, float(eps), float(weight_decay), int(bool(amsgrad)), v.data_ptr(),
+                vmax.data_ptr() if vmax is not None else None, steps.data_ptr(), self.status.data_ptr(),
+                _stream(self.device)))
+        with torch.no_grad():
+            for k, i in enumerate(self.composed, start=len(self.native)):
+                x, g, m = self.factors[i]
+                if g is None:
+                    continue
+                x64 = x.double()
+                g64 = g.double() + weight_decay * x64
+                r = g64 - x64 @ _sym(x64.t() @ g64)
+                m64 = b1 * m.double() + (1.0 - b1) * r
+                t_new = steps[k] + 1
+                v_new = b2 * v[k].double() + (1.0 - b2) * (r * r).sum()
+                top = torch.maximum(vmax[k].double(), v_new) if amsgrad else v_new
+                tf = t_new.double()
+                scale = lr / ((1.0 - b1 ** tf) * (torch.sqrt(top / (1.0 - b2 ** tf)) + eps))
+                q, ok = _cholqr_composed(x64 - scale * m64)
+                m64 = m64 - q @ _sym(q.t() @ m64)
+                ok = ok & torch.isfinite(m64).all() & torch.isfinite(v_new)
+                m.copy_(torch.where(ok, m64.float(), m))
+                x.copy_(torch.where(ok, q.float(), x))
+                v[k:k + 1] = torch.where(ok, v_new.float(), v[k])
+                if amsgrad:
+                    vmax[k:k + 1] = torch.where(ok, top.float(), vmax[k])
+                steps[k:k + 1] = torch.where(ok, t_new, steps[k])
+                self.status[k:k + 1] |= (~ok).to(torch.int32)
+        self._touched(True, False)
+        for t in (v, vmax, steps):
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
+
+    def slot_of(self, i: int) -> int:
+        """The position of factor i in the status words and in the per-factor state arrays of `adam_step`."""
+        return self.order.index(i)
+
     def project_(self):
         """Replaces every X by the Q factor (positive diagonal of R) of its QR decomposition."""
         if self._plan is not None:
@@ -1349,7 +1411,7 @@ class StiefelPlan:
 
     def status_of(self, i: int) -> torch.Tensor:
         """The status word of factor i as a one-element device view (no synchronisation)."""
-        k = self.order.index(i)
+        k = self.slot_of(i)
         return self.status[k:k + 1]
 
     def failed(self) -> List[int]:
@@ -1361,7 +1423,8 @@ class StiefelPlan:
 def stiefel_step(factors: Sequence, lr: float, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False) -> StiefelPlan:
     """One Riemannian SGD step on a list of (X, G, M) (see `StiefelPlan`), in place; returns the plan, whose `failed()`
-    names the factors that were left untouched.  Callers that step repeatedly keep a `StiefelPlan`."""
+    names the factors that were left untouched.  Callers that step repeatedly keep a `StiefelPlan` (and use its
+    `adam_step` for Riemannian Adam)."""
     plan = StiefelPlan(factors)
     plan.step(lr, momentum, dampening, weight_decay, nesterov)
     return plan

@@ -254,6 +254,21 @@ int tadmm_stiefel_plan_create(tadmm_handle h, int n, const tadmm_stiefel_desc* d
                               size_t workspace_bytes, void* stream, tadmm_stiefel_plan* out);
 int tadmm_stiefel_step(tadmm_stiefel_plan p, double lr, double momentum, double dampening, double weight_decay,
                        int nesterov, int32_t* status_dev, void* stream);
+/* Riemannian Adam on the same plan (geoopt.optim.RiemannianAdam on Stiefel factors), one launch.  M of the descriptor is
+ * exp_avg; v_dev (second moment, ONE float32 per factor), vmax_dev (its running maximum, amsgrad only, else may be NULL)
+ * and step_dev (int32 step counter per factor) hold n entries each, in the plan's (descriptor) order:
+ *   t' = t + 1;   g = G + weight_decay X;   r = g - X sym(X^T g);   s = sum_ij r_ij^2   (fp64, fixed summation order)
+ *   M' = beta1 M + (1 - beta1) r;   v' = beta2 v + (1 - beta2) s;   u = amsgrad ? max(vmax, v') : v'
+ *   X <- Q factor (positive diagonal of R) of X - lr / ((1 - beta1^t') (sqrt(u / (1 - beta2^t')) + eps)) M'
+ *   M <- M' - X sym(X^T M');   v <- v', vmax <- u (amsgrad), t <- t'
+ * The bias corrections are computed on the device from the factor's own counter; the host never reads it.  G == NULL
+ * skips the factor: nothing of it is written.  A factor that fails (the rule above, or a non-finite second moment)
+ * keeps X, M, v, vmax and t and gets status_dev[i] = 1.  Copies nothing, synchronises nothing.
+ * Returns TADMM_ERR_INVALID and launches nothing for a NULL plan, beta1 or beta2 outside [0, 1), eps < 0, lr < 0,
+ * weight_decay < 0, a NULL v_dev or step_dev, amsgrad with a NULL vmax_dev, and a plan in which some factor has no M. */
+int tadmm_stiefel_adam_step(tadmm_stiefel_plan p, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, int amsgrad, float* v_dev, float* vmax_dev, int32_t* step_dev,
+                            int32_t* status_dev, void* stream);
 int tadmm_stiefel_project(tadmm_stiefel_plan p, int32_t* status_dev, void* stream);
 int tadmm_stiefel_plan_destroy(tadmm_stiefel_plan p);
 

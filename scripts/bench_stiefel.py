@@ -10,7 +10,11 @@ Timing: HIP events around ITERS calls after a warm-up, ROUNDS rounds with the or
 median and the spread (min..max) of the rounds are reported.  `ahead` is true when the native median is below the composed
 route's fastest round.
 
-    python scripts/bench_stiefel.py [--quick] [--json OUT]
+`--adam` measures one Riemannian Adam step (`ops.StiefelPlan.adam_step`, betas (0.9, 0.999), eps 1e-8) over the same 60
+factors instead: native (one launch of the Adam instantiation), composed (`native=False`), and the native SGD step with
+momentum 0.9 in the same process as the yardstick; `adam_minus_sgd_ms` is the difference of the two native medians.
+
+    python scripts/bench_stiefel.py [--adam] [--quick] [--json OUT]
 """
 import argparse
 import json
@@ -52,14 +56,50 @@ def factors(shapes, seed):
     return fac
 
 
+def adam_state(n):
+    return (torch.zeros(n, device=DEV), torch.zeros(n, device=DEV), torch.zeros(n, dtype=torch.int32, device=DEV))
+
+
+def main_adam(a, shapes, iters, rounds):
+    native = ops.StiefelPlan(factors(shapes, 0))
+    composed = ops.StiefelPlan(factors(shapes, 0), native=False)
+    sgd = ops.StiefelPlan(factors(shapes, 0))
+    sn, sc = adam_state(len(shapes)), adam_state(len(shapes))
+    hyper = (0.01, (0.9, 0.999), 1e-8, 0.0, False)
+    paths = {"native": lambda: native.adam_step(*hyper, *sn), "composed": lambda: composed.adam_step(*hyper, *sc),
+             "native_sgd": lambda: sgd.step(0.01, 0.9)}
+    t = measure(paths, iters, rounds)
+    assert native.failed() == [] and composed.failed() == [] and sgd.failed() == []
+    assert torch.equal(sn[2], sc[2])                                      # both routes counted the same steps
+    worst = max(float((x[0] - y[0]).abs().max()) for x, y in zip(native.factors, composed.factors))
+    # the project's rule: ahead by more than the min..max spread of both
+    gap = t["composed"][0] - t["native"][0]
+    spread = (t["native"][2] - t["native"][1]) + (t["composed"][2] - t["composed"][1])
+    row = {"table": KEY, "factors": len(shapes), "optimiser": "adam", "native_ms": t["native"], "composed_ms": t["composed"],
+           "native_sgd_ms": t["native_sgd"], "adam_minus_sgd_ms": t["native"][0] - t["native_sgd"][0],
+           "ahead": gap > spread, "max_abs_difference_after_the_timed_steps": worst}
+    print(f"{len(shapes)} factors of {KEY}, one Adam step (betas (0.9, 0.999)); SGD with momentum 0.9 as the yardstick")
+    for n in ("native", "composed", "native_sgd"):
+        med, lo, hi = t[n]
+        print(f"  {n:10s} {med:9.4f} ms  ({lo:.4f}..{hi:.4f})")
+    print(f"  native Adam - native SGD: {row['adam_minus_sgd_ms']:.4f} ms   ahead of composed by more than both spreads: "
+          f"{row['ahead']}   max |X_native - X_composed| after the timed steps: {worst:.3e}")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(row, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="fewer iterations and rounds")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--adam", action="store_true", help="the Adam step, with the native SGD step as the yardstick")
     a = ap.parse_args()
     iters, rounds = (5, 3) if a.quick else (20, 5)
     shapes = factor_shapes()
     assert all(ops.stiefel_fits(n, p) for n, p in shapes)
+    if a.adam:
+        return main_adam(a, shapes, iters, rounds)
     native = ops.StiefelPlan(factors(shapes, 0))
     composed = ops.StiefelPlan(factors(shapes, 0), native=False)
     paths = {"native": lambda: native.step(0.01, 0.9), "composed": lambda: composed.step(0.01, 0.9)}
