@@ -96,6 +96,20 @@ class StiefelDesc(C.Structure):
     ]
 
 
+TTM_MAX_D = 4
+
+
+class TtmDesc(C.Structure):
+    _fields_ = [
+        ("cores", C.c_void_p * TTM_MAX_D), ("dcores", C.c_void_p * TTM_MAX_D),
+        ("order", C.c_void_p * TTM_MAX_D), ("offsets", C.c_void_p * TTM_MAX_D),
+        ("index", C.c_void_p), ("dY", C.c_void_p), ("Y", C.c_void_p), ("bad_count", C.c_void_p),
+        ("B", C.c_int64), ("d", C.c_int32), ("index_dtype", C.c_int32),
+        ("n", C.c_int32 * TTM_MAX_D), ("m", C.c_int32 * TTM_MAX_D), ("r", C.c_int32 * (TTM_MAX_D + 1)),
+        ("reserved", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -200,6 +214,10 @@ ABI = {
     "tadmm_wgrad_desc_bytes": (C.c_int, []),
     "tadmm_wgrad_workspace_bytes": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "tadmm_wgrad": (C.c_int, [C.c_void_p, C.POINTER(WgradDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tadmm_ttm_desc_bytes": (C.c_int, []),
+    "tadmm_ttm_gather_fits": (C.c_int, [C.POINTER(TtmDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "tadmm_ttm_gather_fwd": (C.c_int, [C.c_void_p, C.POINTER(TtmDesc), C.c_void_p]),
+    "tadmm_ttm_gather_bwd": (C.c_int, [C.c_void_p, C.POINTER(TtmDesc), C.c_void_p]),
     "tadmm_core_conv_desc_bytes": (C.c_int, []),
     "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
     "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
@@ -283,6 +301,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_stiefel_desc layout mismatch")
         if lib.tadmm_wgrad_desc_bytes() != C.sizeof(WgradDesc):
             raise TadmmLibraryError(f"{path}: tadmm_wgrad_desc layout mismatch")
+        if lib.tadmm_ttm_desc_bytes() != C.sizeof(TtmDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_ttm_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         _lib = lib

@@ -620,3 +620,81 @@ def conv_chain_routed(layer, x: torch.Tensor, w_in: torch.Tensor, w_out: torch.T
     cache = None if training else layer.__dict__.setdefault("_fused_cache", {})
     return conv_chain(x, w_in, core, w_out, layer.bias, layer.stride, layer.padding, layer.dilation, cache=cache)
 
+
+# ---------------------------------------------------------------------------------------------------------------
+# Factorised embedding lookup (csrc/ttm_gather.hip): the gathered TT-matrix chain of TTMEmbedding.py:96-129,
+# TTEmbedding.py:91-118 and SVDEmbedding.py:34-42 as one launch, its core gradients as one launch per core.
+# ---------------------------------------------------------------------------------------------------------------
+class _TtmGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, index, counter, *cores):
+        cs = [c.detach() if c.is_contiguous() else c.detach().contiguous() for c in cores]
+        y = ops.ttm_gather(cs, index, counter)
+        ctx.save_for_backward(index, *cs)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        index, *cs = ctx.saved_tensors
+        grads = ops.ttm_gather_bwd(cs, index, g if g.dtype == torch.float32 else g.float(), ctx.needs_input_grad[2:])
+        return (None, None, *grads)
+
+
+def ttm_embedding_composed(cores, index: torch.Tensor, counter: torch.Tensor = None) -> torch.Tensor:
+    """The lookup as the reference composes it (index split by div / fmod, the selected slices of every core, one batched
+    product per mode), as torch ops under autograd, in the cores' dtype: the route of shapes `ops.ttm_gather_fits`
+    refuses, and the baseline of scripts/bench_embeddings.py.  Bad indices give zero rows and count like the launch."""
+    n, m, r = ops.ttm_core_shapes(cores)
+    flat = index.reshape(-1)
+    total = 1
+    for v in n:
+        total *= v
+    valid = (flat >= 0) & (flat < total)
+    if counter is not None:
+        counter += (~valid).sum().to(counter.dtype)
+    B = flat.numel()
+    res = None
+    for k, ik in enumerate(ops.ttm_index_split(flat, n)):
+        # advanced indexing, not index_select: its backward is torch's sort-based accumulation (tokens of a slice added in
+        # a fixed order), so this route's gradients are reproducible from run to run like the launch's
+        sl = cores[k][:, ik].permute(1, 0, 2, 3)                                # B x r_{k-1} x m_k x r_k
+        if res is None:
+            res = sl.reshape(B, m[0], r[1])
+        else:
+            res = torch.bmm(res.reshape(B, -1, r[k]), sl.reshape(B, r[k], m[k] * r[k + 1]))
+    res = res.reshape(B, -1) * valid.to(res.dtype).unsqueeze(1)
+    return res.reshape(tuple(index.shape) + (res.shape[1],))
+
+
+def ttm_embedding(cores, index: torch.Tensor, counter: torch.Tensor = None, route: str = None) -> torch.Tensor:
+    """Rows of the TT-matrix the cores (r_{k-1}, n_k, m_k, r_k), r_0 = 1, stand for: `index` (int32 / int64, any shape or
+    stride, values in [0, n_1 ... n_d)) -> index.shape + (m_1 ... m_d r_d,), float32, differentiable in the cores.
+    An index outside the range gives a zero row, no gradient, and adds 1 to `counter` (one int32 on the device, optional);
+    nothing synchronises.  Shapes the launch takes (`ops.ttm_gather_fits`: d <= 4, one token's products within the LDS
+    of a CU) run `tadmm_ttm_gather_fwd` / `_bwd` where the measured rule `ops.ttm_gather_pays` says they are ahead
+    (always without gradients); the others the composed device route.  `route`: None (by that rule), "native" (the
+    launches; shapes they do not take raise) or "composed".  ValueError for no cores and r_0 != 1, TypeError for an
+    index that is not of an integer dtype; both before anything is launched."""
+    if route not in (None, "native", "composed"):
+        raise ValueError(f"ttm_embedding: route is None, 'native' or 'composed' (got {route!r})")
+    cores = list(cores)
+    n, m, r = ops.ttm_core_shapes(cores)
+    if not isinstance(index, torch.Tensor) or index.dtype.is_floating_point or index.dtype.is_complex \
+            or index.dtype == torch.bool:
+        raise TypeError(f"ttm_embedding: index must be an integer tensor (got {getattr(index, 'dtype', type(index))})")
+    if not cores[0].is_cuda:
+        raise TadmmError(-1, "ttm_embedding: the cores must live on the HIP device (no CPU fallback)")
+    if index.dtype not in (torch.int32, torch.int64):
+        index = index.to(torch.int64)
+    if index.device != cores[0].device:
+        index = index.to(cores[0].device)
+    if route is None:
+        grad = torch.is_grad_enabled() and any(c.requires_grad for c in cores)
+        native = index.numel() > 0 and all(c.dtype == torch.float32 for c in cores) and ops.ttm_gather_fits(n, m, r) \
+            and ops.ttm_gather_pays(n, m, r, index.numel(), grad)
+    else:
+        native = route == "native"
+    if not native:
+        return ttm_embedding_composed(cores, index, counter)
+    y = _TtmGather.apply(index, counter, *cores)
+    return y.reshape(tuple(index.shape) + (y.shape[1],))

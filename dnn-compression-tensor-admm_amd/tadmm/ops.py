@@ -1435,3 +1435,187 @@ def stiefel_project_(*xs: torch.Tensor) -> StiefelPlan:
     plan = StiefelPlan([(x, None, None) for x in xs])
     plan.project_()
     return plan
+
+
+# ------------------------------------------------------------------ gathered TT-matrix chain (csrc/ttm_gather.hip)
+TTM_MAX_D = _cabi.TTM_MAX_D
+TTM_LDS_BYTES = 160 * 1024
+
+
+def ttm_core_shapes(cores: Sequence[torch.Tensor]):
+    """(n, m, r) of a chain of cores (r_k, n_k, m_k, r_{k+1}).  Host only; ValueError for an empty chain, a core that is
+    not 4-D, ranks that do not chain, or r_0 != 1."""
+    if len(cores) == 0:
+        raise ValueError("ttm_gather: at least one core (d = 0 has no index to split)")
+    n, m, r = [], [], []
+    for k, c in enumerate(cores):
+        if c.dim() != 4:
+            raise ValueError(f"ttm_gather: core {k} must be (r, n, m, r') (got shape {tuple(c.shape)})")
+        if k and int(c.shape[0]) != r[-1]:
+            raise ValueError(f"ttm_gather: core {k} has left rank {int(c.shape[0])}, "
+                             f"core {k - 1} has right rank {r[-1]}")
+        if not k:
+            r.append(int(c.shape[0]))
+        n.append(int(c.shape[1]))
+        m.append(int(c.shape[2]))
+        r.append(int(c.shape[3]))
+    if r[0] != 1:
+        raise ValueError(f"ttm_gather: r_0 must be 1 (got {r[0]})")
+    return n, m, r
+
+
+def _ttm_desc(n, m, r) -> _cabi.TtmDesc:
+    d = len(n)
+    if d == 0:
+        raise ValueError("ttm_gather: at least one mode (d = 0 has no index to split)")
+    if len(m) != d or len(r) != d + 1:
+        raise ValueError(f"ttm_gather: {d} modes want {d} output sizes and {d + 1} ranks (got {len(m)}, {len(r)})")
+    if int(r[0]) != 1:
+        raise ValueError(f"ttm_gather: r_0 must be 1 (got {r[0]})")
+    if d > TTM_MAX_D:
+        raise ValueError(f"ttm_gather: the launch takes at most {TTM_MAX_D} modes (got {d})")
+    if min(list(n) + list(m) + list(r)) <= 0:
+        raise ValueError("ttm_gather: every mode size and rank must be positive")
+    desc = _cabi.TtmDesc()
+    desc.d = d
+    for k in range(d):
+        desc.n[k], desc.m[k], desc.r[k] = int(n[k]), int(m[k]), int(r[k])
+    desc.r[d] = int(r[d])
+    return desc
+
+
+def ttm_gather_plan(n, m, r):
+    """(fits, LDS bytes of the larger launch, tokens per forward workgroup) for mode sizes n, output sizes m and ranks
+    r: `tadmm_ttm_gather_fits`, a pure function of the shapes.  Host only.  ValueError for d = 0, d > 4 and r_0 != 1.  A
+    core of 2^31 elements or a running product beyond 2^30 floats does not fit and is not sized: (False, 0, 0)."""
+    desc = _ttm_desc(n, m, r)
+    nbytes, tile = C.c_size_t(), C.c_int()
+    rc = _cabi.load().tadmm_ttm_gather_fits(C.byref(desc), C.byref(nbytes), C.byref(tile))
+    if rc < 0:
+        raise TadmmError(rc, "tadmm_ttm_gather_fits: invalid descriptor")
+    return bool(rc), int(nbytes.value), int(tile.value)
+
+
+def ttm_gather_fits(n, m, r) -> bool:
+    """True when the one-launch gather takes the shape: at most 4 modes and the products of one token within the 160 KiB
+    of LDS of a CU, forward and backward.  False sends `functional.ttm_embedding` down the composed device route.
+    ValueError for d = 0 and r_0 != 1.  Pure host logic."""
+    if len(n) > TTM_MAX_D:
+        if len(n) and int(r[0]) != 1:
+            raise ValueError(f"ttm_gather: r_0 must be 1 (got {r[0]})")
+        return False
+    return ttm_gather_plan(n, m, r)[0]
+
+
+def ttm_index_split(index: torch.Tensor, n: Sequence[int]) -> List[torch.Tensor]:
+    """Mode indices (i_1 .. i_d), i_1 slowest, of a flat integer index tensor; indices outside [0, prod(n)) are clamped
+    into the range first (callers mask them).  Torch ops on the tensor's device, no synchronisation."""
+    total = 1
+    for v in n:
+        total *= int(v)
+    idx = index.reshape(-1).to(torch.int64).clamp(0, total - 1)
+    out, stride = [], total
+    for v in n:
+        stride //= int(v)
+        out.append(torch.remainder(torch.div(idx, stride, rounding_mode="floor"), int(v)))
+    return out
+
+
+def ttm_groups(index: torch.Tensor, n: Sequence[int]):
+    """For every mode k: (order_k, offsets_k), the tokens grouped by i_k by a stable sort (ascending token order inside
+    a group) and the n_k + 1 group offsets.  Sizes depend on n_k alone, so nothing synchronises."""
+    out = []
+    for k, ik in enumerate(ttm_index_split(index, n)):
+        keys, order = torch.sort(ik, stable=True)
+        edges = torch.arange(int(n[k]) + 1, device=ik.device, dtype=torch.int64)
+        out.append((order, torch.searchsorted(keys, edges)))
+    return out
+
+
+def _ttm_operands(cores, index, who):
+    n, m, r = ttm_core_shapes(cores)
+    desc = _ttm_desc(n, m, r)
+    if not isinstance(index, torch.Tensor) or index.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{who}: index must be an int32 or int64 tensor (got {getattr(index, 'dtype', type(index))})")
+    dev = cores[0].device
+    for k, c in enumerate(cores):
+        if not c.is_cuda or c.device != dev:
+            raise TadmmError(-1, f"{who}: core {k} must live on one HIP device; there is no CPU path")
+        if c.dtype != torch.float32 or not c.is_contiguous():
+            raise TadmmError(-1, f"{who}: core {k} must be contiguous float32")
+    if index.device != dev:
+        raise TadmmError(-1, f"{who}: index on {index.device}, cores on {dev}")
+    flat = index.reshape(-1)
+    flat = flat if flat.is_contiguous() else flat.contiguous()
+    for k, c in enumerate(cores):
+        desc.cores[k] = c.data_ptr()
+    desc.index, desc.index_dtype, desc.B = flat.data_ptr(), int(flat.dtype == torch.int64), flat.numel()
+    row = r[-1]
+    for v in m:
+        row *= v
+    return desc, flat, row, dev
+
+
+def ttm_gather(cores: Sequence[torch.Tensor], index: torch.Tensor, counter: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, m_1 ... m_d r_d) float32 rows of the gathered TT-matrix chain for the B indices of `index` (any shape, int32
+    or int64), in one launch (`tadmm_ttm_gather_fwd`).  An index outside [0, prod(n)) gives a zero row and adds 1 to
+    `counter` (one int32 on the device; a fresh zero when None).  Raises for shapes `ttm_gather_fits` refuses."""
+    desc, flat, row, dev = _ttm_operands(cores, index, "ttm_gather")
+    B = flat.numel()
+    if out is None:
+        out = torch.empty(B, row, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (B, row) or not out.is_contiguous():
+        raise TadmmError(-1, f"ttm_gather: out must be a contiguous float32 ({B}, {row}) tensor on {dev}")
+    if counter is None:
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif counter.dtype != torch.int32 or counter.device != dev or counter.numel() != 1:
+        raise TadmmError(-1, "ttm_gather: counter must be one int32 on the cores' device")
+    desc.Y, desc.bad_count = out.data_ptr(), counter.data_ptr()
+    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h.check(h.lib.tadmm_ttm_gather_fwd(h.ptr, C.byref(desc), _stream(dev)))
+    return out
+
+
+def ttm_gather_bwd(cores: Sequence[torch.Tensor], index: torch.Tensor, dy: torch.Tensor,
+                   needs: Optional[Sequence[bool]] = None) -> List[Optional[torch.Tensor]]:
+    """Gradients of sum(ttm_gather(cores, index) * dy) with respect to every core with needs[k] (all when None), one
+    launch per core (`tadmm_ttm_gather_bwd`): every slice is written by one workgroup that adds its tokens in
+    ascending order, so the result is bitwise reproducible and slices no token selects are exactly zero."""
+    desc, flat, row, dev = _ttm_operands(cores, index, "ttm_gather_bwd")
+    B = flat.numel()
+    if dy.dtype != torch.float32 or dy.device != dev or dy.numel() != B * row:
+        raise TadmmError(-1, f"ttm_gather_bwd: dy must hold ({B}, {row}) float32 values on {dev}")
+    dy = dy.reshape(B, row)
+    dy = dy if dy.is_contiguous() else dy.contiguous()
+    needs = [True] * len(cores) if needs is None else list(needs)
+    n = [int(c.shape[1]) for c in cores]
+    groups = ttm_groups(flat, n)
+    grads: List[Optional[torch.Tensor]] = [None] * len(cores)
+    for k, c in enumerate(cores):
+        if not needs[k]:
+            continue
+        grads[k] = torch.empty_like(c)
+        desc.dcores[k] = grads[k].data_ptr()
+        desc.order[k], desc.offsets[k] = groups[k][0].data_ptr(), groups[k][1].data_ptr()
+    desc.dY = dy.data_ptr()
+    if any(needs):
+        h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+        h.check(h.lib.tadmm_ttm_gather_bwd(h.ptr, C.byref(desc), _stream(dev)))
+    return grads
+
+
+TTM_GRAD_MAX_TOKENS = 512
+
+
+def ttm_gather_pays(n, m, r, tokens: int, grad: bool = False) -> bool:
+    """True when `functional.ttm_embedding` sends a shape the launch takes to the launch and not to the composed device
+    route.  A pure function of the shapes, the token count and whether core gradients will be asked for.  Measured
+    (scripts/bench_embeddings.py): without gradients the launch is ahead of or level with the
+    composed route at every shape and token count of the table (up to 4.4x), so inference always takes it.  With
+    gradients the one-workgroup-per-slice backward is behind the composed route for chains of two and more modes (0.23x
+    at the TT-matrix table) and for one mode at 4096 tokens (0.94x); it is ahead for one mode at 512 tokens (1.30x).
+    Token counts between the two were not measured and stay on the composed route."""
+    if not grad:
+        return True
+    return len(n) == 1 and tokens <= TTM_GRAD_MAX_TOKENS

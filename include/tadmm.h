@@ -495,6 +495,46 @@ int tadmm_core_conv_wgrad_workspace_bytes(const tadmm_core_conv_desc* d, size_t*
 int tadmm_core_conv_wgrad(tadmm_handle h, const tadmm_core_conv_desc* d, float* dW, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- gathered TT-matrix chain: the lookup of the factorised embeddings (csrc/ttm_gather.hip) ------------------------
+ * TTMEmbedding.py:96-129, TTEmbedding.py:91-118 and SVDEmbedding.py:34-42 as one launch.  Cores G_j of shape
+ * (r[j], n[j], m[j], r[j+1]), j < d, float32 contiguous, r[0] == 1.  Token t carries index[t] in [0, n[0] ... n[d-1]),
+ * split into (i_0 .. i_{d-1}) with i_0 slowest; with S_j = G_j[:, i_j, :, :]
+ *   Y[t][j_0 .. j_{d-1}, b] = sum_{a_1 .. a_{d-1}} S_0[0, j_0, a_1] S_1[a_1, j_1, a_2] ... S_{d-1}[a_{d-1}, j_{d-1}, b],
+ * Y (B, m[0] ... m[d-1] * r[d]) float32 contiguous, j_0 slowest.  The running product of a token stays in LDS; every row
+ * of Y is written once.  An index outside the range is never used as an address: its row of Y is zeros, it adds
+ * nothing to the gradients, and the forward adds 1 to *bad_count (int32, device; the caller zeroes it when it likes).
+ * tadmm_ttm_gather_bwd writes dcores[j] (shape of core j) = the gradient of sum(Y * dY) for every j with dcores[j] !=
+ * NULL, one launch per core.  order[j] (B int64 token positions, grouped by i_j, ascending inside a group: a stable sort)
+ * and offsets[j] (n[j] + 1 int64: group i is order[j][offsets[j][i] .. offsets[j][i+1])) come from the caller; bad
+ * tokens may sit in any group.  Workgroup i owns slice i of dcores[j], writes all of it (zeros where no token selects
+ * it) and adds its tokens in the order given: no atomics, no memset, bitwise reproducible.
+ * tadmm_ttm_gather_fits is host only and reads d, n, m, r alone: 1 when the launches take the shape (a token's products
+ * fit the 160 KiB of LDS of a CU, forward and backward), 0 when not, TADMM_ERR_INVALID for d < 1, d > 4, r[0] != 1 or a
+ * size <= 0.  *lds_bytes (nullable): dynamic LDS of the larger launch; *tile (nullable): tokens per forward workgroup;
+ * both 0 for a core of 2^31 elements or more or a product of one token beyond 2^30 floats (0 is returned, unsized).
+ * The two launches return TADMM_ERR_UNSUPPORTED where _fits returns 0; B == 0 succeeds (the backward writes zeros). */
+#define TADMM_TTM_MAX_D 4
+typedef struct {
+  const float* cores[TADMM_TTM_MAX_D];
+  float* dcores[TADMM_TTM_MAX_D];             /* backward only; NULL: core skipped */
+  const int64_t* order[TADMM_TTM_MAX_D];      /* backward only */
+  const int64_t* offsets[TADMM_TTM_MAX_D];    /* backward only */
+  const void* index;                          /* B indices, int32 or int64, contiguous */
+  const float* dY;                            /* backward only */
+  float* Y;                                   /* forward only */
+  int32_t* bad_count;                         /* forward only */
+  int64_t B;
+  int32_t d;
+  int32_t index_dtype;                        /* 0: int32, 1: int64 */
+  int32_t n[TADMM_TTM_MAX_D], m[TADMM_TTM_MAX_D], r[TADMM_TTM_MAX_D + 1];
+  int32_t reserved;
+} tadmm_ttm_desc;
+/* sizeof(tadmm_ttm_desc) as the library was built */
+int tadmm_ttm_desc_bytes(void);
+int tadmm_ttm_gather_fits(const tadmm_ttm_desc* d, size_t* lds_bytes, int* tile);
+int tadmm_ttm_gather_fwd(tadmm_handle h, const tadmm_ttm_desc* d, void* stream);
+int tadmm_ttm_gather_bwd(tadmm_handle h, const tadmm_ttm_desc* d, void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
