@@ -8,6 +8,7 @@ TTConv.py:133-147, TKConv.py:210-214 and TKLinear.py:66-71.
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 
 from . import ops
 from ._cabi import TadmmError
@@ -170,6 +171,22 @@ def fused_rank_ok(r: int) -> bool:
     return 0 < r <= 256
 
 
+def _chain_planes(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor = None, given=None, transpose: bool = False):
+    """(planes, memo) of one chain launch on activations x: the planes of a single map `w_in`, or the pair of the fused
+    chain through `w_in` then `w_out` (middle rank padded to 64); with `transpose` those of the data gradient, which runs
+    the same kernels on the transposed factors in the opposite order.  `given`: prebuilt planes (the layers' inference
+    caches), passed through.  Planes packed here live for this call only, so memo is False: they stay out of the launch
+    memo (`ops._CHAIN_MEMO`)."""
+    if given is not None:
+        return given, True
+    n = _nplanes(x)
+    if w_out is None:
+        return planes_of(w_in, n, transpose=transpose, like=x), False
+    if transpose:
+        return (planes_of(w_out, n, pad_rows=64, transpose=True), planes_of(w_in, n, pad_cols=64, transpose=True)), False
+    return (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x)), False
+
+
 class _ChainSingle(torch.autograd.Function):
     """y = x W^T + bias on token rows (T, K) or, in place, on channels-first images (B, K, H, W) -> (B, N, H, W)."""
 
@@ -179,10 +196,8 @@ class _ChainSingle(torch.autograd.Function):
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
         _inference_only(x)
         image = x.dim() == 4
-        fresh = wp is None                          # planes packed for this call only: keep them out of the launch memo
-        if fresh:
-            wp = planes_of(w, _nplanes(x))
-        y = ops.chain_single(x, wp, bias, w.shape[0], entry=entry, image_out=image, memo=not fresh)
+        wp, memo = _chain_planes(x, w, given=wp)
+        y = ops.chain_single(x, wp, bias, w.shape[0], entry=entry, image_out=image, memo=memo)
         ctx.save_for_backward(x, w)
         ctx.entry, ctx.has_bias, ctx.image = entry, bias is not None, image
         return y
@@ -193,8 +208,8 @@ class _ChainSingle(torch.autograd.Function):
         g = g.contiguous()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:                 # dX = dY W : the same kernel with the transposed weight
-            gx = ops.chain_single(g, planes_of(w, _nplanes(g), transpose=True), None, w.shape[1], entry=ctx.entry,
-                                  image_out=ctx.image, memo=False)
+            wp, memo = _chain_planes(g, w, transpose=True)
+            gx = ops.chain_single(g, wp, None, w.shape[1], entry=ctx.entry, image_out=ctx.image, memo=memo)
         if ctx.needs_input_grad[1]:                 # dW = dY^T X  (N x K) over tokens / pixels, operands in place
             gw = ops.wgrad(g, x)
         if ctx.has_bias and ctx.needs_input_grad[2]:
@@ -208,50 +223,50 @@ def pointwise(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor = None, entry
     (the 1x1 convolutions of TKConv.py:93-98 and the core chains of TTConv.py:131-151).  Differentiable.  `planes`:
     prebuilt `planes_of(w, ...)` (inference caches)."""
     if not _needs_grad(x, w, bias):                   # inference: straight to the C ABI, no autograd node
-        fresh = planes is None
-        if fresh:
-            planes = planes_of(w, _nplanes(x), like=x)
+        planes, memo = _chain_planes(x, w, given=planes)
         if x.dim() == 4:
-            return ops.chain_single(x, planes, bias, w.shape[0], entry=entry, image_out=True, memo=not fresh)
+            return ops.chain_single(x, planes, bias, w.shape[0], entry=entry, image_out=True, memo=memo)
         lead = x.shape[:-1]
         return ops.chain_single(x.reshape(-1, x.shape[-1]), planes, bias, w.shape[0], entry=entry,
-                                memo=not fresh).reshape(*lead, w.shape[0])
+                                memo=memo).reshape(*lead, w.shape[0])
     if x.dim() == 4:
         return _ChainSingle.apply(x.contiguous(), w, bias, entry, planes)
     lead = x.shape[:-1]
     return _ChainSingle.apply(x.reshape(-1, x.shape[-1]), w, bias, entry, planes).reshape(*lead, w.shape[0])
 
 
-def _saved_route(ctx, x, w_in, w_out, save, image: bool) -> bool:
-    """True when this step of a fused chain stores its middle-rank intermediates (`save`: None = `ops.chain_train_pays`
-    decides, True / False = the caller does).  With no factor gradient wanted there is nothing to save either way."""
-    factor_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-    if not factor_grad or save is False:
-        return False
-    return True if save else ops.chain_train_pays(x, w_in.shape[0], w_in.shape[1], w_out.shape[0], image)
+# What tells the fused chain on token rows (T, K) from the one on NCHW images, keyed on x.dim() == 4: the `ops` wrappers
+# (looked up at call time), the prefix of the entry names, how the recomputing `ops.chain_single` launches are addressed
+# and the dims the bias gradient sums over.
+_CHAIN_LAYOUTS = {
+    False: ("chain_fused", "chain_fused_save", "tadmm_ttlinear_", {}, 0),
+    True: ("svd_conv", "svd_conv_save", "tadmm_svdconv_", dict(entry="tadmm_tucker_1x1", image_out=True), (0, 2, 3)),
+}
 
 
-class _ChainFused(torch.autograd.Function):
-    """y = (x Win^T) Wout^T + bias in one launch; Win (R, K), Wout (N, R), R <= 256.  On the saved route
-    (`_saved_route`) the forward launch also stores H = x Win^T and the data-gradient launch dH = dY Wout, and the two
-    weight gradients read them: four launches a step and no recomputation, for T x R elements (H) kept alive from
-    forward to backward that the other route does not keep."""
+class _FusedChain(torch.autograd.Function):
+    """y = Wout (Win x) + bias in one launch, per token of rows (T, K) or per pixel of an NCHW image (`_CHAIN_LAYOUTS`);
+    Win (R, K), Wout (N, R), R <= 256.  On the saved route (`save`: None = `ops.chain_train_pays` decides, True / False =
+    the caller does; with no factor gradient wanted there is nothing to save either way) the forward launch also stores
+    H = Win x and the data-gradient launch dH = Wout^T dY, and the two weight gradients read them: four launches a step
+    and no recomputation, for T x R elements (H) kept alive from forward to backward that the other route does not keep."""
 
     @staticmethod
     def forward(ctx, x, w_in, w_out, bias, planes, save):
         if not x.is_cuda:
             raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
         _inference_only(x)
-        n = _nplanes(x)
-        fresh = planes is None
-        if fresh:
-            planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
-        ctx.saved_route = _saved_route(ctx, x, w_in, w_out, save, False)
+        image = x.dim() == 4
+        plain, saving = _CHAIN_LAYOUTS[image][:2]
+        (p_in, p_out), memo = _chain_planes(x, w_in, w_out, planes)
+        factor_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        ctx.saved_route = bool(factor_grad and save is not False and (
+            save or ops.chain_train_pays(x, w_in.shape[0], w_in.shape[1], w_out.shape[0], image)))
         h = None
         if ctx.saved_route and ctx.needs_input_grad[2]:              # H feeds dWout alone
-            y, h = ops.chain_fused_save(x, planes[0], planes[1], bias, w_out.shape[0], w_in.shape[0])
+            y, h = getattr(ops, saving)(x, p_in, p_out, bias, w_out.shape[0], w_in.shape[0])
         else:
-            y = ops.chain_fused(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
+            y = getattr(ops, plain)(x, p_in, p_out, bias, w_out.shape[0], memo=memo)
         ctx.save_for_backward(x, w_in, w_out, h)
         ctx.has_bias = bias is not None
         return y
@@ -259,42 +274,31 @@ class _ChainFused(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w_in, w_out, h = ctx.saved_tensors
+        plain, saving, prefix, single, bias_dims = _CHAIN_LAYOUTS[x.dim() == 4]
+        need = ctx.needs_input_grad
         g = g.contiguous()
-        n = _nplanes(g)
-        gx = gwi = gwo = gb = None
-        if ctx.saved_route:
-            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:  # dX and dH = dY Wout from one launch
-                gx, gr = ops.chain_fused_save(g, planes_of(w_out, n, pad_rows=64, transpose=True),
-                                              planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
-                                              w_in.shape[0], entry="tadmm_ttlinear_bwd_save")
-                gwi = ops.wgrad(gr, x)
-                del gr
-            elif ctx.needs_input_grad[0]:
-                gx = ops.chain_fused(g, planes_of(w_out, n, pad_rows=64, transpose=True),
-                                     planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
-                                     entry="tadmm_ttlinear_bwd", memo=False)
-            elif ctx.needs_input_grad[1]:           # no dX wanted: product 1 alone
-                gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], memo=False)
-                gwi = ops.wgrad(gr, x)
-                del gr
-            if ctx.needs_input_grad[2]:             # dWout = dY^T H, H from the forward launch
-                gwo = ops.wgrad(g, h)
-            if ctx.has_bias and ctx.needs_input_grad[3]:
-                gb = g.sum(0)
-            return gx, gwi, gwo, gb, None, None
-        if ctx.needs_input_grad[0]:                 # dX = (dY Wout) Win: the fused kernel on the transposed factors
-            gx = ops.chain_fused(g, planes_of(w_out, n, pad_rows=64, transpose=True),
-                                 planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
-                                 entry="tadmm_ttlinear_bwd", memo=False)
-        if ctx.needs_input_grad[1]:                 # dWin = (dY Wout)^T X
-            gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], memo=False)
-            gwi = ops.wgrad(gr, x)
-            del gr
-        if ctx.needs_input_grad[2]:                 # dWout = dY^T (X Win^T)
-            h = ops.chain_single(x, planes_of(w_in, _nplanes(x)), None, w_in.shape[0], memo=False)
-            gwo = ops.wgrad(g, h)
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            gb = g.sum(0)
+        gx = gr = gwi = gwo = gb = None
+        if need[0]:                                 # dX = Win^T (Wout^T dY): the fused kernel on the transposed factors
+            (p_out, p_in), memo = _chain_planes(g, w_in, w_out, transpose=True)
+            if ctx.saved_route and need[1]:         # ... and dH = Wout^T dY from the same launch
+                gx, gr = getattr(ops, saving)(g, p_out, p_in, None, w_in.shape[1], w_in.shape[0], entry=prefix + "bwd_save")
+            else:
+                gx = getattr(ops, plain)(g, p_out, p_in, None, w_in.shape[1], entry=prefix + "bwd", memo=memo)
+        # (the weight gradients are float32; `.to` is the identity for float32 factors, and autograd would cast a
+        # mismatched gradient to the factor's dtype anyway)
+        if need[1]:                                 # dWin = (Wout^T dY) X^T over all tokens / pixels
+            if gr is None:                          # no fused launch delivered it: product 1 alone
+                wp, memo = _chain_planes(g, w_out, transpose=True)
+                gr = ops.chain_single(g, wp, None, w_out.shape[1], memo=memo, **single)
+            gwi = ops.wgrad(gr, x).to(w_in.dtype)
+            del gr                                  # released before the other intermediate is made
+        if need[2]:                                 # dWout = dY (Win X)^T, H from the forward launch where it saved it
+            if h is None:
+                wp, memo = _chain_planes(x, w_in)
+                h = ops.chain_single(x, wp, None, w_in.shape[0], memo=memo, **single)
+            gwo = ops.wgrad(g, h).to(w_out.dtype)
+        if ctx.has_bias and need[3]:
+            gb = g.sum(bias_dims)
         return gx, gwi, gwo, gb, None, None
 
 
@@ -311,81 +315,11 @@ def linear_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias:
     `ops.chain_train_pays` decides.  dX is bit-identical on both routes."""
     lead = x.shape[:-1]
     if not _needs_grad(x, w_in, w_out, bias):         # inference: straight to the C ABI, no autograd node
-        fresh = planes is None
-        if fresh:
-            n = _nplanes(x)
-            planes = (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x))
-        return ops.chain_fused(x.reshape(-1, x.shape[-1]), planes[0], planes[1], bias, w_out.shape[0],
-                               memo=not fresh).reshape(*lead, w_out.shape[0])
-    return _ChainFused.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes, save).reshape(*lead, w_out.shape[0])
-
-
-class _Conv1x1Chain(torch.autograd.Function):
-    """y[b,:,p] = Wout (Win x[b,:,p]) + bias on NCHW images in one launch; Win (R, C), Wout (N, R), R <= 256.  The saved
-    route is `_ChainFused`'s on images: H and dH are (B, R, H, W) tensors."""
-
-    @staticmethod
-    def forward(ctx, x, w_in, w_out, bias, planes, save):
-        if not x.is_cuda:
-            raise TadmmError(-1, "chain operands must live on the HIP device (no CPU fallback)")
-        _inference_only(x)
-        n = _nplanes(x)
-        fresh = planes is None
-        if fresh:
-            planes = (planes_of(w_in, n, pad_rows=64), planes_of(w_out, n, pad_cols=64))
-        ctx.saved_route = _saved_route(ctx, x, w_in, w_out, save, True)
-        h = None
-        if ctx.saved_route and ctx.needs_input_grad[2]:              # H feeds dWout alone
-            y, h = ops.svd_conv_save(x, planes[0], planes[1], bias, w_out.shape[0], w_in.shape[0])
-        else:
-            y = ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
-        ctx.save_for_backward(x, w_in, w_out, h)
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w_in, w_out, h = ctx.saved_tensors
-        g = g.contiguous()
-        n = _nplanes(g)
-        gx = gwi = gwo = gb = None
-        if ctx.saved_route:
-            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:  # dX and dH = Wout^T dY from one launch
-                gx, gr = ops.svd_conv_save(g, planes_of(w_out, n, pad_rows=64, transpose=True),
-                                           planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
-                                           w_in.shape[0], entry="tadmm_svdconv_bwd_save")
-                gwi = ops.wgrad(gr, x).to(w_in.dtype)
-                del gr
-            elif ctx.needs_input_grad[0]:
-                gx = ops.svd_conv(g, planes_of(w_out, n, pad_rows=64, transpose=True),
-                                  planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
-                                  entry="tadmm_svdconv_bwd", memo=False)
-            elif ctx.needs_input_grad[1]:           # no dX wanted: product 1 alone
-                gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1],
-                                      entry="tadmm_tucker_1x1", image_out=True, memo=False)
-                gwi = ops.wgrad(gr, x).to(w_in.dtype)
-                del gr
-            if ctx.needs_input_grad[2]:             # dWout = dY H^T over all pixels, H from the forward launch
-                gwo = ops.wgrad(g, h).to(w_out.dtype)
-            if ctx.has_bias and ctx.needs_input_grad[3]:
-                gb = g.sum((0, 2, 3))
-            return gx, gwi, gwo, gb, None, None
-        if ctx.needs_input_grad[0]:                 # dX = Win^T (Wout^T dY): the fused kernel on the transposed factors
-            gx = ops.svd_conv(g, planes_of(w_out, n, pad_rows=64, transpose=True),
-                              planes_of(w_in, n, pad_cols=64, transpose=True), None, w_in.shape[1],
-                              entry="tadmm_svdconv_bwd", memo=False)
-        if ctx.needs_input_grad[1]:                 # dWin = (Wout^T dY) X^T over all pixels
-            gr = ops.chain_single(g, planes_of(w_out, n, transpose=True), None, w_out.shape[1], entry="tadmm_tucker_1x1",
-                                  image_out=True, memo=False)
-            gwi = ops.wgrad(gr, x).to(w_in.dtype)
-            del gr                                  # released before the other intermediate is made
-        if ctx.needs_input_grad[2]:                 # dWout = dY (Win X)^T over all pixels
-            h = ops.chain_single(x, planes_of(w_in, _nplanes(x)), None, w_in.shape[0], entry="tadmm_tucker_1x1",
-                                 image_out=True, memo=False)
-            gwo = ops.wgrad(g, h).to(w_out.dtype)
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            gb = g.sum((0, 2, 3))
-        return gx, gwi, gwo, gb, None, None
+        # (given planes go round the helper: this is what TTLinearM's fast path calls, and a Python frame shows there)
+        (p_in, p_out), memo = (planes, True) if planes is not None else _chain_planes(x, w_in, w_out)
+        return ops.chain_fused(x.reshape(-1, x.shape[-1]), p_in, p_out, bias, w_out.shape[0],
+                               memo=memo).reshape(*lead, w_out.shape[0])
+    return _FusedChain.apply(x.reshape(-1, x.shape[-1]), w_in, w_out, bias, planes, save).reshape(*lead, w_out.shape[0])
 
 
 def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias: torch.Tensor = None, planes=None,
@@ -401,12 +335,9 @@ def conv1x1_chain(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, bias
     if not fused_rank_ok(w_in.shape[0]):
         raise TadmmError(-5, f"conv1x1_chain: rank {w_in.shape[0]} does not fit the fused kernel (at most 256)")
     if not _needs_grad(x, w_in, w_out, bias):         # inference: straight to the C ABI, no autograd node
-        fresh = planes is None
-        if fresh:
-            n = _nplanes(x)
-            planes = (planes_of(w_in, n, pad_rows=64, like=x), planes_of(w_out, n, pad_cols=64, like=x))
-        return ops.svd_conv(x, planes[0], planes[1], bias, w_out.shape[0], memo=not fresh)
-    return _Conv1x1Chain.apply(x.contiguous(), w_in, w_out, bias, planes, save)
+        (p_in, p_out), memo = _chain_planes(x, w_in, w_out, planes)
+        return ops.svd_conv(x, p_in, p_out, bias, w_out.shape[0], memo=memo)
+    return _FusedChain.apply(x.contiguous(), w_in, w_out, bias, planes, save)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -464,17 +395,31 @@ def core_conv(x: torch.Tensor, core: torch.Tensor, stride=1, padding=0, dilation
     return ops.core_conv(x, planes, core.shape[0], core.shape[2:], stride, padding, dilation, memo=not fresh)
 
 
-
-def core_conv_routed(layer, x: torch.Tensor):
-    """`core_conv` of a factorised layer's `core_kernel` when `ops.core_conv_pays` routes it to the native kernel (its
-    planes cached on the layer in inference), else None: the caller keeps the device library's conv2d."""
+def conv_stages(layer, x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, entries, planes=None):
+    """A factorised convolution layer as three launches: (f1, f2, f3) = the 1x1 map `w_in` (entries[0]) on the NCHW tensor
+    as it stands (no NHWC copies), the k x k convolution with `layer.core_kernel` -- the native kernel of csrc/coreconv.hip
+    where `ops.core_conv_pays` routes it there (its planes cached on the layer in inference), else the device library's
+    conv2d -- and the 1x1 map `w_out` + `layer.bias` (entries[1], bias in the epilogue).  Differentiable.  `planes`: the
+    caller's prebuilt (planes_of(w_in, n), planes_of(w_out, n)); without them, outside grad mode, the layer's
+    `_plane_cache` holds them."""
+    n = _nplanes(x)
+    p_in, p_out = planes if planes is not None else (None, None)
+    cache = None if planes is not None or torch.is_grad_enabled() else layer.__dict__.setdefault("_plane_cache", {})
+    if cache is not None:
+        p_in = planes_of(w_in, n, cache=cache, tag="first", like=x)
+    f1 = pointwise(x, w_in, None, entries[0], p_in)
     core = layer.core_kernel
-    grad = _needs_grad(x, core)
-    if layer.groups != 1 or not ops.core_conv_pays(x, core.shape[0], layer.kernel_size, layer.stride, layer.padding,
-                                                    layer.dilation, layer.groups, training=grad):
-        return None
-    cache = None if grad else layer.__dict__.setdefault("_core_cache", {})
-    return core_conv(x, core, layer.stride, layer.padding, layer.dilation, cache=cache)
+    grad = _needs_grad(f1, core)
+    if layer.groups == 1 and ops.core_conv_pays(f1, core.shape[0], layer.kernel_size, layer.stride, layer.padding,
+                                                layer.dilation, layer.groups, training=grad):
+        f2 = core_conv(f1, core, layer.stride, layer.padding, layer.dilation,
+                       cache=None if grad else layer.__dict__.setdefault("_core_cache", {}))
+    else:
+        f2 = F.conv2d(f1, core if x.dtype == core.dtype else core.to(x.dtype), None, layer.stride, layer.padding,
+                      layer.dilation, layer.groups)
+    if cache is not None:
+        p_out = planes_of(w_out, n, cache=cache, tag="last", like=x)
+    return f1, f2, pointwise(f2, w_out, layer.bias, entries[1], p_out)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -605,17 +550,28 @@ def conv_chain(x: torch.Tensor, w_in: torch.Tensor, core: torch.Tensor, w_out: t
     return ops.conv_chain(x, p1, p2, p3, bias, w_out.shape[0], ksize, stride, padding, dilation, memo=cache is not None)
 
 
-def conv_chain_routed(layer, x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor):
-    """`conv_chain` of a factorised layer in grad mode where `ops.conv_chain_train_pays` routes it to the one-launch path,
-    else None: the caller keeps its three differentiable launches."""
+def conv_chain_layer(layer, x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, inference: bool):
+    """A factorised convolution layer (`layer.core_kernel` between the 1x1 maps w_in (r1, C) and w_out (O, r2)) in ONE
+    launch, or None where that does not apply and the caller keeps `conv_stages`.  `inference` (the caller's decision:
+    the route builds no autograd node): where `ops.conv_chain_pays` says so, the planes packed once into the layer's
+    `_fused_cache` (`_cached_conv_chain_planes`).  Otherwise `conv_chain` where something wants a gradient and
+    `ops.conv_chain_train_pays` routes it there; frozen factors keep their planes in the same cache."""
     core = layer.core_kernel
-    if layer.groups != 1 or not _needs_grad(x, w_in, core, w_out, layer.bias):
+    if layer.groups != 1:
         return None
+    r1, r2 = w_in.shape[0], w_out.shape[1]
     geom = (layer.kernel_size, layer.stride, layer.padding, layer.dilation)
-    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or not ops.conv_chain_fits(x, w_in.shape[0], w_out.shape[1], *geom):
+    if inference:
+        if not ops.conv_chain_pays(x, r1, r2, *geom):
+            return None
+        cache = layer.__dict__.setdefault("_fused_cache", {})
+        p1, p2, p3 = _cached_conv_chain_planes(cache, w_in, core, w_out, _nplanes(x), x.device, False, plane_dtype(x))
+        return ops.conv_chain(x, p1, p2, p3, layer.bias, w_out.shape[0], *geom)
+    if not _needs_grad(x, w_in, core, w_out, layer.bias) or x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) \
+            or not ops.conv_chain_fits(x, r1, r2, *geom):
         return None
     training = _needs_grad(w_in, core, w_out)         # a factor wants a gradient: the intermediates are saved
-    if not ops.conv_chain_train_pays(x, w_in.shape[0], w_out.shape[1], *geom, training=training):
+    if not ops.conv_chain_train_pays(x, r1, r2, *geom, training=training):
         return None
     cache = None if training else layer.__dict__.setdefault("_fused_cache", {})
     return conv_chain(x, w_in, core, w_out, layer.bias, layer.stride, layer.padding, layer.dilation, cache=cache)

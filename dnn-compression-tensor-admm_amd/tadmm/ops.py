@@ -500,6 +500,28 @@ def _chain_dtype(xdtype, who: str):
     raise TadmmError(-1, f"{who}: unsupported dtype {xdtype}")
 
 
+def _f32_bias(bias):
+    """(the bias as the kernels read it: contiguous float32, its launch-memo key).  The key is None for a converted copy:
+    nothing to memoise."""
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        return bias.detach().float().contiguous(), None
+    return bias, 0 if bias is None else bias.data_ptr()
+
+
+def _out_tensors(out, shapes, like):
+    """One contiguous tensor of `like`'s dtype and device per shape: the caller's (`out`: a tensor or a sequence, None
+    entries allowed) where given, else a fresh one."""
+    given = (out,) if isinstance(out, torch.Tensor) else (tuple(out) if out is not None else ())
+    res = []
+    for shape, t in zip(shapes, given + (None,) * len(shapes)):
+        if t is None:
+            t = torch.empty(shape, dtype=like.dtype, device=like.device)
+        elif tuple(t.shape) != tuple(shape) or t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
+            raise TadmmError(-1, f"conv chain: `out` must be a contiguous {like.dtype} tensor of shape {tuple(shape)}")
+        res.append(t)
+    return res
+
+
 def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin: int, n1: int, n_out: int,
                 image_out: bool, tile_tokens: int, prepare_only: bool = False, use_memo: bool = True, save_rank: int = 0):
     """`save_rank` > 0: `entry` is one of the `_save` entries; the launch also stores the first `save_rank` columns of the
@@ -513,11 +535,7 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
             x = x.contiguous()
     elif x.stride(1) != 1 or (x.stride(0) * x.element_size()) % 16 or x.data_ptr() % 16:
         x = x.contiguous()
-    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
-        bias = bias.detach().float().contiguous()
-        bias_key = None                                 # a converted copy: nothing to memoise
-    else:
-        bias_key = 0 if bias is None else bias.data_ptr()
+    bias, bias_key = _f32_bias(bias)
     if not use_memo:
         bias_key = None                                 # short-lived planes (training): build, launch, forget
     # geometry + weight identity -> validated descriptor; only the activation pointers change between calls
@@ -672,36 +690,47 @@ def svd_conv_pays(x: torch.Tensor, rank: int) -> bool:
     return x.dtype in HALF_DTYPES and 0 < rank <= 256
 
 
-def _conv_chain_plan(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation):
-    """(pixels per workgroup, output rows per workgroup, halo tiles, workgroups per image) of the one-launch factorised
-    convolution, or None when it does not apply -- the rule tadmm_ttconv_fused applies."""
-    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+def _conv_tile_plan(dtype, rows: int, width: int, r_halo: int, r_tile: int, halo_rows, halo_width: int,
+                    extra_per_pixel: int = 0):
+    """The tile search of the one-launch factorised convolution and of its data gradient: (pixels per workgroup, rows per
+    workgroup, halo tiles, workgroups per image) or None.  A workgroup takes a run of whole rows of the `rows` x `width`
+    plane it writes, at most tm = 64 (else 32) pixels; `halo_rows(tr)` rows of `halo_width` pixels of the plane it reads
+    feed a run of tr rows, in at most three tiles of tm pixels.  The intermediate of rank `r_halo` is held for the halo, that
+    of rank `r_tile` for the tile; `extra_per_pixel`: further LDS bytes per tile pixel."""
+    r_halo, r_tile = -(-r_halo // 32) * 32, -(-r_tile // 32) * 32
+    if r_halo > 256 or r_tile > 256:
         return None
-    H, W = x.shape[2], x.shape[3]
-    ho = (H + 2 * padding[0] - dilation[0] * (kernel_size[0] - 1) - 1) // stride[0] + 1
-    wo = (W + 2 * padding[1] - dilation[1] * (kernel_size[1] - 1) - 1) // stride[1] + 1
-    if ho <= 0 or wo <= 0 or wo > 64:
-        return None
-    r1p, r2p = -(-r1 // 32) * 32, -(-r2 // 32) * 32
-    if r1p > 256 or r2p > 256:
-        return None
-    planes, kc = (3, 64) if x.dtype == torch.float32 else (1, 128)
+    planes, kc = (3, 64) if dtype == torch.float32 else (1, 128)
     for tm in (64, 32):                                  # pixels per workgroup: 64, or 32 when 64 does not fit the LDS
-        if wo > tm:
+        if width > tm:
             continue
-        tr, nt = min(ho, tm // wo), 0
+        tr, nt = min(rows, tm // width), 0
         while tr >= 1:
-            irows = min(H, (tr - 1) * stride[0] + (kernel_size[0] - 1) * dilation[0] + 1)
-            nt = -(-(irows * W) // tm)
+            nt = -(-(halo_rows(tr) * halo_width) // tm)
             if nt <= 3:
                 break
             tr -= 1
         if tr < 1:
             continue
-        lds = (2 * planes * tm * (kc + 8) + planes * tm * nt * (r1p + 8) + planes * tm * (r2p + 8)) * 2
+        lds = (2 * planes * tm * (kc + 8) + planes * tm * nt * (r_halo + 8) + planes * tm * (r_tile + 8)) * 2 \
+            + extra_per_pixel * tm
         if lds <= 160 * 1024:
-            return tm, tr, nt, -(-ho // tr)
+            return tm, tr, nt, -(-rows // tr)
     return None
+
+
+def _conv_chain_plan(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation):
+    """(pixels per workgroup, output rows per workgroup, halo tiles, workgroups per image) of the one-launch factorised
+    convolution, or None when it does not apply -- the rule tadmm_ttconv_fused applies.  The tile is a run of output
+    rows, its halo the input rows the taps reach."""
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return None
+    H, W = x.shape[2], x.shape[3]
+    ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
+    if ho <= 0 or wo <= 0:
+        return None
+    return _conv_tile_plan(x.dtype, ho, wo, r1, r2,
+                           lambda tr: min(H, (tr - 1) * stride[0] + (kernel_size[0] - 1) * dilation[0] + 1), W)
 
 
 def conv_chain_fits(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation) -> bool:
@@ -738,29 +767,11 @@ def _conv_chain_bwd_plan(x_shape, dtype, r1: int, r2: int, kernel_size, stride, 
         return None
     H, W = x_shape[2], x_shape[3]
     ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
-    if ho <= 0 or wo <= 0 or H <= 0 or W <= 0 or W > 64:
+    if ho <= 0 or wo <= 0 or H <= 0 or W <= 0:
         return None
-    r1p, r2p = -(-r1 // 32) * 32, -(-r2 // 32) * 32
-    if r1p > 256 or r2p > 256:
-        return None
-    planes, kc = (3, 64) if dtype == torch.float32 else (1, 128)
-    for tm in (64, 32):
-        if W > tm:
-            continue
-        tr, nt = min(H, tm // W), 0
-        while tr >= 1:
-            srows = min(ho, (tr - 1 + (kernel_size[0] - 1) * dilation[0]) // stride[0] + 1)
-            nt = -(-(srows * wo) // tm)
-            if nt <= 3:
-                break
-            tr -= 1
-        if tr < 1:
-            continue
-        lds = (2 * planes * tm * (kc + 8) + planes * tm * nt * (r2p + 8) + planes * tm * (r1p + 8)) * 2 \
-            + kernel_size[0] * kernel_size[1] * tm * 2
-        if lds <= 160 * 1024:
-            return tm, tr, nt, -(-H // tr)
-    return None
+    return _conv_tile_plan(dtype, H, W, r2, r1,
+                           lambda tr: min(ho, (tr - 1 + (kernel_size[0] - 1) * dilation[0]) // stride[0] + 1), wo,
+                           extra_per_pixel=kernel_size[0] * kernel_size[1] * 2)
 
 
 def conv_chain_bwd_fits(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation) -> bool:
@@ -830,11 +841,7 @@ def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch
         raise TadmmError(-1, "x must live on a HIP device; there is no CPU path")
     if not x.is_contiguous():
         x = x.contiguous()
-    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
-        bias = bias.detach().float().contiguous()
-        bias_key = None
-    else:
-        bias_key = 0 if bias is None else bias.data_ptr()
+    bias, bias_key = _f32_bias(bias)
     if save_ranks is not None or not memo:
         bias_key = None                                 # training: the planes are short-lived -- build, launch, forget
     key = ("conv", tuple(x.shape), x.dtype, x.device, w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr(),
@@ -854,24 +861,17 @@ def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch
             _CHAIN_MEMO.store(key, memo)
     d, fn, h, yshape, _ = memo
 
-    def result(shape, given):
-        if given is None:
-            return torch.empty(shape, dtype=x.dtype, device=x.device)
-        if tuple(given.shape) != tuple(shape) or given.dtype != x.dtype or given.device != x.device or not given.is_contiguous():
-            raise TadmmError(-1, f"conv chain: `out` must be a contiguous {x.dtype} tensor of shape {tuple(shape)}")
-        return given
-
-    outs = (out,) if isinstance(out, torch.Tensor) else (tuple(out) if out is not None else ())
-    outs = outs + (None,) * (3 - len(outs))
-    y = result(yshape, outs[0])
+    shapes = [yshape]
+    if save_ranks is not None:
+        r1, r2 = save_ranks
+        shapes += [(x.shape[0], r1, x.shape[2], x.shape[3]), (yshape[0], r2, yshape[2], yshape[3])]
+    y, *saved = _out_tensors(out, shapes, x)
     d.X, d.Y = x.data_ptr(), y.data_ptr()
     if save_ranks is None:
         if yshape[0] > 0:
             h.check(fn(h.ptr, C.byref(d), _stream(x.device)))
         return y
-    r1, r2 = save_ranks
-    h1 = result((x.shape[0], r1, x.shape[2], x.shape[3]), outs[1])
-    h2 = result((yshape[0], r2, yshape[2], yshape[3]), outs[2])
+    h1, h2 = saved
     h.check(h.lib.tadmm_ttconv_fused_save(h.ptr, C.byref(d), r1, r2, h1.data_ptr(), h2.data_ptr(), _stream(x.device)))
     return y, h1, h2
 
@@ -904,19 +904,8 @@ def conv_chain_bwd(dy: torch.Tensor, w3tp: torch.Tensor, w2tp: torch.Tensor, w1t
         raise TadmmError(-1, f"conv chain: dy of shape {tuple(dy.shape)} is not the output of x {tuple(x_shape)}")
     dev = dy.device
     h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
-    def result(shape, given):
-        if given is None:
-            return torch.empty(shape, dtype=dy.dtype, device=dev)
-        if tuple(given.shape) != tuple(shape) or given.dtype != dy.dtype or given.device != dev or not given.is_contiguous():
-            raise TadmmError(-1, f"conv chain: `out` must be a contiguous {dy.dtype} tensor of shape {tuple(shape)}")
-        return given
-
-    outs = (out,) if isinstance(out, torch.Tensor) else (tuple(out) if out is not None else ())
-    outs = outs + (None,) * (3 - len(outs))
-    dx = result(tuple(x_shape), outs[0])
-    dh1 = dh2 = None
-    if save:
-        dh1, dh2 = result((B, r1, H, W), outs[1]), result((B, r2, ho, wo), outs[2])
+    shapes = [tuple(x_shape)] + ([(B, r1, H, W), (B, r2, ho, wo)] if save else [])
+    dx, dh1, dh2 = _out_tensors(out, shapes, dy) + [None] * (3 - len(shapes))
     d.X, d.Y = dy.data_ptr(), dx.data_ptr()
     h.check(h.lib.tadmm_ttconv_fused_bwd(h.ptr, C.byref(d), r1, r2, None if dh1 is None else dh1.data_ptr(),
                                          None if dh2 is None else dh2.data_ptr(), _stream(dev)))

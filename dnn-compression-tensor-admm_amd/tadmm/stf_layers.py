@@ -31,7 +31,8 @@ from torch import Tensor, nn
 from torch.nn import init
 
 from . import ops
-from .tk_layers import TKConv2dC, _TKConvBase, _check_mode, _tucker_factors
+from ._layer_common import make_bias
+from .tk_layers import _TKConvChain, _check_mode, _tucker_factors
 
 
 class StiefelParameter(nn.Parameter):
@@ -42,7 +43,7 @@ class StiefelParameter(nn.Parameter):
         return "Stiefel parameter containing:\n" + torch.Tensor.__repr__(self.data)
 
 
-class StfTKConv2dC(_TKConvBase):
+class StfTKConv2dC(_TKConvChain):
     def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1,
                  groups: int = 1, bias: bool = True, padding_mode: str = 'zeros', hp_dict=None, name: str = None,
                  dense_w: Tensor = None, dense_b: Tensor = None):
@@ -56,7 +57,7 @@ class StfTKConv2dC(_TKConvBase):
         self.first_kernel = StiefelParameter(torch.empty(self.in_channels, self.in_rank))
         self.core_kernel = nn.Parameter(torch.empty(self.out_rank, self.in_rank, *self.kernel_size))
         self.last_kernel = StiefelParameter(torch.empty(self.out_channels, self.out_rank))
-        self._make_bias(bias, dense_b)
+        make_bias(self, self.out_channels, bias, dense_b)
         self._pending_projection = False
         if dense_w is not None:                       # the HOOI factors have orthonormal columns already
             core, u_out, u_in = _tucker_factors(dense_w, self.out_rank, self.in_rank)
@@ -92,13 +93,5 @@ class StfTKConv2dC(_TKConvBase):
         self._pending_projection = False              # the loaded factors are the caller's
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def _stages(self, x):
-        return TKConv2dC._stages(self, x, self.first_kernel.t(), self.last_kernel)
-
-    def forward(self, x):
-        y = TKConv2dC._fused(self, x, self.first_kernel.t(), self.core_kernel, self.last_kernel)
-        return y if y is not None else self._stages(x)[2]
-
-    forward_features = TKConv2dC.forward_features
-    forward_flops = TKConv2dC.forward_flops
-    extra_repr = TKConv2dC.extra_repr
+    def _factors(self):
+        return self.first_kernel.t(), self.last_kernel

@@ -32,11 +32,12 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 from torch.nn import init
-from torch.nn.modules.utils import _pair, _reverse_repeat_tuple
+from torch.nn.modules.utils import _pair
 
 from . import functional as HF
 from . import ops
 from ._cabi import KIND_SVD
+from ._layer_common import DenseConvMixin, make_bias
 
 
 def svd_factors(ws, ranks, device=None):
@@ -67,14 +68,6 @@ def _rank_of(hp_dict, name):
 
 
 class _SVDConvBase(HF.InferenceCacheMixin, nn.Module):
-    def _make_bias(self, bias, dense_b):
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_channels))
-            if dense_b is not None:
-                self.bias.data = dense_b
-        else:
-            self.register_parameter('bias', None)
-
     def _setup(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode, hp_dict,
                name):
         kernel_size, stride = _pair(kernel_size), _pair(stride)
@@ -116,7 +109,7 @@ class _SVDConvBase(HF.InferenceCacheMixin, nn.Module):
         return x.is_cuda and x.dim() == 4 and HF.chain_dtype_ok(x, *self.parameters(recurse=False))
 
 
-class SVDConv2dR(_SVDConvBase):
+class SVDConv2dR(DenseConvMixin, _SVDConvBase):
     def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1,
                  groups: int = 1, bias: bool = True, padding_mode: str = 'zeros', hp_dict=None, name: str = None,
                  dense_w: Tensor = None, dense_b: Tensor = None):
@@ -129,24 +122,16 @@ class SVDConv2dR(_SVDConvBase):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.ranks, self.rank = _rank_of(hp_dict, name)
-        if in_channels % groups != 0:
-            raise ValueError('in_channels must be divisible by groups')
-        if out_channels % groups != 0:
-            raise ValueError('out_channels must be divisible by groups')
-        valid_padding_modes = {'zeros', 'reflect', 'replicate', 'circular'}
-        if padding_mode not in valid_padding_modes:
-            raise ValueError("padding_mode must be one of {}, but got padding_mode='{}'".format(
-                valid_padding_modes, padding_mode))
         self.kernel_size, self.stride = kernel_size, stride
         self.padding, self.dilation = padding, dilation
+        self._init_dense_conv(in_channels, out_channels, groups, padding_mode)
         self.transposed = False
         self.output_padding = _pair(0)
         self.groups = groups
         self.padding_mode = padding_mode
-        self._reversed_padding_repeated_twice = _reverse_repeat_tuple(self.padding, 2)
         self.left_factor = nn.Parameter(torch.empty(self.rank, self.in_channels))
         self.right_factor = nn.Parameter(torch.empty(self.out_channels, self.rank))
-        self._make_bias(bias, dense_b)
+        make_bias(self, self.out_channels, bias, dense_b)
         if dense_w is not None:
             u, sv = svd_factors([dense_w], [self.rank])[0]
             self.left_factor.data = u                 # (O, r): the reference's layout, not the declared one
@@ -169,15 +154,6 @@ class SVDConv2dR(_SVDConvBase):
             return HF.mm(self.left_factor, self.right_factor).unsqueeze(-1).unsqueeze(-1)
         return self.left_factor.mm(self.right_factor).unsqueeze(-1).unsqueeze(-1)
 
-    def _conv_forward(self, x, weight):
-        if self.padding_mode != 'zeros':
-            return F.conv2d(F.pad(x, self._reversed_padding_repeated_twice, mode=self.padding_mode), weight, self.bias,
-                            self.stride, _pair(0), self.dilation, self.groups)
-        return F.conv2d(x, weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
-
-    def forward(self, x: Tensor) -> Tensor:
-        return self._conv_forward(x, self._recover_weight())
-
 
 class SVDConv2dC(_SVDConvBase):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
@@ -185,10 +161,10 @@ class SVDConv2dC(_SVDConvBase):
         super().__init__()
         self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode, hp_dict,
                     name)
-        self._make_bias(bias, dense_b)
+        make_bias(self, self.out_channels, bias, dense_b)
         self.left_kernel = nn.Parameter(torch.empty(self.rank, self.in_channels, *self.kernel_size))
         self.right_kernel = nn.Parameter(torch.empty(self.out_channels, self.rank, *self.kernel_size))
-        self._make_bias(bias, dense_b)                # registered twice, as the reference: first in the state_dict
+        make_bias(self, self.out_channels, bias, dense_b)    # registered twice, as the reference: first in the state_dict
         if dense_w is not None:
             u, sv = svd_factors([dense_w], [self.rank])[0]
             self.right_kernel.data = u[:, :, None, None]
@@ -241,10 +217,10 @@ class SVDConv2dM(_SVDConvBase):
         super().__init__()
         self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode, hp_dict,
                     name)
-        self._make_bias(bias, dense_b)
+        make_bias(self, self.out_channels, bias, dense_b)
         self.left_factor = nn.Parameter(torch.empty(self.rank, self.in_channels))
         self.right_factor = nn.Parameter(torch.empty(self.out_channels, self.rank))
-        self._make_bias(bias, dense_b)                # registered twice, as the reference: first in the state_dict
+        make_bias(self, self.out_channels, bias, dense_b)    # registered twice, as the reference: first in the state_dict
         if dense_w is not None:
             u, sv = svd_factors([dense_w], [self.rank])[0]
             self.right_factor.data = u

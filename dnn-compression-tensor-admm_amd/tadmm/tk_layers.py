@@ -18,14 +18,13 @@ from __future__ import annotations
 import math
 
 import torch
-import torch.nn.functional as F
 from torch import Tensor, nn
 from torch.nn import init
-from torch.nn.modules.utils import _pair, _reverse_repeat_tuple
+from torch.nn.modules.utils import _pair
 
 from . import functional as HF
-from . import ops
 from . import tucker
+from ._layer_common import DenseConvMixin, fused_linear_ok, make_bias
 
 
 def _empty(*shape):
@@ -59,89 +58,20 @@ class _TKConvBase(HF.InferenceCacheMixin, nn.Module):
         self.groups = groups
         self.padding_mode = padding_mode
 
-    def _make_bias(self, bias, dense_b):
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_channels))
-            if dense_b is not None:
-                self.bias.data = dense_b
-        else:
-            self.register_parameter('bias', None)
 
+class _TKConvChain(_TKConvBase):
+    """1x1 -> k x k -> 1x1 + bias on the chain kernels.  A subclass stores the two factors in its own layout and says
+    through `_factors()` what they are: w1 (in_rank, in_channels) and w3 (out_channels, out_rank)."""
 
-def _check_mode(groups, padding_mode):
-    if groups != 1:
-        raise ValueError("groups must be 1 in this mode")
-    if padding_mode != 'zeros':
-        raise ValueError("padding_mode must be zero in this mode")
-
-
-class TKConv2dC(_TKConvBase):
-    def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1,
-                 groups: int = 1, bias: bool = True, padding_mode: str = 'zeros', hp_dict=None, name: str = None,
-                 dense_w: Tensor = None, dense_b: Tensor = None):
-        _check_mode(groups, padding_mode)
-        super().__init__()
-        self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode,
-                    hp_dict.ranks[name])
-        self.first_kernel = _empty(self.in_rank, self.in_channels, 1, 1)
-        self.core_kernel = _empty(self.out_rank, self.in_rank, *self.kernel_size)
-        self.last_kernel = _empty(self.out_channels, self.out_rank, 1, 1)
-        self._make_bias(bias, dense_b)
-        if dense_w is not None:
-            core, u_out, u_in = _tucker_factors(dense_w, self.out_rank, self.in_rank)
-            self.first_kernel.data = u_in.t().contiguous()[:, :, None, None]
-            self.last_kernel.data = u_out.contiguous()[:, :, None, None]
-            self.core_kernel.data = core
-        else:
-            self.reset_parameters()
-
-    def reset_parameters(self) -> None:
-        for p in (self.first_kernel, self.core_kernel, self.last_kernel):
-            init.xavier_uniform_(p)
-
-    def _stages(self, x, w1=None, w3=None):
-        # a 1x1 conv is a per-pixel channel mix: one chain-kernel launch on the NCHW tensor as it stands
-        # (`tadmm_tucker_1x1`: no NHWC copies, bias in the epilogue).  w1 (in_rank, in_channels) / w3 (out_channels,
-        # out_rank): given by layers that store the two factors in another layout (stf_layers.StfTKConv2dC)
-        grad = torch.is_grad_enabled()
-        cache = None if grad else self.__dict__.setdefault("_plane_cache", {})
-        if w1 is None:
-            w1 = self.first_kernel.reshape(self.in_rank, self.in_channels)
-        if w3 is None:
-            w3 = self.last_kernel.reshape(self.out_channels, self.out_rank)
-        n = HF._nplanes(x)
-        p1 = None if grad else HF.planes_of(w1, n, cache=cache, tag="first", like=x)
-        f1 = HF.pointwise(x, w1, None, "tadmm_tucker_1x1", p1)
-        f2 = HF.core_conv_routed(self, f1)                      # the native k x k kernel where it pays (csrc/coreconv.hip)
-        if f2 is None:
-            core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
-            f2 = F.conv2d(f1, core, None, self.stride, self.padding, self.dilation, self.groups)
-        p3 = None if grad else HF.planes_of(w3, n, cache=cache, tag="last", like=x)
-        f3 = HF.pointwise(f2, w3, self.bias, "tadmm_tucker_1x1", p3)
-        return f1, f2, f3
-
-    def _fused(self, x, w1, core, w3):
-        """The whole layer in one launch when the planes are small (csrc/convchain.hip); None when it does not apply."""
-        y = HF.conv_chain_routed(self, x, w1, w3)              # grad mode, where ops.conv_chain_train_pays says so
-        if y is not None:
-            return y
-        if torch.is_grad_enabled() or self.groups != 1 or not ops.conv_chain_pays(
-                x, w1.shape[0], w3.shape[1], self.kernel_size, self.stride, self.padding, self.dilation):
-            return None
-        n, pdt = HF._nplanes(x), HF.plane_dtype(x)
-        cache = self.__dict__.setdefault("_fused_cache", {})
-        key = (x.dtype, x.device, HF.param_key(w1, core, w3))    # the dtype, not n: bf16 and f16 planes differ
-        if cache.get("key") != key:
-            cache.update(key=key, planes=(ops.weight_planes(w1.detach(), n, pad_rows=32, dtype=pdt),
-                                          ops.conv_core_planes(core, n, dtype=pdt),
-                                          ops.weight_planes(w3.detach(), n, dtype=pdt)))
-        p1, p2, p3 = cache["planes"]
-        return ops.conv_chain(x, p1, p2, p3, self.bias, self.out_channels, self.kernel_size, self.stride, self.padding,
-                              self.dilation)
+    def _stages(self, x):
+        return HF.conv_stages(self, x, *self._factors(), ("tadmm_tucker_1x1", "tadmm_tucker_1x1"))
 
     def forward(self, x):
-        y = self._fused(x, self.first_kernel.reshape(self.in_rank, self.in_channels), self.core_kernel,
-                        self.last_kernel.reshape(self.out_channels, self.out_rank))
+        """The whole layer in one launch when the planes are small (csrc/convchain.hip), else three."""
+        w1, w3 = self._factors()
+        # "inference" is grad mode off here.  With grad mode on and nothing requiring a gradient this is therefore three
+        # launches whose planes are packed afresh on every call, where TTConv2dM takes the cached one-launch route.
+        y = HF.conv_chain_layer(self, x, w1, w3, inference=not torch.is_grad_enabled())
         return y if y is not None else self._stages(x)[2]
 
     def forward_features(self, x):                                # TKConv.py:100-109
@@ -150,11 +80,12 @@ class TKConv2dC(_TKConvBase):
 
     def forward_flops(self, x):                                   # TKConv.py:111-134
         f1, f2, out = self._stages(x)
-        compr_params = (self.first_kernel.numel() + self.core_kernel.numel() + self.last_kernel.numel()) / 1000
-        compr_flops = f1.shape[2] * f1.shape[3] * self.first_kernel.numel() / 1e6
+        w1, w3 = self._factors()
+        compr_params = (w1.numel() + self.core_kernel.numel() + w3.numel()) / 1000
+        compr_flops = f1.shape[2] * f1.shape[3] * w1.numel() / 1e6
         compr_flops += f2.shape[2] * f2.shape[3] * self.core_kernel.numel() / 1e6
         h2, w2 = out.shape[2], out.shape[3]
-        compr_flops += h2 * w2 * self.last_kernel.numel() / 1e6
+        compr_flops += h2 * w2 * w3.numel() / 1e6
         kh, kw = self.kernel_size
         base_params = kh * kw * self.in_channels * self.out_channels / 1000
         base_flops = h2 * w2 * kh * kw * self.in_channels * self.out_channels / 1e6
@@ -171,7 +102,43 @@ class TKConv2dC(_TKConvBase):
             self.bias is None, self.out_rank, self.out_channels)
 
 
-class TKConv2dM(_TKConvBase):
+def _check_mode(groups, padding_mode):
+    if groups != 1:
+        raise ValueError("groups must be 1 in this mode")
+    if padding_mode != 'zeros':
+        raise ValueError("padding_mode must be zero in this mode")
+
+
+class TKConv2dC(_TKConvChain):
+    def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1,
+                 groups: int = 1, bias: bool = True, padding_mode: str = 'zeros', hp_dict=None, name: str = None,
+                 dense_w: Tensor = None, dense_b: Tensor = None):
+        _check_mode(groups, padding_mode)
+        super().__init__()
+        self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode,
+                    hp_dict.ranks[name])
+        self.first_kernel = _empty(self.in_rank, self.in_channels, 1, 1)
+        self.core_kernel = _empty(self.out_rank, self.in_rank, *self.kernel_size)
+        self.last_kernel = _empty(self.out_channels, self.out_rank, 1, 1)
+        make_bias(self, self.out_channels, bias, dense_b)
+        if dense_w is not None:
+            core, u_out, u_in = _tucker_factors(dense_w, self.out_rank, self.in_rank)
+            self.first_kernel.data = u_in.t().contiguous()[:, :, None, None]
+            self.last_kernel.data = u_out.contiguous()[:, :, None, None]
+            self.core_kernel.data = core
+        else:
+            self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        for p in (self.first_kernel, self.core_kernel, self.last_kernel):
+            init.xavier_uniform_(p)
+
+    def _factors(self):
+        return (self.first_kernel.reshape(self.in_rank, self.in_channels),
+                self.last_kernel.reshape(self.out_channels, self.out_rank))
+
+
+class TKConv2dM(_TKConvChain):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  padding_mode='zeros', hp_dict=None, name=str, dense_w=None, dense_b=None):
         _check_mode(groups, padding_mode)
@@ -181,7 +148,7 @@ class TKConv2dM(_TKConvBase):
         self.first_factor = _empty(self.in_rank, in_channels)
         self.core_kernel = _empty(self.out_rank, self.in_rank, *self.kernel_size)
         self.last_factor = _empty(out_channels, self.out_rank)
-        self._make_bias(bias, dense_b)
+        make_bias(self, self.out_channels, bias, dense_b)
         if dense_w is not None:
             core, u_out, u_in = _tucker_factors(dense_w, self.out_rank, self.in_rank)
             self.first_factor.data = u_in.t().contiguous()
@@ -194,46 +161,24 @@ class TKConv2dM(_TKConvBase):
         for p in (self.first_factor, self.last_factor, self.core_kernel):
             init.xavier_uniform_(p)
 
-    def forward(self, x: Tensor) -> Tensor:                       # TKConv.py:210-214
-        y = TKConv2dC._fused(self, x, self.first_factor, self.core_kernel, self.last_factor)
-        if y is not None:
-            return y
-        grad = torch.is_grad_enabled()
-        cache = None if grad else self.__dict__.setdefault("_plane_cache", {})
-        n = HF._nplanes(x)
-        p1 = None if grad else HF.planes_of(self.first_factor, n, cache=cache, tag="first", like=x)
-        out = HF.pointwise(x, self.first_factor, None, "tadmm_tucker_1x1", p1)
-        mid = HF.core_conv_routed(self, out)
-        if mid is None:
-            core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
-            mid = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
-        out = mid
-        p3 = None if grad else HF.planes_of(self.last_factor, n, cache=cache, tag="last", like=x)
-        return HF.pointwise(out, self.last_factor, self.bias, "tadmm_tucker_1x1", p3)
+    def _factors(self):                                           # TKConv.py:210-214
+        return self.first_factor, self.last_factor
 
 
-class TKConv2dR(_TKConvBase):
+class TKConv2dR(DenseConvMixin, _TKConvBase):
     def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1,
                  groups: int = 1, bias: bool = True, padding_mode: str = 'zeros', hp_dict=None, name: str = None,
                  dense_w: Tensor = None, dense_b: Tensor = None):
         super().__init__()
         self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode,
                     list(hp_dict.ranks[name]))
-        if in_channels % groups != 0:
-            raise ValueError('in_channels must be divisible by groups')
-        if out_channels % groups != 0:
-            raise ValueError('out_channels must be divisible by groups')
-        valid_padding_modes = {'zeros', 'reflect', 'replicate', 'circular'}
-        if padding_mode not in valid_padding_modes:
-            raise ValueError("padding_mode must be one of {}, but got padding_mode='{}'".format(
-                valid_padding_modes, padding_mode))
-        self._reversed_padding_repeated_twice = _reverse_repeat_tuple(self.padding, 2)
+        self._init_dense_conv(in_channels, out_channels, groups, padding_mode)
         self.kernel_shape = [out_channels, in_channels // groups, *self.kernel_size]
         self.filter_dim = int(self.kernel_shape[2] * self.kernel_shape[3])
         self.first_factor = _empty(self.in_rank, in_channels)
         self.core_tensor = _empty(self.out_rank, self.in_rank, self.kernel_shape[2], self.kernel_shape[3])
         self.last_factor = _empty(out_channels, self.out_rank)
-        self._make_bias(bias, dense_b)
+        make_bias(self, self.out_channels, bias, dense_b)
         if dense_w is not None:
             core, u_out, u_in = _tucker_factors(dense_w, self.out_rank, self.in_rank)
             self.first_factor.data = u_in.t().contiguous()
@@ -253,15 +198,6 @@ class TKConv2dR(_TKConvBase):
     def _recover_weight(self):
         return _recover(self.core_tensor, self.last_factor, self.first_factor)
 
-    def _conv_forward(self, x, weight):
-        if self.padding_mode != 'zeros':
-            return F.conv2d(F.pad(x, self._reversed_padding_repeated_twice, mode=self.padding_mode), weight, self.bias,
-                            self.stride, _pair(0), self.dilation, self.groups)
-        return F.conv2d(x, weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
-
-    def forward(self, x: Tensor) -> Tensor:
-        return self._conv_forward(x, self._recover_weight())
-
 
 class _TKLinearBase(HF.InferenceCacheMixin, nn.Module):
     def __init__(self, in_features: int, out_features: int, bias: bool = True, hp_dict=None, name: str = None,
@@ -273,12 +209,7 @@ class _TKLinearBase(HF.InferenceCacheMixin, nn.Module):
         self.first_factor = _empty(self.in_rank, self.in_features)
         self.core_tensor = _empty(self.out_rank, self.in_rank)
         self.last_factor = _empty(self.out_features, self.out_rank)
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_features))   # reference: uninitialised (TKLinear.py); see tt_layers._zero_bias
-            if dense_b is not None:
-                self.bias.data = dense_b
-        else:
-            self.register_parameter('bias', None)
+        make_bias(self, self.out_features, bias, dense_b)
         if dense_w is not None:
             core, u_out, u_in = _tucker_factors(dense_w, self.out_rank, self.in_rank)
             self.first_factor.data = u_in.t().contiguous()
@@ -300,13 +231,9 @@ class TKLinearM(_TKLinearBase):
         """Three products in the reference; here the small core is contracted into the input factor and the layer is one
         launch of the fused chain (`tadmm_ttlinear_fwd`: y = last (core first) x + bias, the out_rank-vector of a token in
         LDS) whenever out_rank fits it; otherwise three strided GEMMs."""
-        align = 8 if x.dtype in ops.HALF_DTYPES else 4
         params = (self.first_factor, self.core_tensor, self.last_factor)
-        # (the backward runs the fused kernel with the gradient as X: its row length out_features must be aligned too;
-        # float16 is inference only -- in grad mode it keeps the three products below)
-        if (HF.chain_dtype_ok(x, self.bias, *params) and HF.fused_rank_ok(self.out_rank) and x.is_cuda
-                and self.in_features % align == 0
-                and (self.out_features % align == 0 or not HF._needs_grad(x, self.bias, *params))):
+        # (float16 is inference only -- in grad mode it keeps the three products below)
+        if x.is_cuda and fused_linear_ok(x, self.bias, params, self.out_rank, self.in_features, self.out_features):
             grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
             if grad and x.dtype == torch.float32:
                 w_in = HF.mm(self.core_tensor, self.first_factor)             # (out_rank, in_features), differentiable

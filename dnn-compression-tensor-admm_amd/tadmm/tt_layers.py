@@ -27,12 +27,13 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 from torch.nn import init
-from torch.nn.modules.utils import _pair, _reverse_repeat_tuple
+from torch.nn.modules.utils import _pair
 
 from . import functional as HF
 from . import ops
 from . import ttd
 from ._cabi import KIND_TT_CONV, KIND_TT_LINEAR
+from ._layer_common import DenseConvMixin, fused_linear_ok, make_bias
 
 
 def _split_modes(tt_shapes, out_dim, has_kernel_mode):
@@ -52,14 +53,6 @@ def _split_modes(tt_shapes, out_dim, has_kernel_mode):
 
 def _empty(*shape):
     return nn.Parameter(torch.empty(*shape))
-
-
-def _zero_bias(n: int):
-    """Deliberate deviation: the reference allocates the bias with `torch.Tensor(n)` (TTLinear.py:53, TTConv.py:254) and
-    the M variants (and every layer built from `dense_w` without `dense_b`) never initialise it -- it holds whatever the
-    allocator hands out, NaNs included.  Zeros are one of the values that memory can hold; `reset_parameters` of the R
-    variants overwrites them as the reference does."""
-    return nn.Parameter(torch.zeros(n))
 
 
 def _decompose(dense_w: Tensor, tt_shapes, tt_ranks, kind):
@@ -114,12 +107,7 @@ class TTConv2dM(_TTConvBase):
         self.out_tt_cores = nn.ParameterList(
             [_empty(self.out_tt_ranks[i], self.out_tt_shapes[i], self.out_tt_ranks[i + 1])
              for i in range(self.out_tt_order)])
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_channels))
-            if dense_b is not None:
-                self.bias.data = dense_b
-        else:
-            self.register_parameter('bias', None)
+        make_bias(self, self.out_channels, bias, dense_b)
         if dense_w is not None:
             cores = _decompose(dense_w, self.tt_shapes, self.tt_ranks, KIND_TT_CONV)
             kq = self.out_tt_order
@@ -178,11 +166,11 @@ class TTConv2dM(_TTConvBase):
                 or not self.out_tt_order):
             return self._chains(x)[0]
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        n, pdt = HF._nplanes(x), HF.plane_dtype(x)
         if grad:
             w_in, w_out = self._factors()
-            p_in = p_out = None
+            planes = None
         else:
+            n = HF._nplanes(x)
             cache = self.__dict__.setdefault("_chain_cache", {})
             # keyed on the activation dtype: one plane means bfloat16 OR float16, and their planes differ
             key = (x.dtype, x.device, HF.param_key(*params, self.core_kernel))
@@ -190,30 +178,16 @@ class TTConv2dM(_TTConvBase):
                 with torch.no_grad():
                     w_in, w_out = self._factors()
                 cache.update(key=key, w=(w_in, w_out), planes=(HF.planes_of(w_in, n, like=x), HF.planes_of(w_out, n, like=x)))
-            (w_in, w_out), (p_in, p_out) = cache["w"], cache["planes"]
-        # the one-launch path builds no autograd node: only when NOTHING it reads wants a gradient (frozen cores with a
-        # trainable input / core kernel / bias keep the three differentiable launches below)
-        if (not grad and not HF._needs_grad(x, self.core_kernel, self.bias) and self.groups == 1
-                and ops.conv_chain_pays(x, w_in.shape[0], w_out.shape[1], self.kernel_size, self.stride, self.padding,
-                                        self.dilation)):
-            # small planes (<= 64 pixels): the whole layer in ONE launch, both intermediates in LDS (csrc/convchain.hip)
-            fkey = (key, "fused")
-            if cache.get("fkey") != fkey:
-                cache.update(fkey=fkey, fplanes=(ops.weight_planes(w_in, n, pad_rows=32, dtype=pdt),
-                                                 ops.conv_core_planes(self.core_kernel, n, dtype=pdt),
-                                                 ops.weight_planes(w_out, n, dtype=pdt)))
-            f1, f2, f3 = cache["fplanes"]
-            return ops.conv_chain(x, f1, f2, f3, self.bias, self.out_channels, self.kernel_size, self.stride, self.padding,
-                                  self.dilation)
-        y = HF.conv_chain_routed(self, x, w_in, w_out)           # grad mode, where ops.conv_chain_train_pays says so
+                self.__dict__.pop("_fused_cache", None)      # one-launch planes of the factors just replaced
+            (w_in, w_out), planes = cache["w"], cache["planes"]
+        # small planes (<= 64 pixels): the whole layer in ONE launch, both intermediates in LDS (csrc/convchain.hip).  In
+        # inference it builds no autograd node: only when NOTHING it reads wants a gradient (frozen cores with a
+        # trainable input / core kernel / bias take `functional.conv_chain` or the three differentiable launches)
+        y = HF.conv_chain_layer(self, x, w_in, w_out,
+                                inference=not grad and not HF._needs_grad(x, self.core_kernel, self.bias))
         if y is not None:
             return y
-        out = HF.pointwise(x, w_in, None, "tadmm_ttconv_chain_in", p_in)
-        mid = HF.core_conv_routed(self, out)                    # the native k x k kernel where it pays (csrc/coreconv.hip)
-        if mid is None:
-            core = self.core_kernel if x.dtype == self.core_kernel.dtype else self.core_kernel.to(x.dtype)
-            mid = F.conv2d(out, core, None, self.stride, self.padding, self.dilation, self.groups)
-        return HF.pointwise(mid, w_out, self.bias, "tadmm_ttconv_chain_out", p_out)
+        return HF.conv_stages(self, x, w_in, w_out, ("tadmm_ttconv_chain_in", "tadmm_ttconv_chain_out"), planes)[2]
 
     def forward_flops(self, x):                                   # TTConv.py:155-195
         out, tt_flops, (h2, w2) = self._chains(x, True)
@@ -235,22 +209,14 @@ def _chain_recover(cores: List[Tensor]) -> Tensor:
     return w
 
 
-class TTConv2dR(_TTConvBase):
+class TTConv2dR(DenseConvMixin, _TTConvBase):
     def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1,
                  groups: int = 1, bias: bool = True, padding_mode: str = 'zeros', hp_dict=None, name=str,
                  dense_w: Tensor = None, dense_b: Tensor = None):
         super().__init__()
         self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, padding_mode,
                     hp_dict, name)
-        if in_channels % groups != 0:
-            raise ValueError('in_channels must be divisible by groups')
-        if out_channels % groups != 0:
-            raise ValueError('out_channels must be divisible by groups')
-        valid_padding_modes = {'zeros', 'reflect', 'replicate', 'circular'}
-        if padding_mode not in valid_padding_modes:
-            raise ValueError("padding_mode must be one of {}, but got padding_mode='{}'".format(
-                valid_padding_modes, padding_mode))
-        self._reversed_padding_repeated_twice = _reverse_repeat_tuple(self.padding, 2)
+        self._init_dense_conv(in_channels, out_channels, groups, padding_mode)
         self.kernel_shape = [out_channels, in_channels // groups, *self.kernel_size]
         self.filter_dim = int(self.kernel_shape[2] * self.kernel_shape[3])
         self.out_tt_cores = nn.ParameterList(
@@ -259,12 +225,7 @@ class TTConv2dR(_TTConvBase):
         self.conv_core = _empty(self.out_tt_ranks[-1], self.filter_dim, self.in_tt_ranks[0])
         self.in_tt_cores = nn.ParameterList(
             [_empty(self.in_tt_ranks[i], self.in_tt_shapes[i], self.in_tt_ranks[i + 1]) for i in range(self.in_tt_order)])
-        if bias:
-            self.bias = _zero_bias(self.out_channels)
-            if dense_b is not None:
-                self.bias.data = dense_b
-        else:
-            self.register_parameter('bias', None)
+        make_bias(self, self.out_channels, bias, dense_b)
         if dense_w is not None:
             # reference quirk kept on purpose (TTConv.py:285-288): the (O,I,k^2) buffer is TT-decomposed
             # WITHOUT the (0,2,1) transpose, i.e. as a flat re-interpretation with modes out|k^2|in.
@@ -294,15 +255,6 @@ class TTConv2dR(_TTConvBase):
         w = _chain_recover(list(self.out_tt_cores) + [self.conv_core] + list(self.in_tt_cores))
         return w.reshape(self.out_channels, self.filter_dim, self.in_channels).reshape(self.kernel_shape)
 
-    def _conv_forward(self, x, weight):
-        if self.padding_mode != 'zeros':
-            return F.conv2d(F.pad(x, self._reversed_padding_repeated_twice, mode=self.padding_mode), weight, self.bias,
-                            self.stride, _pair(0), self.dilation, self.groups)
-        return F.conv2d(x, weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
-
-    def forward(self, x: Tensor) -> Tensor:
-        return self._conv_forward(x, self._recover_weight())
-
 
 class _TTLinearBase(HF.InferenceCacheMixin, nn.Module):
     def __init__(self, in_features: int, out_features: int, bias: bool = True, hp_dict=None, name: str = None,
@@ -319,12 +271,7 @@ class _TTLinearBase(HF.InferenceCacheMixin, nn.Module):
         self.tt_ranks = list(hp_dict.ranks[name])
         self.tt_cores = nn.ParameterList(
             [_empty(self.tt_ranks[i], self.tt_shapes[i], self.tt_ranks[i + 1]) for i in range(self.tt_order)])
-        if bias:
-            self.bias = _zero_bias(self.out_features)
-            if dense_b is not None:
-                self.bias.data = dense_b
-        else:
-            self.register_parameter('bias', None)
+        make_bias(self, self.out_features, bias, dense_b)
         if dense_w is not None:
             cores = _decompose(dense_w, self.tt_shapes, self.tt_ranks, KIND_TT_LINEAR)   # TTLinear.py:61-66
             for i, c in enumerate(cores):
@@ -350,13 +297,8 @@ class TTLinearM(_TTLinearBase):
 
     def _fused_ok(self, x):
         q = self.out_tt_order
-        align = 8 if x.dtype in ops.HALF_DTYPES else 4
-        if not (HF.chain_dtype_ok(x, self.bias, *self.tt_cores) and 0 < q < self.tt_order
-                and HF.fused_rank_ok(self.tt_ranks[q]) and self.in_features % align == 0):
-            return False
-        # the backward runs the same kernels with the gradient as X (row length out_features): a head whose width is
-        # not 16-byte aligned (10 classes) trains through the per-core chain instead
-        return self.out_features % align == 0 or not HF._needs_grad(x, self.bias, *self.tt_cores)
+        return 0 < q < self.tt_order and fused_linear_ok(x, self.bias, self.tt_cores, self.tt_ranks[q], self.in_features,
+                                                         self.out_features)
 
     def _dense_pays(self, x, r_q: int) -> bool:
         """bf16 / float16 inference only (float16 runs bf16's kernel on bf16's rule; measured at the four DeiT-small shapes: DESIGN.md section 12).  The contracted chain costs r_q (in + out) multiply-adds per token, the dense layer in * out:

@@ -231,10 +231,10 @@ def _reference(kind, layer, x64):
 @pytest.mark.parametrize("bf16", [False, True])
 @pytest.mark.parametrize("kind", ["ttm", "tkc", "tkm"])
 def test_layers_forced_onto_the_native_core_convolution(kind, bf16, monkeypatch):
-    from tadmm import ops, tk_layers, tt_layers
+    from tadmm import functional as HF, ops, tt_layers
     monkeypatch.setattr(ops, "core_conv_pays", lambda *a, **k: True)
-    monkeypatch.setattr(tt_layers, "F", _raising_functional())
-    monkeypatch.setattr(tk_layers, "F", _raising_functional())
+    monkeypatch.setattr(HF, "F", _raising_functional())            # the fallback conv2d of `functional.conv_stages`
+    monkeypatch.setattr(tt_layers, "F", _raising_functional())     # (tk_layers no longer imports it)
     torch.manual_seed(21)
     layer = _layers()[kind]()
     with torch.no_grad():

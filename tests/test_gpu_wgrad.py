@@ -9,7 +9,7 @@ kernel's error beside the error of the route it replaces (`ops.mm` on channel-ma
 bf16 at training size: the convolution layers (SVDConv2dC, TKConv2dC, TTConv2dM) hand bf16 activations to the chain
 kernels and so to `ops.wgrad` as bf16.  TTLinearM / TKLinearM take the fused chain for training in fp32 only; with bf16
 activations and trainable cores they run their per-core `mm` chain (fp32 products), so their bf16 tests below exercise
-that route, and the bf16 token-row route of `_ChainFused.backward` is tested through `functional.linear_chain` itself."""
+that route, and the bf16 token-row route of `_FusedChain.backward` is tested through `functional.linear_chain` itself."""
 import ctypes as C
 
 import pytest
@@ -391,7 +391,7 @@ def test_tklinearm_deit_qkv_bf16_activations():
 
 
 def test_linear_chain_bf16_token_rows_12608():
-    """`_ChainFused.backward` with bf16 token rows: bf16 `gr` / `h` against bf16 `x` / `g` in `ops.wgrad` (DeiT-S qkv
+    """`_FusedChain.backward` with bf16 token rows: bf16 `gr` / `h` against bf16 `x` / `g` in `ops.wgrad` (DeiT-S qkv
     factors: Win 256 x 384, Wout 1152 x 256)."""
     from tadmm import functional as HF
     g = torch.Generator().manual_seed(18)
