@@ -612,10 +612,9 @@ int tadmm_dgemm3_f64(tadmm_handle h, const double* A, const double* Gm, double* 
 }
 
 size_t tadmm_cholqr_scratch_bytes(int n, int ncols) {
-  const size_t cols64 = align_up(ncols, 64);
   return align_up(sizeof(DgemmDesc), 256) + align_up(sizeof(CholDesc), 256) + 2 * align_up((size_t)n * n * 8, 256) +
          align_up((size_t)n * 16 * 8, 256) + align_up((size_t)(n / 32) * (n / 32) * sizeof(BlockRef), 256) +
-         align_up((cols64 / 64) * sizeof(BlockRef), 256) + 256;
+         align_up((size_t)(ncols / kCholStrip) * sizeof(BlockRef), 256) + 256;
 }
 
 int tadmm_cholqr_f64(tadmm_handle h, double* YT, int n, int ncols, int ldy, void* scratch, size_t scratch_bytes,
@@ -634,7 +633,7 @@ int tadmm_cholqr_f64(tadmm_handle h, double* YT, int n, int ncols, int ldy, void
   double* Rm = (double*)(base + off); off += align_up((size_t)n * n * 8, 256);
   double* Wd = (double*)(base + off); off += align_up((size_t)n * 16 * 8, 256);
   BlockRef* mg = (BlockRef*)(base + off); off += align_up((size_t)(n / 32) * (n / 32) * sizeof(BlockRef), 256);
-  BlockRef* ms = (BlockRef*)(base + off); off += align_up((size_t)(ncols / 64) * sizeof(BlockRef), 256);
+  BlockRef* ms = (BlockRef*)(base + off); off += align_up((size_t)(ncols / kCholStrip) * sizeof(BlockRef), 256);
   int32_t* bad = (int32_t*)(base + off);
   DgemmDesc g;
   memset(&g, 0, sizeof g);
@@ -646,7 +645,7 @@ int tadmm_cholqr_f64(tadmm_handle h, double* YT, int n, int ncols, int ldy, void
   c.ring[0] = YT; c.ring[1] = YT; c.ring[2] = YT; c.rot = nullptr; c.sel = 0; c.ldy = ldy; c.ncols = ncols; c.bad = bad;
   std::vector<BlockRef> vg, vs;
   for (int b = 0; b < g.tiles_m * g.tiles_n; ++b) vg.push_back(BlockRef{0, b});
-  for (int b = 0; b < ncols / 64; ++b) vs.push_back(BlockRef{0, b});
+  for (int b = 0; b < ncols / kCholStrip; ++b) vs.push_back(BlockRef{0, b});
   HIP_OK(h, hipMemsetAsync(bad, 0, 4, s));
   HIP_OK(h, hipMemcpyAsync(gd, &g, sizeof g, hipMemcpyHostToDevice, s));
   HIP_OK(h, hipMemcpyAsync(cd, &c, sizeof c, hipMemcpyHostToDevice, s));

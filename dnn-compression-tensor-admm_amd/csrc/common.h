@@ -247,13 +247,14 @@ void launch_dgemm3(const DgemmDesc* descs_dev, const BlockRef* map_dev, int nblo
 // C = R^T R of an n x n Gram matrix (n multiple of 16, <= 256), one workgroup per problem, upper tiles resident in
 // registers; writes the off-diagonal tiles of R and the inverses Wd[k] = R_kk^{-T} of the diagonal tiles, which
 // is what the block forward substitution Q^T = R^{-T} Y^T (chol_solve) consumes.
+constexpr int kCholStrip = 16;          // columns of the image one chol_solve workgroup owns: a solve map has ncols / kCholStrip blocks
 struct CholDesc {
   const double* C; int32_t ldc;         // Gram matrix (symmetric; only the upper tiles are read)
   int32_t n;
   double* R; int32_t ldr;               // upper factor, off-diagonal tiles only are meaningful
   double* Wd;                           // [n/16][16*16] row-major inverse-transposed diagonal tiles
   double* ring[3]; const int32_t* rot; int32_t sel;   // block image Y^T [n][ldy] to be solved in place
-  int32_t ldy, ncols;                   // ncols multiple of 16 (a wave of chol_solve owns 16 columns)
+  int32_t ldy, ncols;                   // ncols multiple of kCholStrip (a workgroup of chol_solve owns one strip of columns)
   int32_t* bad;                         // set to 1 on a non-positive pivot (sticky, device word)
   const int32_t* gate; int32_t gate_min;
   int32_t* rot_out;                     // optional: *rot_out <- (*rot + sel) % 3 after the solve (new basis index)

@@ -385,7 +385,7 @@ static inline void filter_layout(FilterGroup& fg, const std::vector<FilterSpec>&
       c_comp.push_back(c);
       for (int b = 0; b < (cr + 3) / 4; ++b) { m_cform.push_back(BlockRef{ci, b}); m_cemit.push_back(BlockRef{ci, b}); }
       for (int b = 0; b < ((cr + TMW - 1) / TMW) * ((cr + TNW - 1) / TNW); ++b) m_cgram.push_back(BlockRef{ci, b});
-      for (int b = 0; b < (int)align_up(Npad, 64) / 64; ++b) m_csolve.push_back(BlockRef{ci, b});
+      for (int b = 0; b < Npad / kCholStrip; ++b) m_csolve.push_back(BlockRef{ci, b});
     }
 
     // Rayleigh-Ritz eigen-problem
@@ -410,7 +410,7 @@ static inline void filter_layout(FilterGroup& fg, const std::vector<FilterSpec>&
     for (int b = 0; b < (r32 / 32) * (Npad / 32); ++b) m_uform.push_back(BlockRef{i, b});     // NN kernel: 32x32 tiles
     for (int b = 0; b < ((r32 + TMW - 1) / TMW) * tn; ++b) m_verify.push_back(BlockRef{i, b});
     for (int b = 0; b < (sp.r + 3) / 4; ++b) m_emit.push_back(BlockRef{i, b});
-    for (int b = 0; b < (int)align_up(Npad, 64) / 64; ++b) m_solve.push_back(BlockRef{i, b});
+    for (int b = 0; b < Npad / kCholStrip; ++b) m_solve.push_back(BlockRef{i, b});
     (void)vh_off;
   }
   if (const char* e = getenv("TADMM_FILTER_XCD"); e && atoi(e)) {
