@@ -110,6 +110,16 @@ class TtmDesc(C.Structure):
     ]
 
 
+class LstmDesc(C.Structure):
+    _fields_ = [
+        ("Xp", C.c_void_p), ("W", C.c_void_p), ("h0", C.c_void_p), ("c0", C.c_void_p),
+        ("Y", C.c_void_p), ("hT", C.c_void_p), ("cT", C.c_void_p), ("G", C.c_void_p), ("C", C.c_void_p),
+        ("dY", C.c_void_p), ("dhT", C.c_void_p), ("dcT", C.c_void_p),
+        ("dZ", C.c_void_p), ("dh0", C.c_void_p), ("dc0", C.c_void_p),
+        ("T", C.c_int64), ("B", C.c_int64), ("H", C.c_int32), ("sigmoid", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -218,6 +228,11 @@ ABI = {
     "tadmm_ttm_gather_fits": (C.c_int, [C.POINTER(TtmDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "tadmm_ttm_gather_fwd": (C.c_int, [C.c_void_p, C.POINTER(TtmDesc), C.c_void_p]),
     "tadmm_ttm_gather_bwd": (C.c_int, [C.c_void_p, C.POINTER(TtmDesc), C.c_void_p]),
+    "tadmm_lstm_desc_bytes": (C.c_int, []),
+    "tadmm_lstm_fits": (C.c_int, [C.POINTER(LstmDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "tadmm_lstm_seq_fwd": (C.c_int, [C.c_void_p, C.POINTER(LstmDesc), C.c_void_p]),
+    "tadmm_lstm_seq_fwd_save": (C.c_int, [C.c_void_p, C.POINTER(LstmDesc), C.c_void_p]),
+    "tadmm_lstm_seq_bwd": (C.c_int, [C.c_void_p, C.POINTER(LstmDesc), C.c_void_p]),
     "tadmm_core_conv_desc_bytes": (C.c_int, []),
     "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
     "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
@@ -303,6 +318,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_wgrad_desc layout mismatch")
         if lib.tadmm_ttm_desc_bytes() != C.sizeof(TtmDesc):
             raise TadmmLibraryError(f"{path}: tadmm_ttm_desc layout mismatch")
+        if lib.tadmm_lstm_desc_bytes() != C.sizeof(LstmDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_lstm_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         _lib = lib

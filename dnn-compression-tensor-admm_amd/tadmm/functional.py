@@ -654,3 +654,110 @@ def ttm_embedding(cores, index: torch.Tensor, counter: torch.Tensor = None, rout
         return ttm_embedding_composed(cores, index, counter)
     y = _TtmGather.apply(index, counter, *cores)
     return y.reshape(tuple(index.shape) + (y.shape[1],))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# LSTM recurrence over a whole sequence (csrc/lstm.hip): the step function of ablation/tt_lstm_inference.py:44-77 for
+# all T steps in one launch, its backward through time in one launch; the products over all T*B tokens (weight and
+# bias gradients) go through `ops.wgrad` and a reduction.
+# ---------------------------------------------------------------------------------------------------------------
+LSTM_GATES = ("hardsigmoid", "sigmoid")
+
+
+class _LstmSeq(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xp, w_hh, h0, c0, sigmoid):
+        w = w_hh.detach()
+        planes = ops.lstm_planes(w)
+        grad = any(ctx.needs_input_grad[:4])
+        if not grad:
+            return ops.lstm_seq(xp, planes, h0, c0, sigmoid)
+        y, hT, cT, g, c = ops.lstm_seq_save(xp, planes, h0, c0, sigmoid)
+        ctx.save_for_backward(w, y, g, c, h0, c0)
+        ctx.sigmoid = sigmoid
+        return y, hT, cT
+
+    @staticmethod
+    def backward(ctx, dy, dhT, dcT):
+        w, y, g, c, h0, c0 = ctx.saved_tensors
+        T, B, H = y.shape
+        f32 = lambda t: None if t is None else (t if t.dtype == torch.float32 else t.float())
+        dz, dh0, dc0 = ops.lstm_seq_bwd(ops.lstm_planes(w, transpose=True), g, c, c0, f32(dy), f32(dhT), f32(dcT),
+                                        ctx.sigmoid)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            hprev = torch.empty_like(y)
+            if h0 is None:
+                hprev[0].zero_()
+            else:
+                hprev[0].copy_(h0)
+            hprev[1:].copy_(y[:-1])
+            dw = ops.wgrad(dz.view(T * B, 4 * H), hprev.view(T * B, H))
+        return (dz if ctx.needs_input_grad[0] else None, dw, dh0 if ctx.needs_input_grad[2] else None,
+                dc0 if ctx.needs_input_grad[3] else None, None)
+
+
+def _lstm_gate(z: torch.Tensor, gate: str) -> torch.Tensor:
+    return torch.sigmoid(z) if gate == "sigmoid" else F.hardsigmoid(z)
+
+
+def lstm_sequence_composed(xp: torch.Tensor, w_hh: torch.Tensor, h0: torch.Tensor = None, c0: torch.Tensor = None,
+                           gate: str = "hardsigmoid"):
+    """`lstm_sequence` as the reference composes a step (tt_lstm_inference.py:61-77): one `mm` and torch pointwise
+    operations per step, on the device, under autograd.  The route of hidden sizes `ops.lstm_fits` refuses and of the
+    classes `ops.lstm_seq_pays` sends here, and the yardstick of scripts/bench_lstm.py."""
+    if gate not in LSTM_GATES:
+        raise ValueError(f"lstm_sequence: gate is 'hardsigmoid' or 'sigmoid' (got {gate!r})")
+    T, B, H = xp.shape[0], xp.shape[1], w_hh.shape[1]
+    h = xp.new_zeros(B, H) if h0 is None else h0
+    c = xp.new_zeros(B, H) if c0 is None else c0
+    wt = w_hh.t()
+    ys = []
+    for t in range(T):
+        z = xp[t] + mm(h, wt)
+        zi, zf, zg, zo = z.split(H, dim=1)
+        c = _lstm_gate(zf, gate) * c + _lstm_gate(zi, gate) * torch.tanh(zg)
+        h = _lstm_gate(zo, gate) * torch.tanh(c)
+        ys.append(h)
+    return torch.stack(ys), (h, c)
+
+
+def lstm_sequence(xp: torch.Tensor, w_hh: torch.Tensor, h0: torch.Tensor = None, c0: torch.Tensor = None,
+                  gate: str = "hardsigmoid", route: str = None):
+    """(y (T, B, H), (h_T, c_T)) of the LSTM recurrence  z_t = xp[t] + h_{t-1} w_hh^T,  i, f, o = S(z), g = tanh(z),
+    c_t = f c_{t-1} + i g,  h_t = o tanh(c_t),  gate order [i | f | g | o], S = Hardsigmoid (the reference) or the logistic
+    function (`gate="sigmoid"`, torch.nn.LSTM).  xp (T, B, 4H) float32 carries the input map and the bias; h0, c0 (B, H)
+    default to zeros.  Differentiable in xp, w_hh, h0 and c0.  Hidden sizes the launch takes (`ops.lstm_fits`) run
+    `tadmm_lstm_seq_fwd` / `_bwd` where the measured rule `ops.lstm_seq_pays` says so, everything else the composed step
+    loop.  `route`: None (by that rule), "launch" (shapes the launch does not take raise) or "composed".  ValueError for
+    another route or gate and for shapes that do not agree, TadmmError for tensors that are not float32 on the device."""
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"lstm_sequence: route is None, 'launch' or 'composed' (got {route!r})")
+    if gate not in LSTM_GATES:
+        raise ValueError(f"lstm_sequence: gate is 'hardsigmoid' or 'sigmoid' (got {gate!r})")
+    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1] or w_hh.shape[1] < 1:
+        raise ValueError(f"lstm_sequence: w_hh must be (4H, H) (got {tuple(w_hh.shape)})")
+    H = w_hh.shape[1]
+    if xp.dim() != 3 or xp.shape[2] != 4 * H or xp.shape[0] < 1 or xp.shape[1] < 1:
+        raise ValueError(f"lstm_sequence: xp must be (T >= 1, B >= 1, {4 * H}) (got {tuple(xp.shape)})")
+    T, B = xp.shape[0], xp.shape[1]
+    for t, what in ((h0, "h0"), (c0, "c0")):
+        if t is not None and tuple(t.shape) != (B, H):
+            raise ValueError(f"lstm_sequence: {what} must be ({B}, {H}) (got {tuple(t.shape)})")
+    for t, what in ((xp, "xp"), (w_hh, "w_hh"), (h0, "h0"), (c0, "c0")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise TadmmError(-1, f"lstm_sequence: {what} must live on the HIP device (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise TadmmError(-1, f"lstm_sequence: {what} must be float32 (got {t.dtype}); the recurrence has no "
+                                 "bfloat16 / float16 form")
+    if route is None:
+        grad = torch.is_grad_enabled() and _needs_grad(xp, w_hh, h0, c0)
+        launch = ops.lstm_fits(H) and ops.lstm_seq_pays(T, B, H, grad)
+    else:
+        launch = route == "launch"
+    if not launch:
+        return lstm_sequence_composed(xp, w_hh, h0, c0, gate)
+    y, hT, cT = _LstmSeq.apply(xp, w_hh, h0, c0, gate == "sigmoid")
+    return y, (hT, cT)

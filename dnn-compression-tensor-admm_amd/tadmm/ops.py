@@ -1608,3 +1608,176 @@ def ttm_gather_pays(n, m, r, tokens: int, grad: bool = False) -> bool:
     if not grad:
         return True
     return len(n) == 1 and tokens <= TTM_GRAD_MAX_TOKENS
+
+
+# ------------------------------------------------------------------ LSTM recurrence over a sequence (csrc/lstm.hip)
+LSTM_MAX_H = 256                 # kLstmMaxH of csrc/lstm.hip: four waves of at most four 16-unit tiles
+LSTM_ROWS = 16                   # batch rows of a workgroup
+LSTM_LDS_BYTES = 160 * 1024
+
+
+def lstm_plan(H: int):
+    """(fits, LDS bytes of the larger launch, batch rows per workgroup) for hidden size H: `tadmm_lstm_fits`, a pure
+    function of H.  Host only.  ValueError for H < 1; (False, 0, 16) for a hidden size the launch does not take."""
+    if int(H) < 1:
+        raise ValueError(f"lstm: the hidden size must be positive (got {H})")
+    desc = _cabi.LstmDesc()
+    desc.H = min(int(H), 2 ** 31 - 1)
+    nbytes, rows = C.c_size_t(), C.c_int()
+    rc = _cabi.load().tadmm_lstm_fits(C.byref(desc), C.byref(nbytes), C.byref(rows))
+    if rc < 0:
+        raise TadmmError(rc, "tadmm_lstm_fits: invalid descriptor")
+    return bool(rc), int(nbytes.value), int(rows.value)
+
+
+def lstm_fits(H: int) -> bool:
+    """True when the one-launch recurrence takes hidden size H (1 <= H <= 256).  False sends
+    `functional.lstm_sequence` down the composed step loop.  Pure host logic."""
+    return lstm_plan(H)[0]
+
+
+def lstm_planes(w_hh: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    """Three bf16 planes of the hidden-to-hidden weight (4H, H), gate order [i | f | g | o], as csrc/lstm.hip reads them:
+    every gate's H rows padded to Hp = ceil16(H) with zeros, so that unit u of gate g is row g * Hp + u, then packed with
+    `weight_planes(…, 3, pad_cols=32)`: (3, 4Hp/16, ceil32(H)/32, 64, 8).  `transpose=True`: the planes of the
+    TRANSPOSED padded weight (H, 4Hp) -> (3, Hp/16, 4Hp/32, 64, 8), what the backward multiplies dz by."""
+    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1] or w_hh.shape[1] < 1:
+        raise ValueError(f"lstm_planes: w_hh must be (4H, H) (got {tuple(w_hh.shape)})")
+    if not w_hh.is_cuda:
+        raise TadmmError(-1, "lstm_planes: the weight must live on a HIP device; there is no CPU path")
+    H = w_hh.shape[1]
+    Hp = -(-H // 16) * 16
+    wp = torch.zeros(4, Hp, H, dtype=torch.float32, device=w_hh.device)
+    wp[:, :H] = w_hh.detach().float().view(4, H, H)
+    wp = wp.view(4 * Hp, H)
+    return weight_planes(wp.t() if transpose else wp, 3, 16, 32)
+
+
+def _lstm_tensor(t, shape, who, what, optional=False):
+    if t is None:
+        if optional:
+            return None
+        raise TadmmError(-1, f"{who}: {what} is required")
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TadmmError(-1, f"{who}: {what} must live on a HIP device; there is no CPU path")
+    if t.dtype != torch.float32:
+        raise TadmmError(-1, f"{who}: {what} must be float32 (got {t.dtype})")
+    if tuple(t.shape) != tuple(shape):
+        raise TadmmError(-1, f"{who}: {what} must be {tuple(shape)} (got {tuple(t.shape)})")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _lstm_out(out, shape, like, who, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != like.device
+            or tuple(out.shape) != tuple(shape) or not out.is_contiguous()):
+        raise TadmmError(-1, f"{who}: {what} must be a contiguous float32 {tuple(shape)} tensor on {like.device}")
+    return out
+
+
+def _lstm_check_planes(planes, H, transpose, dev, who):
+    Hp, Kp = -(-H // 16) * 16, -(-H // 32) * 32
+    want = (3, Hp // 16, 4 * Hp // 32, 64, 8) if transpose else (3, 4 * Hp // 16, Kp // 32, 64, 8)
+    if (not isinstance(planes, torch.Tensor) or planes.dtype != torch.bfloat16 or tuple(planes.shape) != want
+            or planes.device != dev or not planes.is_contiguous()):
+        raise TadmmError(-1, f"{who}: the weight planes must be `lstm_planes(w_hh, transpose={transpose})`: bfloat16 "
+                             f"{want} on {dev}")
+
+
+def _lstm_fwd(entry, xp, planes, h0, c0, sigmoid, save, out):
+    who = "lstm_seq_save" if save else "lstm_seq"
+    if not isinstance(xp, torch.Tensor) or xp.dim() != 3 or xp.shape[2] % 4 or xp.shape[2] == 0:
+        raise TadmmError(-1, f"{who}: xp must be (T, B, 4H)")
+    T, B, H = xp.shape[0], xp.shape[1], xp.shape[2] // 4
+    xp = _lstm_tensor(xp, (T, B, 4 * H), who, "xp")
+    dev = xp.device
+    if not lstm_fits(H):
+        raise TadmmError(-5, f"{who}: H = {H}, the launch takes 1 <= H <= {LSTM_MAX_H}")
+    _lstm_check_planes(planes, H, False, dev, who)
+    h0 = _lstm_tensor(h0, (B, H), who, "h0", optional=True)
+    c0 = _lstm_tensor(c0, (B, H), who, "c0", optional=True)
+    out = dict(out or {})
+    y = _lstm_out(out.get("y"), (T, B, H), xp, who, "y")
+    hT = _lstm_out(out.get("hT"), (B, H), xp, who, "hT")
+    cT = _lstm_out(out.get("cT"), (B, H), xp, who, "cT")
+    d = _cabi.LstmDesc()
+    d.Xp, d.W, d.Y, d.hT, d.cT = xp.data_ptr(), planes.data_ptr(), y.data_ptr(), hT.data_ptr(), cT.data_ptr()
+    d.h0 = None if h0 is None else h0.data_ptr()
+    d.c0 = None if c0 is None else c0.data_ptr()
+    d.T, d.B, d.H, d.sigmoid = T, B, H, int(bool(sigmoid))
+    res = (y, hT, cT)
+    if save:
+        g = torch.empty(T, B, 4 * H, dtype=torch.float32, device=dev)
+        c = torch.empty(T, B, H, dtype=torch.float32, device=dev)
+        d.G, d.C = g.data_ptr(), c.data_ptr()
+        res = (y, hT, cT, g, c)
+    if T == 0 or B == 0:
+        raise TadmmError(-1, f"{who}: T >= 1 and B >= 1 are required")
+    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h.check(getattr(h.lib, entry)(h.ptr, C.byref(d), _stream(dev)))
+    return res
+
+
+def lstm_seq(xp: torch.Tensor, planes: torch.Tensor, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None,
+             sigmoid: bool = False, out: Optional[dict] = None):
+    """(y (T, B, H), hT, cT (B, H)) of the LSTM recurrence over the whole sequence in ONE launch (`tadmm_lstm_seq_fwd`).
+    xp (T, B, 4H) float32: the input pre-activations, bias included, gate order [i | f | g | o]; planes:
+    `lstm_planes(w_hh)`; h0, c0 (B, H), zeros when None; i, f, o through Hardsigmoid, or the logistic function with
+    `sigmoid`.  `out`: optional {"y", "hT", "cT"} tensors to write into (any 4-byte aligned contiguous view)."""
+    return _lstm_fwd("tadmm_lstm_seq_fwd", xp, planes, h0, c0, sigmoid, False, out)
+
+
+def lstm_seq_save(xp: torch.Tensor, planes: torch.Tensor, h0: Optional[torch.Tensor] = None,
+                  c0: Optional[torch.Tensor] = None, sigmoid: bool = False, out: Optional[dict] = None):
+    """`lstm_seq` for a training step (`tadmm_lstm_seq_fwd_save`): (y, hT, cT, G, C) with G (T, B, 4H) the four gate
+    activations and C (T, B, H) every cell state, what `lstm_seq_bwd` reads.  y, hT, cT are bitwise those of `lstm_seq`."""
+    return _lstm_fwd("tadmm_lstm_seq_fwd_save", xp, planes, h0, c0, sigmoid, True, out)
+
+
+def lstm_seq_bwd(planes_t: torch.Tensor, g: torch.Tensor, c: torch.Tensor, c0: Optional[torch.Tensor] = None,
+                 dy: Optional[torch.Tensor] = None, dhT: Optional[torch.Tensor] = None, dcT: Optional[torch.Tensor] = None,
+                 sigmoid: bool = False, dz: Optional[torch.Tensor] = None):
+    """Backward through time in one launch (`tadmm_lstm_seq_bwd`): (dZ (T, B, 4H), dh0, dc0 (B, H)) from the saved G, C
+    of `lstm_seq_save`, c0 and the gradients of y, hT, cT (each zeros when None).  planes_t:
+    `lstm_planes(w_hh, transpose=True)`.  dZ is the gradient of the pre-activations and so of xp; the weight gradient is
+    `wgrad(dZ.view(T*B, 4H), Hprev.view(T*B, H))` with Hprev = [h0, y[0 .. T-2]], the bias gradient `dZ.sum((0, 1))`.
+    `dz`: optional tensor to write dZ into."""
+    who = "lstm_seq_bwd"
+    if not isinstance(c, torch.Tensor) or c.dim() != 3:
+        raise TadmmError(-1, f"{who}: C must be (T, B, H)")
+    T, B, H = c.shape
+    c = _lstm_tensor(c, (T, B, H), who, "C")
+    dev = c.device
+    if T == 0 or B == 0 or H == 0:
+        raise TadmmError(-1, f"{who}: T >= 1, B >= 1 and H >= 1 are required")
+    if not lstm_fits(H):
+        raise TadmmError(-5, f"{who}: H = {H}, the launch takes 1 <= H <= {LSTM_MAX_H}")
+    g = _lstm_tensor(g, (T, B, 4 * H), who, "G")
+    _lstm_check_planes(planes_t, H, True, dev, who)
+    c0 = _lstm_tensor(c0, (B, H), who, "c0", optional=True)
+    dy = _lstm_tensor(dy, (T, B, H), who, "dy", optional=True)
+    dhT = _lstm_tensor(dhT, (B, H), who, "dhT", optional=True)
+    dcT = _lstm_tensor(dcT, (B, H), who, "dcT", optional=True)
+    dz = _lstm_out(dz, (T, B, 4 * H), c, who, "dz")
+    dh0 = torch.empty(B, H, dtype=torch.float32, device=dev)
+    dc0 = torch.empty(B, H, dtype=torch.float32, device=dev)
+    d = _cabi.LstmDesc()
+    d.W, d.G, d.C, d.dZ, d.dh0, d.dc0 = planes_t.data_ptr(), g.data_ptr(), c.data_ptr(), dz.data_ptr(), dh0.data_ptr(), \
+        dc0.data_ptr()
+    for name, t in (("c0", c0), ("dY", dy), ("dhT", dhT), ("dcT", dcT)):
+        setattr(d, name, None if t is None else t.data_ptr())
+    d.T, d.B, d.H, d.sigmoid = T, B, H, int(bool(sigmoid))
+    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h.check(h.lib.tadmm_lstm_seq_bwd(h.ptr, C.byref(d), _stream(dev)))
+    return dz, dh0, dc0
+
+
+def lstm_seq_pays(T: int, B: int, H: int, grad: bool = False) -> bool:
+    """True when `functional.lstm_sequence` sends a shape the launch takes to the launch and not to the composed step
+    loop.  A pure function of the sequence length, the batch, the hidden size and whether gradients will be asked for.
+    Measured (scripts/bench_lstm.py) at H in {64, 128, 256}, T in {6, 64}, B in {1, 16, 64, 256}:
+    the launch is ahead of the composed loop beyond the spread of both in every class, forward (2.1x - 18.5x) and
+    training step (3.3x - 30.6x); the smallest margin is H = 256, T = 6, B = 256.  No class of the table goes the other
+    way, so every shape the launch takes is sent to it.  Batches beyond 256 rows were not measured."""
+    return True

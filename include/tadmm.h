@@ -535,6 +535,56 @@ int tadmm_ttm_gather_fits(const tadmm_ttm_desc* d, size_t* lds_bytes, int* tile)
 int tadmm_ttm_gather_fwd(tadmm_handle h, const tadmm_ttm_desc* d, void* stream);
 int tadmm_ttm_gather_bwd(tadmm_handle h, const tadmm_ttm_desc* d, void* stream);
 
+/* ---- LSTM recurrence over a whole sequence (csrc/lstm.hip) ------------------------------------------------------------
+ * ablation/tt_lstm_inference.py:44-77 for all T steps in ONE launch.  H = hidden size, gate order z = [i | f | g | o]:
+ *   z_t = Xp[t] + h_{t-1} Whh^T,  i, f, o = S(z),  g = tanh(z),  c_t = f c_{t-1} + i g,  h_t = o tanh(c_t)
+ * S = Hardsigmoid (sigmoid == 0) or the logistic function (sigmoid == 1).  Xp (T, B, 4H) holds the input pre-activations
+ * with the bias in them; Y (T, B, H) = every h_t; hT, cT, h0, c0 (B, H); all float32 and contiguous, any 4-byte aligned
+ * base (16-byte stores and loads where the base is 16-byte aligned and H % 4 == 0, single elements otherwise).  h0 / c0
+ * NULL: zeros.  A workgroup owns 16 batch rows and walks the sequence alone; h stays in LDS, c in registers.
+ *   forward  W = the three bf16 planes of Whh packed gate by gate, each gate's H rows padded to Hp = ceil16(H), columns
+ *            to ceil32(H): (3, 4Hp/16, ceil32(H)/32, 64, 8) in the fragment-major order of the chain entries
+ *            (tadmm.ops.lstm_planes builds it), 16-byte aligned.
+ *   _save    also writes G (T, B, 4H), the four gate ACTIVATIONS, and C (T, B, H), every c_t; Y, hT, cT are bitwise
+ *            those of the plain entry.
+ *   backward W = the planes of the transposed padded weight, (3, Hp/16, 4Hp/32, 64, 8) (lstm_planes(transpose=True)).
+ *            Reads G, C, c0 and the output gradients dY (T, B, H), dhT, dcT (B, H) (each NULL: zeros); writes dZ
+ *            (T, B, 4H) -- the gradient of the pre-activations, which is also the gradient of Xp -- and dh0, dc0 (B, H;
+ *            NULL: not written).  The Hardsigmoid derivative is 1/6 where the saved activation is strictly between 0
+ *            and 1, else 0.  dWhh = dZ^T [h0, Y[0 .. T-2]] and dbias = sum dZ are left to the caller (tadmm_wgrad).
+ * tadmm_lstm_fits is host only and reads H alone: 1 when the launches take it (1 <= H <= 256: four waves of at most four
+ * 16-unit tiles; the backward's LDS image of dz would allow 368), 0 when not (*lds_bytes is then 0),
+ * TADMM_ERR_INVALID for a NULL descriptor or H < 1.  *lds_bytes (nullable): dynamic LDS of the larger launch;
+ * *rows_per_wg (nullable): 16.  The launches return TADMM_ERR_UNSUPPORTED where _fits returns 0 and TADMM_ERR_INVALID for
+ * T < 1, B < 1, sigmoid outside {0, 1}, T * B * 4H beyond 2^40 or a required pointer that is NULL or misaligned; nothing
+ * is launched in any of these cases.  No atomics; bitwise reproducible; rows never influence one another. */
+typedef struct {
+  const float* Xp;                            /* forward */
+  const void* W;                              /* forward: planes of Whh; backward: planes of its transpose */
+  const float* h0;                            /* forward; nullable */
+  const float* c0;                            /* forward and backward; nullable */
+  float* Y;                                   /* forward */
+  float* hT;                                  /* forward */
+  float* cT;                                  /* forward */
+  float* G;                                   /* _save writes it, backward reads it */
+  float* C;                                   /* _save writes it, backward reads it */
+  const float* dY;                            /* backward; nullable */
+  const float* dhT;                           /* backward; nullable */
+  const float* dcT;                           /* backward; nullable */
+  float* dZ;                                  /* backward */
+  float* dh0;                                 /* backward; nullable */
+  float* dc0;                                 /* backward; nullable */
+  int64_t T, B;
+  int32_t H;
+  int32_t sigmoid;                            /* 0: Hardsigmoid, 1: logistic */
+} tadmm_lstm_desc;
+/* sizeof(tadmm_lstm_desc) as the library was built */
+int tadmm_lstm_desc_bytes(void);
+int tadmm_lstm_fits(const tadmm_lstm_desc* d, size_t* lds_bytes, int* rows_per_wg);
+int tadmm_lstm_seq_fwd(tadmm_handle h, const tadmm_lstm_desc* d, void* stream);
+int tadmm_lstm_seq_fwd_save(tadmm_handle h, const tadmm_lstm_desc* d, void* stream);
+int tadmm_lstm_seq_bwd(tadmm_handle h, const tadmm_lstm_desc* d, void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
