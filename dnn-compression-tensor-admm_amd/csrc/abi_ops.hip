@@ -194,6 +194,7 @@ static int chain_entry(tadmm_handle h, const tadmm_chain_desc* c, int fused, con
   }
   const int rc = svdconv ? launch_svdconv_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_)
                          : launch_tt_chain(d, c->dtype, c->tile_tokens, (hipStream_t)stream_);
+  if (rc > 0) CTX_FAIL(h, TADMM_ERR_HIP, "chain: dynamic-LDS opt-in failed: %s", hipGetErrorString((hipError_t)rc));
   if (rc != 0) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "chain: token tile does not fit the LDS");
   HIP_OK(h, hipGetLastError());
   (void)who;
@@ -268,6 +269,14 @@ static void conv_chain_operands(const tadmm_conv_chain_desc* c, ConvChainDesc& d
   d.x_vec = ((d.H * d.W) % epl == 0 && (((uintptr_t)c->X) & 15) == 0) ? 1 : 0;
 }
 
+static int conv_chain_launch(tadmm_handle h, const ConvChainDesc& d, int dtype, hipStream_t s) {
+  const int rc = launch_tt_conv(d, dtype, s);
+  if (rc > 0) CTX_FAIL(h, TADMM_ERR_HIP, "conv chain: dynamic-LDS opt-in failed: %s", hipGetErrorString((hipError_t)rc));
+  if (rc != 0) CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: the intermediates do not fit the LDS");
+  HIP_OK(h, hipGetLastError());
+  return TADMM_OK;
+}
+
 int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* c, void* stream_) {
   DeviceGuard device_guard(h);
   if (!h || !c) return TADMM_ERR_INVALID;
@@ -279,10 +288,7 @@ int tadmm_ttconv_fused(tadmm_handle h, const tadmm_conv_chain_desc* c, void* str
     CTX_FAIL(h, TADMM_ERR_INVALID, "conv chain: weight planes too small or misaligned");
   conv_chain_operands(c, d);
   d.bias = c->bias;
-  if (launch_tt_conv(d, c->dtype, (hipStream_t)stream_) != 0)
-    CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: the intermediates do not fit the LDS");
-  HIP_OK(h, hipGetLastError());
-  return TADMM_OK;
+  return conv_chain_launch(h, d, c->dtype, (hipStream_t)stream_);
 }
 
 // forward with saved intermediates (mode FWD) and data gradient (mode BWD): statuses as tadmm_core_conv_*
@@ -313,10 +319,7 @@ static int conv_chain_train(tadmm_handle h, const tadmm_conv_chain_desc* c, int 
   // S1 is product 1's tensor, S2 product 2's: H1, H2 forward; dH2, dH1 in the data gradient
   d.S1 = bwd ? s2 : s1; d.S2 = bwd ? s1 : s2;
   d.r1t = bwd ? r2 : r1; d.r2t = bwd ? r1 : r2;
-  if (launch_tt_conv(d, c->dtype, (hipStream_t)stream_) != 0)
-    CTX_FAIL(h, TADMM_ERR_UNSUPPORTED, "conv chain: the intermediates do not fit the LDS");
-  HIP_OK(h, hipGetLastError());
-  return TADMM_OK;
+  return conv_chain_launch(h, d, c->dtype, (hipStream_t)stream_);
 }
 
 int tadmm_ttconv_fused_save(tadmm_handle h, const tadmm_conv_chain_desc* d, int r1, int r2, void* H1, void* H2, void* stream) {
@@ -474,8 +477,8 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
     int* verdict = (int*)(done + 8);          // [8..9] verdict of the single-launch solvers
     HIP_OK(h, hipMemsetAsync(done, 0, 64, s));
     const bool direct = eig_small_direct_on();
-    if (direct) launch_eig_small_direct(edev, 1, nullptr, fast, verdict, s);
-    launch_jacobi_small(edev, 1, Npad, tol, 60, nullptr, verdict, s, false, direct ? fast : nullptr);
+    if (direct) HIP_OK(h, launch_eig_small_direct(edev, 1, nullptr, fast, verdict, s));
+    HIP_OK(h, launch_jacobi_small(edev, 1, Npad, tol, 60, nullptr, verdict, s, false, direct ? fast : nullptr));
     int hv[6] = {0, 0, 0, 0, 0, 0};
     HIP_OK(h, hipMemcpyAsync(hv, done + 4, sizeof hv, hipMemcpyDeviceToHost, s));
     HIP_OK(h, hipStreamSynchronize(s));
@@ -492,10 +495,10 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   for (; gs < 40 && !conv; ++gs) {
     for (int t = 0; t < units - 1; ++t, ++tick) {
       if (mode >= 2) {
-        if (t == 0) launch_jacobi_self(edev, m_self, L.self.nblocks, tick, tol, 1, ld, s);
-        launch_jacobi_tick3(edev, m_tick, L.tick.nblocks, tick, tol, ld, s);
+        if (t == 0) HIP_OK(h, launch_jacobi_self(edev, m_self, L.self.nblocks, tick, tol, 1, ld, s));
+        HIP_OK(h, launch_jacobi_tick3(edev, m_tick, L.tick.nblocks, tick, tol, ld, s));
       } else {
-        launch_jacobi_tick(edev, m_tick, L.tick.nblocks, tick, tol, 1, L.tick_lds, mode == 1, s);
+        HIP_OK(h, launch_jacobi_tick(edev, m_tick, L.tick.nblocks, tick, tol, 1, L.tick_lds, mode == 1, s));
       }
     }
     HIP_OK(h, hipMemcpyAsync(hoff, offs, 24, hipMemcpyDeviceToHost, s));

@@ -30,6 +30,7 @@
 // the MFMAs of step s (one wave per SIMD: nothing else hides the L2 latency).  Workgroups walk the weights in rotated
 // order (by blockIdx) so that the CUs of an XCD do not all ask the same L2 channel for the same line at once.
 #include "chain_common.h"
+#include "host.h"
 
 namespace tadmm {
 namespace {
@@ -218,14 +219,9 @@ int launch_variant(const ChainDesc& d, hipStream_t s) {
   size_t lds = (size_t)2 * P * TM * (KC + kPad) * 2;
   if (FUSED) lds += (size_t)P * TM * (d.R + kPad) * 2;
   if (lds > 160 * 1024) return -1;
-  static bool attr_done[64] = {false};
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (!attr_done[devi & 63]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_done[devi & 63] = true;
-  }
+  static DynLdsOptIn allow_lds;
+  const hipError_t e = allow_lds(kern, 160 * 1024);
+  if (e != hipSuccess) return (int)e;
   const int gx = (int)((d.T + TM - 1) / TM);
   const int gy = FUSED ? 1 : (d.R + 4 * kNB1 * 16 - 1) / (4 * kNB1 * 16);
   ChainDesc dd = d;
@@ -322,7 +318,7 @@ int launch_fused_save_ks(const ChainDesc& d, int dtype, int tile_tokens, hipStre
 }  // namespace
 
 // Fused chain with image input and image output of the same plane size (tadmm_svdconv_fwd / _bwd).  -1 when the shape
-// does not fit (the caller validated it already).
+// does not fit (the caller validated it already); > 0: the hipError_t of a refused dynamic-LDS opt-in.
 int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
   if (d.T <= 0) return 0;
   if (!d.fused || d.x_hw <= 0 || d.y_hw != d.x_hw || d.R % 64 || d.R > 256) return -1;
@@ -336,8 +332,8 @@ int launch_svdconv_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStre
 }
 
 // dtype 0: fp32 in/out through three bf16 planes per operand; dtype 1: bf16 in/out; dtype 2: binary16 in/out, the
-// one-plane kernels with the f16 MFMA and conversions.  Returns 0, or -1 when the shape
-// does not fit the kernel (the caller reports it; there is no other path inside the library).
+// one-plane kernels with the f16 MFMA and conversions.  Returns 0, -1 when the shape does not fit the kernel (the caller
+// reports it; there is no other path inside the library), or > 0: the hipError_t of a refused dynamic-LDS opt-in.
 int launch_tt_chain(const ChainDesc& d, int dtype, int tile_tokens, hipStream_t s) {
   if (d.T <= 0) return 0;
   if (!d.fused) {

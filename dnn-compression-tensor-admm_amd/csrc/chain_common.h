@@ -10,6 +10,7 @@ namespace tadmm {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float float4v_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // weight pointers carry their address space: through arrays and selects hipcc otherwise degrades them to generic
 // pointers, and flat loads count on vmcnt AND lgkmcnt -- every wait behind them becomes a full drain
 typedef const uint16_t __attribute__((address_space(1)))* gw_t;
@@ -208,6 +209,33 @@ __device__ __forceinline__ void load_x(bf16x8_t (&a)[P][TM / 16], const uint16_t
 #pragma unroll
     for (int mt = 0; mt < TM / 16; ++mt)
       a[p][mt] = *reinterpret_cast<const bf16x8_t*>(&img[(p * TM + 16 * mt + r) * ld + 32 * kloc + 8 * q]);
+}
+
+// ---- the gathered product of the convolutions (coreconv.hip, convchain.hip) ----
+// gathered token fragments of one k-step: row `row` of the LDS image [P][prow][ld] (or zeros), three or one plane
+template <int P>
+__device__ __forceinline__ void gather_x(bf16x8_t (&a)[P], const uint16_t* img, int prow, int ld, int row, int kloc, int q) {
+  const int rr = row < 0 ? 0 : row;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(&img[(p * prow + rr) * ld + 32 * kloc + 8 * q]);
+    if (row < 0) v = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
+    a[p] = v;
+  }
+}
+
+template <int P, int NB, bool F16 = false>
+__device__ __forceinline__ void mma_tile(const bf16x8_t (&a)[P], const bf16x8_t (&b)[P][NB], float4v_t (&acc)[NB]) {
+  if constexpr (P == 1) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[j] = mfma16<F16>(b[0][j], a[0], acc[j]);
+  } else {
+    constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+    for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[pb[pr]][j], a[pa[pr]], acc[j], 0, 0, 0);
+  }
 }
 
 // ---- tap <-> pixel maps of a convolution axis (coreconv.hip, convchain.hip).  transposed 0: destination = output

@@ -99,30 +99,30 @@ size_t jacobi_tick2_lds_bytes(int ld_max);   // same for the LDS-resident super-
 bool jacobi_tick2_fits(int ld_max);
 // super=false: one workgroup per pair of 8-column blocks (nb/2 per problem, nb-1 ticks per sweep)
 // super=true : one workgroup per pair of 16-column super-blocks (nb/4 per problem, nb/2-1 ticks per sweep)
-void launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                        int inner_sweeps, size_t lds_bytes, bool super, hipStream_t s);
+hipError_t launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
+                              int inner_sweeps, size_t lds_bytes, bool super, hipStream_t s);
 void dump_stamps();
 size_t jacobi_tick3_lds_bytes(int ld_max);
 bool jacobi_tick3_fits(int ld_max);
 // tick3: super-pair kernel with carried self-Grams (one cross-Gram per launch, round-2 solve overlapped with the
 // round-1 update).  Needs launch_jacobi_self on the first tick of every sweep (it refreshes EigDesc::sblk).
-void launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                         int ld_max, hipStream_t s);
+hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
+                               int ld_max, hipStream_t s);
 // rows of an eigen-solver image are whole 1 KiB chunks (128 doubles: LDS-DMA loads).  The LDS-resident pair kernel
 // holds 16 such rows up to ld = 1152; longer rows go through the streamed pair kernel.
 constexpr int kLdResidentMax = 1152;
 static inline int eig_ld(int N) { return (N + 127) / 128 * 128; }
 // once-per-sweep companion of tick3 (tick1 in self mode): within-block pairs + refresh of the carried self-Grams
-void launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                        int inner_sweeps, int ld_max, hipStream_t s);
+hipError_t launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
+                              int inner_sweeps, int ld_max, hipStream_t s);
 // whole eigen-solve of small problems (Npad <= 64) in one launch, one workgroup per problem; converged flags go to
 // verdict_pinned[1 + p]
 bool jacobi_small_fits(int npad_max);
 // warm: reserve the second LDS image a warm-started problem needs (EigDesc::warm)
 // `fast_done` (optional): per-problem words set by eig_small_direct_kernel -- those problems are finished already
-void launch_jacobi_small(const EigDesc* descs_dev, int nprob, int npad_max, double tol, int max_sweeps,
-                         const int32_t* skip, int* verdict_pinned, hipStream_t s, bool warm,
-                         const int32_t* fast_done = nullptr);
+hipError_t launch_jacobi_small(const EigDesc* descs_dev, int nprob, int npad_max, double tol, int max_sweeps,
+                               const int32_t* skip, int* verdict_pinned, hipStream_t s, bool warm,
+                               const int32_t* fast_done = nullptr);
 // tridiag.hip: direct solver (tridiagonalisation + bisection + inverse iteration) for problems of at most 64 columns;
 // verified results only, everything else is left to jacobi_small_kernel
 bool eig_small_direct_on();
@@ -131,8 +131,8 @@ bool eig_mid_direct_on();
 bool eig_mid_direct_size(int n);
 size_t eig_mid_scratch_bytes(int n);
 void launch_eig_mid_direct(const EigDesc* descs_dev, int nprob, int ns, const int32_t* skip, int* verdict_pinned, hipStream_t s);
-void launch_eig_small_direct(const EigDesc* descs_dev, int nprob, const int32_t* skip, int32_t* fast_done_dev,
-                             int* verdict_pinned, hipStream_t s);
+hipError_t launch_eig_small_direct(const EigDesc* descs_dev, int nprob, const int32_t* skip, int32_t* fast_done_dev,
+                                   int* verdict_pinned, hipStream_t s);
 void launch_eig_norms(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, hipStream_t s,
                       const int32_t* skip = nullptr);
 // npad_max: largest padded problem size of the launch (sizes the eigenvalue table in LDS; 0 = the largest supported)

@@ -31,38 +31,12 @@
 // by the test conv_load applies (base, plane size and run length).
 // Wider planes (more than 64 output columns) and intermediates beyond the LDS take the three-launch path (tadmm_ttconv_chain_in, the device library's conv2d, tadmm_ttconv_chain_out).
 #include "chain_common.h"
+#include "host.h"
 
 namespace tadmm {
 namespace {
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 constexpr size_t kConvMaxLds = 160 * 1024;
-
-// gathered token fragments of one k-step: row src[mt] of the LDS image (or zeros), three or one plane
-template <int P>
-__device__ __forceinline__ void gather_x(bf16x8_t (&a)[P], const uint16_t* img, int prow, int ld, int row, int kloc, int q) {
-  const int rr = row < 0 ? 0 : row;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(&img[(p * prow + rr) * ld + 32 * kloc + 8 * q]);
-    if (row < 0) v = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
-    a[p] = v;
-  }
-}
-
-template <int P, int NB, bool F16 = false>
-__device__ __forceinline__ void mma_tile(const bf16x8_t (&a)[P], const bf16x8_t (&b)[P][NB], float4v_t (&acc)[NB]) {
-  if constexpr (P == 1) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) acc[j] = mfma16<F16>(b[0][j], a[0], acc[j]);
-  } else {
-    constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-    for (int pr = 0; pr < 6; ++pr)
-#pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[pb[pr]][j], a[pa[pr]], acc[j], 0, 0, 0);
-  }
-}
 
 // acc (features 4q..4q+3 of token row0 + r, tile j) -> P planes of an LDS image [P][prow][ld]
 template <int P, int TM, int NB, bool F16 = false>
@@ -457,14 +431,9 @@ int launch_conv_mode(const ConvChainDesc& d, hipStream_t s) {
   auto kern = tt_conv_kernel<P, TM, KC, NBW, T, BWD, SAVE>;
   const size_t lds = conv_lds_bytes<P, KC>(d);
   if (lds > kConvMaxLds) return -1;
-  static bool attr_done[64] = {false};
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (!attr_done[devi & 63]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvMaxLds);
-    (void)hipGetLastError();
-    attr_done[devi & 63] = true;
-  }
+  static DynLdsOptIn allow_lds;
+  const hipError_t e = allow_lds(kern, kConvMaxLds);
+  if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(kern, dim3(d.B * d.tiles), dim3(256), lds, s, d);
   return 0;
 }
@@ -516,7 +485,7 @@ bool plan_tt_conv(ConvChainDesc& d, int dtype, size_t* lds_bytes) {
 }
 
 // dtype 0: fp32 through three bf16 planes; 1: bf16; 2: binary16 (forward only, nothing saved).  -1: the intermediates do not fit the LDS (the caller takes the
-// three-launch path).
+// three-launch path); > 0: the hipError_t of a refused dynamic-LDS opt-in.
 int launch_tt_conv(const ConvChainDesc& d, int dtype, hipStream_t s) {
   if (d.B <= 0) return 0;
   if (d.TM == 32) {

@@ -28,8 +28,6 @@
 namespace tadmm {
 namespace {
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int kCcTok = 64;               // destination pixels per workgroup
 constexpr size_t kCcMaxLds = 96 * 1024;  // halo buffers + tap table: one workgroup never takes more
 
@@ -92,32 +90,6 @@ __device__ __forceinline__ void halo_load(uint16_t* img, const T* S, int64_t img
         }
       }
     }
-  }
-}
-
-// gathered token fragments of one k-step: row `row` of the LDS image (or zeros), three or one plane
-template <int P>
-__device__ __forceinline__ void gather_rows(bf16x8_t (&a)[P], const uint16_t* img, int prow, int ld, int row, int kloc, int q) {
-  const int rr = row < 0 ? 0 : row;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(&img[(p * prow + rr) * ld + 32 * kloc + 8 * q]);
-    if (row < 0) v = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
-    a[p] = v;
-  }
-}
-
-template <int P, int NB>
-__device__ __forceinline__ void mma_rows(const bf16x8_t (&a)[P], const bf16x8_t (&b)[P][NB], float4v_t (&acc)[NB]) {
-  if constexpr (P == 1) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0][j], a[0], acc[j], 0, 0, 0);
-  } else {
-    constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-    for (int pr = 0; pr < 6; ++pr)
-#pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[pb[pr]][j], a[pa[pr]], acc[j], 0, 0, 0);
   }
 }
 
@@ -213,8 +185,8 @@ __global__ __launch_bounds__(256) void core_conv_kernel(const CoreConvArgs d) {
           for (int mt = 0; mt < MT; ++mt) {
             const int row = live ? (int)tab[tap * kCcTok + 16 * mt + r] : -1;
             bf16x8_t a[P];
-            gather_rows<P>(a, Xc, d.HP, LDK, row, ks, q);
-            mma_rows<P, NBW>(a, b[u], acc[mt]);
+            gather_x<P>(a, Xc, d.HP, LDK, row, ks, q);
+            mma_tile<P, NBW>(a, b[u], acc[mt]);
           }
           tap = ntap; ks = nk;
         }
@@ -291,15 +263,9 @@ template <int P, int KC, int NBW, typename T>
 hipError_t cc_launch_nbw(const CoreConvArgs& a, hipStream_t s) {
   auto kern = core_conv_kernel<P, KC, NBW, T>;
   const size_t lds = cc_lds_bytes<P, KC>(a.HP, a.kh * a.kw);
-  static bool attr_done[64] = {false};
-  int devi = 0;
-  hipError_t e = hipGetDevice(&devi);
+  static DynLdsOptIn allow_lds;
+  const hipError_t e = allow_lds(kern, kCcMaxLds);
   if (e != hipSuccess) return e;
-  if (!attr_done[devi & 63]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCcMaxLds);
-    if (e != hipSuccess) return e;
-    attr_done[devi & 63] = true;
-  }
   const unsigned gy = (unsigned)((a.N + 4 * NBW * 16 - 1) / (4 * NBW * 16));
   hipLaunchKernelGGL(kern, dim3((unsigned)a.B * a.tiles_y * a.tiles_x, gy), dim3(256), lds, s, a);
   return hipGetLastError();

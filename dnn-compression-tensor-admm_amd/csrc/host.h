@@ -6,6 +6,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,6 +50,25 @@ struct DeviceGuard {
   ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// Raises a kernel's dynamic-LDS limit above the default 64 KiB, once per device (the attribute belongs to the device's
+// code object).  A launcher keeps one static instance per kernel instantiation.  The flags are atomic: the two lanes of a
+// projection plan launch from two host threads, and setting the attribute twice is harmless.  A failed call is returned
+// and leaves the flag clear; every launcher hands it to the ABI caller as TADMM_ERR_HIP.
+struct DynLdsOptIn {
+  std::atomic<bool> done[64] = {};
+  template <class K> hipError_t operator()(K kernel, size_t bytes) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::atomic<bool>& flag = done[dev & 63];
+    if (flag.load(std::memory_order_acquire)) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) flag.store(true, std::memory_order_release);
+    else (void)hipGetLastError();      // reported through the return value: not left behind for the next HIP call
+    return e;
+  }
 };
 
 // core convolution (coreconv.hip): descriptor checks shared with its weight gradient (wgrad.hip), and the launch
@@ -418,8 +438,8 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
       // direct route first (tridiag.hip); the Jacobi launch behind it skips what that one solved and verified.  The flag
       // words live in the group's `prev` scratch (doubles of the tick path's convergence kernel, unused here).
       int32_t* fast = (g.prev_dev && eig_small_direct_on()) ? reinterpret_cast<int32_t*>(g.prev_dev) : nullptr;
-      if (fast) launch_eig_small_direct(g.ed, g.neig, g.skip, fast, poll.host, s);
-      launch_jacobi_small(g.ed, g.neig, g.npad_max, tol, std::max(max_sweeps, 60), g.skip, poll.host, s, g.warm, fast);
+      if (fast) HIP_OK(h, launch_eig_small_direct(g.ed, g.neig, g.skip, fast, poll.host, s));
+      HIP_OK(h, launch_jacobi_small(g.ed, g.neig, g.npad_max, tol, std::max(max_sweeps, 60), g.skip, poll.host, s, g.warm, fast));
       if (timed) {
         float ms = 0.f;
         (void)hipEventRecord(jt->b, s);
@@ -482,10 +502,10 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
         bool any_first = false;     // does any unfinished problem start a sweep of its own at this tick?
         for (int q = 0; q < g.neig && !any_first; ++q)
           any_first = !known_done[q] && g.players[q] > 1 && (tick % (g.aligned ? g.gsteps : g.players[q] - 1)) == 0;
-        if (any_first) launch_jacobi_self(g.ed, g.self_map, g.self_blocks, tick, tol, inner_sweeps, g.ld_max, s);
+        if (any_first) HIP_OK(h, launch_jacobi_self(g.ed, g.self_map, g.self_blocks, tick, tol, inner_sweeps, g.ld_max, s));
         const bool timed = jt && jt->on;
         if (timed) (void)hipEventRecord(jt->a, s);
-        launch_jacobi_tick3(g.ed, g.tick_map, g.tick_blocks, tick, tol, g.ld_max, s);
+        HIP_OK(h, launch_jacobi_tick3(g.ed, g.tick_map, g.tick_blocks, tick, tol, g.ld_max, s));
         if (timed) {
           float ms = 0.f;
           (void)hipEventRecord(jt->b, s);
@@ -505,7 +525,7 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
           }
         }
       } else {
-        launch_jacobi_tick(g.ed, g.tick_map, g.tick_blocks, tick, tol, inner_sweeps, g.tick_lds, g.mode == 1, s);
+        HIP_OK(h, launch_jacobi_tick(g.ed, g.tick_map, g.tick_blocks, tick, tol, inner_sweeps, g.tick_lds, g.mode == 1, s));
       }
     }
     launch_jacobi_conv(g.ed, g.neig, tick, tol, g.mode >= 1, g.prev_dev, poll.host + (size_t)(gs & 1) * poll.stride, s);

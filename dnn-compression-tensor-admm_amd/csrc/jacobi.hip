@@ -31,7 +31,7 @@
 // target scales accordingly (exactly low-rank inputs would otherwise never terminate).  A problem is
 // converged when a whole sweep saw nothing above `tol` (Jacobi converges quadratically, so tol = 1e-9 leaves
 // ~1e-16 after that sweep) or, on the tick path, when the quadratic-phase prediction of jacobi_conv_kernel says so.
-#include "common.h"
+#include "host.h"
 #include <algorithm>
 #include <cstdio>
 
@@ -1159,24 +1159,20 @@ __global__ __launch_bounds__(256) void jacobi_small_kernel(const EigDesc* __rest
 
 bool jacobi_small_fits(int npad_max) { return npad_max <= kSmallNpad; }
 
-void launch_jacobi_small(const EigDesc* descs_dev, int nprob, int npad_max, double tol, int max_sweeps,
-                         const int32_t* skip, int* verdict_pinned, hipStream_t s, bool warm, const int32_t* fast_done) {
-  if (nprob <= 0) return;
+hipError_t launch_jacobi_small(const EigDesc* descs_dev, int nprob, int npad_max, double tol, int max_sweeps,
+                               const int32_t* skip, int* verdict_pinned, hipStream_t s, bool warm, const int32_t* fast_done) {
+  if (nprob <= 0) return hipSuccess;
   // X image | 4 wave scratches | red[8] + flags (8 doubles) | second image (warm start only)
   const size_t lds = ((size_t)npad_max * (npad_max + 2) * (warm ? 2 : 1) + 4 * kSmallWaveScratch + 16) * 8;
   if (lds > 64 * 1024) {                     // two images of a 64-column problem: above the default dynamic-LDS cap
-    static bool attr_done[64] = {false};     // per device: the attribute belongs to the device's code object
-    int devi = 0;
-    (void)hipGetDevice(&devi);
-    if (!attr_done[devi & 63]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_small_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipGetLastError();
-      attr_done[devi & 63] = true;
-    }
+    // the kernel carries 16 bytes of static LDS (warm_bad): as for tick2, the full 160 KiB as dynamic LDS is refused
+    static DynLdsOptIn allow_lds;
+    const hipError_t e = allow_lds(jacobi_small_kernel, 160 * 1024 - 256);
+    if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(jacobi_small_kernel, dim3(nprob), dim3(256), lds, s, descs_dev, skip, tol, max_sweeps,
                      verdict_pinned, fast_done);
+  return hipSuccess;
 }
 
 #ifdef TADMM_STAMPS
@@ -1345,80 +1341,60 @@ size_t jacobi_tick3_lds_bytes(int ld_max) {
   return ((size_t)kSuper * (ld_max + 2) + 2048 + 2 * (3 * kPair * kHP)) * 8 + 16;
 }
 bool jacobi_tick3_fits(int ld_max) { return jacobi_tick3_lds_bytes(ld_max) <= 160 * 1024; }
-void launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                         int ld_max, hipStream_t s) {
-  if (nblocks <= 0) return;
-  static bool attr_done[64] = {false};       // per device: the attribute belongs to the device's code object
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  bool& attr_set = attr_done[devi & 63];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_tick3_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_set = true;
-  }
+hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
+                               int ld_max, hipStream_t s) {
+  if (nblocks <= 0) return hipSuccess;
+  static DynLdsOptIn allow_lds;
+  hipError_t e = allow_lds(jacobi_tick3_kernel, 160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(jacobi_tick3_kernel, dim3(nblocks), dim3(512), jacobi_tick3_lds_bytes(ld_max), s, descs_dev, map_dev,
                      tick, tol);
-  const hipError_t e = hipPeekAtLastError();
+  e = hipPeekAtLastError();
   if (e != hipSuccess)
     fprintf(stderr, "[tadmm] jacobi tick3 launch failed: %s (blocks=%d lds=%zu)\n", hipGetErrorString(e), nblocks,
             jacobi_tick3_lds_bytes(ld_max));
+  return hipSuccess;
 }
 size_t jacobi_tick2_lds_bytes(int ld_max) { return ((size_t)kSuper * (ld_max + 2) + 2 * kPairScratchDoubles) * 8; }
 bool jacobi_tick2_fits(int ld_max) { return jacobi_tick2_lds_bytes(ld_max) <= 160 * 1024 - 256; }
 
-void launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                        int inner_sweeps, int ld_max, hipStream_t s) {
-  if (nblocks <= 0) return;
-  static bool attr_done[64] = {false};
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  bool& attr_set = attr_done[devi & 63];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_tick_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_set = true;
-  }
+static DynLdsOptIn allow_tick_lds;      // jacobi_tick_kernel has two launchers: the self pass and the plain pair tick
+
+hipError_t launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
+                              int inner_sweeps, int ld_max, hipStream_t s) {
+  if (nblocks <= 0) return hipSuccess;
+  const hipError_t e = allow_tick_lds(jacobi_tick_kernel, 160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), jacobi_tick_lds_bytes(ld_max), s, descs_dev, map_dev,
                      tick, tol, inner_sweeps, 1);
+  return hipSuccess;
 }
 
-void launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                        int inner_sweeps, size_t lds_bytes, bool super, hipStream_t s) {
-  if (nblocks <= 0) return;
-  static bool attr_done[64] = {false};
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  bool& attr_set = attr_done[devi & 63];
-  if (!attr_set) {   // allow the full 160 KiB of a CU as dynamic LDS (default cap is 64 KiB)
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_tick_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+hipError_t launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
+                              int inner_sweeps, size_t lds_bytes, bool super, hipStream_t s) {
+  if (nblocks <= 0) return hipSuccess;
+  hipError_t e;
+  if (super) {
     // tick2 carries 256 bytes of static LDS: asking for the full 160 KiB as dynamic LDS is refused (invalid argument)
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_tick2_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_tick_stream_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e1 != hipSuccess || e2 != hipSuccess)
-      fprintf(stderr, "[tadmm] hipFuncSetAttribute(max dynamic LDS): %s / %s\n", hipGetErrorString(e1),
-              hipGetErrorString(e2));
-    (void)hipGetLastError();
-    attr_set = true;
-  }
-  if (super)
+    static DynLdsOptIn allow_lds;
+    if ((e = allow_lds(jacobi_tick2_kernel, 160 * 1024 - 256)) != hipSuccess) return e;
     hipLaunchKernelGGL(jacobi_tick2_kernel, dim3(nblocks), dim3(512), lds_bytes, s, descs_dev, map_dev, tick, tol,
                        inner_sweeps);
-  else if (lds_bytes > 160 * 1024)      // rows too long for an LDS-resident pair: streamed pair kernel
+  } else if (lds_bytes > 160 * 1024) {  // rows too long for an LDS-resident pair: streamed pair kernel
+    static DynLdsOptIn allow_lds;
+    if ((e = allow_lds(jacobi_tick_stream_kernel, 160 * 1024)) != hipSuccess) return e;
     hipLaunchKernelGGL(jacobi_tick_stream_kernel, dim3(nblocks), dim3(256), jacobi_tick_stream_lds_bytes(), s, descs_dev,
                        map_dev, tick, tol);
-  else
+  } else {
+    if ((e = allow_tick_lds(jacobi_tick_kernel, 160 * 1024)) != hipSuccess) return e;
     hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), lds_bytes, s, descs_dev, map_dev, tick, tol,
                        inner_sweeps, 0);
-  hipError_t e = hipPeekAtLastError();
+  }
+  e = hipPeekAtLastError();
   if (e != hipSuccess)
     fprintf(stderr, "[tadmm] jacobi tick launch failed: %s (blocks=%d lds=%zu super=%d)\n", hipGetErrorString(e),
             nblocks, lds_bytes, (int)super);
+  return hipSuccess;
 }
 void launch_eig_norms(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, hipStream_t s,
                       const int32_t* skip) {

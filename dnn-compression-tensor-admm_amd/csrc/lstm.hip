@@ -371,21 +371,18 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_seq_bwd_kernel(const LstmAr
   }
 }
 
-template <class K> hipError_t lstm_allow_lds(K kern, size_t lds) {
-  if (lds <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLstmMaxLds);
-}
-
 template <int TPW, bool SAVE, bool SIGMOID> hipError_t lstm_launch_fwd(const LstmArgs& a, unsigned blocks, size_t lds, hipStream_t s) {
   auto kern = lstm_seq_kernel<TPW, SAVE, SIGMOID>;
-  const hipError_t e = lstm_allow_lds(kern, lds);
+  static DynLdsOptIn allow_lds;
+  const hipError_t e = lds > 64 * 1024 ? allow_lds(kern, kLstmMaxLds) : hipSuccess;
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kLstmThreads), lds, s, a);
   return hipGetLastError();
 }
 template <int TPW, bool SIGMOID> hipError_t lstm_launch_bwd(const LstmArgs& a, unsigned blocks, size_t lds, hipStream_t s) {
   auto kern = lstm_seq_bwd_kernel<TPW, SIGMOID>;
-  const hipError_t e = lstm_allow_lds(kern, lds);
+  static DynLdsOptIn allow_lds;
+  const hipError_t e = lds > 64 * 1024 ? allow_lds(kern, kLstmMaxLds) : hipSuccess;
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kLstmThreads), lds, s, a);
   return hipGetLastError();

@@ -360,23 +360,11 @@ int stiefel_check(tadmm_handle h, int n, const tadmm_stiefel_desc* descs, size_t
   return TADMM_OK;
 }
 
-// raises the kernel's dynamic-LDS limit once per device
-int stiefel_allow_lds(tadmm_handle h, const void* kernel, bool* done) {
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (!done[devi & 63]) {
-    HIP_OK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStfMaxLds));
-    done[devi & 63] = true;
-  }
-  return TADMM_OK;
-}
-
 int stiefel_launch(tadmm_stiefel_plan p, int mode, double lr, double mom, double damp, double wd, int nesterov,
                    int32_t* status, hipStream_t s) {
   tadmm_handle h = p->h;
-  static bool attr_done[64] = {false};
-  const int rc = stiefel_allow_lds(h, reinterpret_cast<const void*>(stiefel_kernel), attr_done);
-  if (rc != TADMM_OK) return rc;
+  static DynLdsOptIn allow_lds;
+  HIP_OK(h, allow_lds(stiefel_kernel, kStfMaxLds));
   hipLaunchKernelGGL(stiefel_kernel, dim3(p->n), dim3(kStfThreads), p->lds, s, p->descs, mode, lr, mom, damp, wd,
                      nesterov, status);
   HIP_OK(h, hipGetLastError());
@@ -385,9 +373,8 @@ int stiefel_launch(tadmm_stiefel_plan p, int mode, double lr, double mom, double
 
 int stiefel_adam_launch(tadmm_stiefel_plan p, double lr, double wd, const StfAdam& ad, int32_t* status, hipStream_t s) {
   tadmm_handle h = p->h;
-  static bool attr_done[64] = {false};
-  const int rc = stiefel_allow_lds(h, reinterpret_cast<const void*>(stiefel_adam_kernel), attr_done);
-  if (rc != TADMM_OK) return rc;
+  static DynLdsOptIn allow_lds;
+  HIP_OK(h, allow_lds(stiefel_adam_kernel, kStfMaxLds));
   hipLaunchKernelGGL(stiefel_adam_kernel, dim3(p->n), dim3(kStfThreads), p->lds, s, p->descs, lr, wd, ad, status);
   HIP_OK(h, hipGetLastError());
   return TADMM_OK;

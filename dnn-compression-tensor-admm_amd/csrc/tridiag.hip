@@ -23,6 +23,7 @@
 // Output convention = jacobi_small_kernel's: row j of XT = lambda_j * v_j for the computed pairs (the leading
 // min(N, r + 2)), zero rows for the rest (they sort last in eig_sort_kernel and are never extracted).
 #include "tridiag_common.h"
+#include "host.h"
 
 namespace tadmm {
 
@@ -546,18 +547,12 @@ bool eig_small_direct_on() {
   return !(e && !atoi(e));
 }
 
-void launch_eig_small_direct(const EigDesc* descs_dev, int nprob, const int32_t* skip, int32_t* fast_done_dev,
-                             int* verdict_pinned, hipStream_t s) {
-  if (nprob <= 0) return;
-  static bool attr_done[64] = {false};
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (!attr_done[devi & 63]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(eig_small_direct_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_done[devi & 63] = true;
-  }
+hipError_t launch_eig_small_direct(const EigDesc* descs_dev, int nprob, const int32_t* skip, int32_t* fast_done_dev,
+                                   int* verdict_pinned, hipStream_t s) {
+  if (nprob <= 0) return hipSuccess;
+  static DynLdsOptIn allow_lds;
+  const hipError_t e = allow_lds(eig_small_direct_kernel, 160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(eig_small_direct_kernel, dim3(nprob), dim3(256), kTLdsBytes, s, descs_dev, skip, fast_done_dev,
                      verdict_pinned);
 #ifdef TADMM_TRI_STAMPS
@@ -570,6 +565,7 @@ void launch_eig_small_direct(const EigDesc* descs_dev, int nprob, const int32_t*
               h[8], h[9], h[10], h[11], h[12]);
   }
 #endif
+  return hipSuccess;
 }
 
 }  // namespace tadmm

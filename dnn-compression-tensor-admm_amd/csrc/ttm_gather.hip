@@ -315,11 +315,6 @@ __global__ __launch_bounds__(kTtmBwdThreads) void ttm_gather_bwd_kernel(TtmArgs 
   }
 }
 
-template <class K> hipError_t ttm_allow_lds(K kern, size_t lds) {
-  if (lds <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTtmMaxLds);
-}
-
 int ttm_args(tadmm_ctx_s* h, const tadmm_ttm_desc* c, TtmGeom& g, TtmArgs& a) {
   const int rc = ttm_geom(c, g);
   if (rc != TADMM_OK) CTX_FAIL(h, rc, "ttm_gather: 1 <= d <= 4, r_0 = 1 and positive sizes are required");
@@ -373,7 +368,8 @@ int tadmm_ttm_gather_fwd(tadmm_handle h, const tadmm_ttm_desc* d, void* stream) 
   if (!d->Y || ((uintptr_t)d->Y & 3) || !d->bad_count || ((uintptr_t)d->bad_count & 3))
     CTX_FAIL(h, TADMM_ERR_INVALID, "ttm_gather_fwd: Y or bad_count is null or misaligned");
   a.Y = d->Y; a.bad = d->bad_count;
-  HIP_OK(h, ttm_allow_lds(ttm_gather_fwd_kernel, g.fwd_lds));
+  static DynLdsOptIn allow_lds;
+  if (g.fwd_lds > 64 * 1024) HIP_OK(h, allow_lds(ttm_gather_fwd_kernel, kTtmMaxLds));
   const int64_t blocks = (a.B + g.tile - 1) / g.tile;
   hipLaunchKernelGGL(ttm_gather_fwd_kernel, dim3((unsigned)blocks), dim3(kTtmFwdThreads), g.fwd_lds, (hipStream_t)stream, a);
   HIP_OK(h, hipGetLastError());
@@ -395,7 +391,8 @@ int tadmm_ttm_gather_bwd(tadmm_handle h, const tadmm_ttm_desc* d, void* stream) 
         ((uintptr_t)d->offsets[j] & 7))
       CTX_FAIL(h, TADMM_ERR_INVALID, "ttm_gather_bwd: dcores / order / offsets of core %d are null or misaligned", j);
   }
-  HIP_OK(h, ttm_allow_lds(ttm_gather_bwd_kernel, g.bwd_lds));
+  static DynLdsOptIn allow_lds;
+  if (g.bwd_lds > 64 * 1024) HIP_OK(h, allow_lds(ttm_gather_bwd_kernel, kTtmMaxLds));
   for (int j = 0; j < g.d; ++j) {
     if (!d->dcores[j]) continue;
     a.k = j; a.dG = d->dcores[j]; a.order = d->order[j]; a.offs = d->offsets[j];

@@ -359,23 +359,16 @@ int wgrad_geom(tadmm_handle h, const tadmm_wgrad_desc* d, WgradGeom& g) {
   return TADMM_OK;
 }
 
-// Tiles above 64 KiB of LDS need the attribute once per device and instantiation (a handle is not thread-safe, and
-// setting it twice is harmless: the flag is only a shortcut, as in chain.hip); a refusal is reported with the size.
+// Tiles above 64 KiB of LDS need the dynamic-LDS opt-in (host.h); a refusal is reported with the size.
 template <int P, int TM, int TN, typename TIn, bool IMG>
 hipError_t wgrad_launch(const WgradArgs& a, hipStream_t s, size_t* lds_out) {
   auto kern = wgrad_kernel<P, TM, TN, TIn, IMG>;
   constexpr size_t lds = wgrad_lds_bytes<P, TM, TN>();
   *lds_out = lds;
   if (lds > 64 * 1024) {
-    static bool attr_done[64] = {false};
-    int devi = 0;
-    hipError_t e = hipGetDevice(&devi);
+    static DynLdsOptIn allow_lds;
+    const hipError_t e = allow_lds(kern, lds);
     if (e != hipSuccess) return e;
-    if (!attr_done[devi & 63]) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_done[devi & 63] = true;
-    }
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles * a.slices), dim3(256), lds, s, a);
   return hipGetLastError();
@@ -581,15 +574,9 @@ hipError_t core_wgrad_launch(const CoreWgradArgs& a, hipStream_t s, size_t* lds_
   constexpr size_t lds = wgrad_lds_bytes<P, TM, TN>();
   *lds_out = lds;
   if (lds > 64 * 1024) {
-    static bool attr_done[64] = {false};
-    int devi = 0;
-    hipError_t e = hipGetDevice(&devi);
+    static DynLdsOptIn allow_lds;
+    const hipError_t e = allow_lds(kern, lds);
     if (e != hipSuccess) return e;
-    if (!attr_done[devi & 63]) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_done[devi & 63] = true;
-    }
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)a.g.tiles * a.g.slices, (unsigned)(a.kh * a.kw)), dim3(256), lds, s, a);
   return hipGetLastError();

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import functools
 import weakref
 from typing import List, Optional, Sequence
 
@@ -18,20 +19,119 @@ from ._cabi import (FLAG_SKIP_ROTATIONS, KIND_SVD, KIND_TT_CONV, KIND_TT_LINEAR,
                     LayerDesc, StiefelDesc, TadmmError, make_layer_desc)
 
 
-def _require_cuda(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise TadmmError(-1, f"{what} must live on a HIP device (got {t.device}); there is no CPU path")
-    if t.dtype != torch.float32 and what != "G":
-        raise TadmmError(-1, f"{what} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise TadmmError(-1, f"{what} must be contiguous")
+def _handle(device) -> Handle:
+    """The library handle of a torch device; a device without an index is the current one."""
+    return Handle.get(device.index if device.index is not None else torch.cuda.current_device())
 
 
 def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-class ProjectionPlan:
+def _operand(t, who: str, what: str, dtypes=None, shape=None, layout: Optional[str] = "raise"):
+    """The one check of a device operand; returns the tensor to hand to the library.  `who` (the entry; may be empty)
+    and `what` (the operand) word the message.  `t` must be a tensor on a HIP device, of one of `dtypes` and exactly of
+    `shape` (each checked when given).  `layout`: a non-contiguous tensor is an error ("raise"), is replaced by
+    `.contiguous()` ("copy"), or has a layout rule of its own at the call site (None)."""
+    name = f"{who}: {what}" if who else what
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+        raise TadmmError(-1, f"{name} must live on a HIP device (got {where}); there is no CPU path")
+    if dtypes is not None and t.dtype not in dtypes:
+        want = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise TadmmError(-1, f"{name} must be {want} (got {t.dtype})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise TadmmError(-1, f"{name} must be {tuple(shape)} (got {tuple(t.shape)})")
+    if layout is not None and not t.is_contiguous():
+        if layout != "copy":
+            raise TadmmError(-1, f"{name} must be contiguous")
+        t = t.contiguous()
+    return t
+
+
+def _output(out, shape, dtype, device, name: str, fresh=torch.empty, strided_rows: bool = False):
+    """The caller's output tensor where given, else a `fresh` one: `dtype`, `device` and exactly `shape`, contiguous --
+    or, with `strided_rows`, any row stride under a unit column stride."""
+    if out is None:
+        return fresh(shape, dtype=dtype, device=device)
+    ok = isinstance(out, torch.Tensor) and out.dtype == dtype and out.device == device and tuple(out.shape) == tuple(shape)
+    if ok:
+        ok = (shape[-1] <= 1 or out.stride(-1) == 1) if strided_rows else out.is_contiguous()
+    if not ok:
+        how = "with unit column stride" if strided_rows else "contiguous"
+        raise TadmmError(-1, f"{name} must be a {dtype} {tuple(shape)} tensor on {device}, {how}")
+    return out
+
+
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    """The uint8 device buffer of a scratch size the library reported."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+class _LayerPlan:
+    """What the grouped projections share: W / U / Z of every layer validated and captured by pointer, the workspace
+    the library sizes, the per-layer ||W-Z||^2 buffer, run / enable_timing / close, and the teardown of the native plan
+    when the object goes away.  A subclass names the prefix of its C entries (`<prefix>workspace_bytes`, `create`,
+    `run`, `enable_timing`, `destroy`), builds the descriptor of a layer, and calls `_create` once it has its own buffers."""
+    _PREFIX = ""
+    _plan = None
+    _fin = None
+
+    def __init__(self, layers: Sequence[dict], make_desc):
+        if not layers:
+            raise ValueError("empty plan")
+        dev = layers[0]["W"].device
+        self.device = dev
+        n = len(layers)
+        self.n = n
+        self._descs = (LayerDesc * n)()
+        self._keep = []
+        self._ptrs = tuple((C.c_void_p * n)() for _ in "WUZ")
+        for i, L in enumerate(layers):
+            for key in ("W", "U", "Z"):
+                _operand(L[key], "", key, (torch.float32,))
+                if L[key].shape != L["W"].shape:
+                    raise TadmmError(-1, f"{key} shape differs from W")
+            self._descs[i] = make_desc(L)
+            for p, key in zip(self._ptrs, "WUZ"):
+                p[i] = L[key].data_ptr()
+            self._keep.append((L["W"], L["U"], L["Z"]))
+        self.h = _handle(dev)
+        size = C.c_size_t()
+        self.h.check(self._entry("workspace_bytes")(self.h.ptr, n, self._descs, C.byref(size)))
+        self.workspace_bytes = int(size.value)
+        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=dev)
+        self.resid_sq = torch.zeros(n, dtype=torch.float64, device=dev)
+
+    def _entry(self, name: str):
+        return getattr(self.h.lib, self._PREFIX + name)
+
+    def _create(self, *extra):
+        """The native plan over the captured pointers; `extra`: the subclass's own pointer arrays."""
+        plan = C.c_void_p()
+        self.h.check(self._entry("create")(self.h.ptr, self.n, self._descs, *self._ptrs, *extra, self.workspace.data_ptr(),
+                                         self.workspace_bytes, C.byref(plan)))
+        self._plan = plan
+        self._fin = weakref.finalize(self, self._entry("destroy"), plan)
+
+    def run(self, update_u: bool = True, use_u: bool = True) -> torch.Tensor:
+        """One projection; returns the device tensor of per-layer ||W-Z||^2 (float64)."""
+        self.h.check(self._entry("run")(self._plan, int(update_u), int(use_u), self.resid_sq.data_ptr(),
+                                      _stream(self.device)))
+        return self.resid_sq
+
+    def enable_timing(self, on: bool = True):
+        self.h.check(self._entry("enable_timing")(self._plan, int(on)))
+
+    def close(self):
+        """Destroys the native plan now instead of with the object.  Idempotent, and a no-op on an object whose
+        constructor raised before the plan existed."""
+        if self._fin is not None:
+            self._fin()
+        self._plan = None
+
+
+class ProjectionPlan(_LayerPlan):
     """Grouped TT/SVD projection of a set of layers (ADMM.update, admm.py:42-78).
 
     layers: sequence of dicts with keys
@@ -41,34 +141,16 @@ class ProjectionPlan:
         ranks      : list[int] (TT) | int / [int] (SVD)
     """
 
+    _PREFIX = "tadmm_plan_"
+
     def __init__(self, layers: Sequence[dict], want_cores: bool = False, skip_rotations: bool = True):
-        if not layers:
-            raise ValueError("empty plan")
-        dev = layers[0]["W"].device
-        self.device = dev
-        self.h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
-        lib = self.h.lib
-        n = len(layers)
-        self.n = n
         flags = 0 if want_cores or not skip_rotations else FLAG_SKIP_ROTATIONS
-        self._descs = (LayerDesc * n)()
-        self._keep = []
-        Wp = (C.c_void_p * n)()
-        Up = (C.c_void_p * n)()
-        Zp = (C.c_void_p * n)()
+        super().__init__(layers, lambda L: make_layer_desc(L["kind"], list(L["W"].shape), L.get("tt_shapes"), L["ranks"],
+                                                           flags))
+        n, dev = self.n, self.device
         Cp = (C.c_void_p * n)()
         self.cores: List[Optional[torch.Tensor]] = [None] * n
         self._core_shapes = []
-        for i, L in enumerate(layers):
-            for key in ("W", "U", "Z"):
-                _require_cuda(L[key], key)
-                if L[key].shape != L["W"].shape:
-                    raise TadmmError(-1, f"{key} shape differs from W")
-            self._descs[i] = make_layer_desc(L["kind"], list(L["W"].shape), L.get("tt_shapes"), L["ranks"], flags)
-            Wp[i], Up[i], Zp[i] = L["W"].data_ptr(), L["U"].data_ptr(), L["Z"].data_ptr()
-            self._keep.append((L["W"], L["U"], L["Z"]))
-        size = C.c_size_t()
-        self.h.check(lib.tadmm_plan_workspace_bytes(self.h.ptr, n, self._descs, C.byref(size)))
         # clamped ranks are a pure function of the shapes: compute them to size the core buffers
         self.ranks = []
         for i, L in enumerate(layers):
@@ -88,24 +170,10 @@ class ProjectionPlan:
                 Cp[i] = self.cores[i].data_ptr()
             else:
                 Cp[i] = None
-        self.workspace_bytes = int(size.value)
-        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=dev)
-        self.resid_sq = torch.zeros(n, dtype=torch.float64, device=dev)
-        self._plan = C.c_void_p()
-        self.h.check(lib.tadmm_plan_create(self.h.ptr, n, self._descs, Wp, Up, Zp, Cp, self.workspace.data_ptr(),
-                                           self.workspace_bytes, C.byref(self._plan)))
-
-    def run(self, update_u: bool = True, use_u: bool = True) -> torch.Tensor:
-        """One projection; returns the device tensor of per-layer ||W-Z||^2 (float64)."""
-        self.h.check(self.h.lib.tadmm_plan_run(self._plan, int(update_u), int(use_u), self.resid_sq.data_ptr(),
-                                               _stream(self.device)))
-        return self.resid_sq
+        self._create(Cp)
 
     def set_jacobi(self, tol=0.0, inner_sweeps=0, max_sweeps=0):
         self.h.check(self.h.lib.tadmm_plan_set_jacobi(self._plan, float(tol), int(inner_sweeps), int(max_sweeps)))
-
-    def enable_timing(self, on=True):
-        self.h.check(self.h.lib.tadmm_plan_enable_timing(self._plan, int(on)))
 
     def last_timing(self):
         out = (C.c_double * 8)()
@@ -161,17 +229,6 @@ class ProjectionPlan:
             off += a * b * c
         return out
 
-    def close(self):
-        if getattr(self, "_plan", None) is not None and self._plan:
-            self.h.lib.tadmm_plan_destroy(self._plan)
-            self._plan = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ------------------------------------------------------------------ grouped GEMM
 def gemm_desc(A, B, Cout, M, N, K, a_strides, b_strides, c_strides, alpha=1.0, beta=0.0, bias_n=None, bias_m=None):
@@ -187,53 +244,27 @@ def gemm_desc(A, B, Cout, M, N, K, a_strides, b_strides, c_strides, alpha=1.0, b
     return g
 
 
-class TuckerPlan:
+class TuckerPlan(_LayerPlan):
     """Grouped Tucker-2 projection of a set of layers (the 'tk' branches of ADMM.update, admm.py:47-50, :59-62).
 
     layers: sequence of dicts with keys W, U, Z (float32 device tensors, 4-D (O,I,kh,kw) or 2-D (out,in)) and
     ranks = [r_out, r_in].  HOSVD + HOOI for all layers in lock-step on the device (csrc/tucker_plan.hip).
     """
 
+    _PREFIX = "tadmm_tucker_"
+
     def __init__(self, layers: Sequence[dict], n_iter_max: int = 100, tol: float = 1e-4):
-        if not layers:
-            raise ValueError("empty plan")
-        dev = layers[0]["W"].device
-        self.device = dev
-        self.h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
-        lib = self.h.lib
-        n = len(layers)
-        self.n = n
-        self._descs = (LayerDesc * n)()
-        self._keep = []
         self._shapes = []
-        Wp = (C.c_void_p * n)()
-        Up = (C.c_void_p * n)()
-        Zp = (C.c_void_p * n)()
-        for i, L in enumerate(layers):
-            for key in ("W", "U", "Z"):
-                _require_cuda(L[key], key)
-                if L[key].shape != L["W"].shape:
-                    raise TadmmError(-1, f"{key} shape differs from W")
+
+        def desc(L):
             shape = list(L["W"].shape)
             if len(shape) not in (2, 4):
                 raise TadmmError(-1, "Tucker layers are 2-D or 4-D")
-            self._descs[i] = make_layer_desc(KIND_TUCKER2, shape, None, L["ranks"], 0, n_iter_max, tol)
-            Wp[i], Up[i], Zp[i] = L["W"].data_ptr(), L["U"].data_ptr(), L["Z"].data_ptr()
-            self._keep.append((L["W"], L["U"], L["Z"]))
             self._shapes.append((shape, int(L["ranks"][0]), int(L["ranks"][1])))
-        size = C.c_size_t()
-        self.h.check(lib.tadmm_tucker_workspace_bytes(self.h.ptr, n, self._descs, C.byref(size)))
-        self.workspace_bytes = int(size.value)
-        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=dev)
-        self.resid_sq = torch.zeros(n, dtype=torch.float64, device=dev)
-        self._plan = C.c_void_p()
-        self.h.check(lib.tadmm_tucker_create(self.h.ptr, n, self._descs, Wp, Up, Zp, self.workspace.data_ptr(),
-                                             self.workspace_bytes, C.byref(self._plan)))
+            return make_layer_desc(KIND_TUCKER2, shape, None, L["ranks"], 0, n_iter_max, tol)
 
-    def run(self, update_u: bool = True, use_u: bool = True) -> torch.Tensor:
-        self.h.check(self.h.lib.tadmm_tucker_run(self._plan, int(update_u), int(use_u), self.resid_sq.data_ptr(),
-                                                 _stream(self.device)))
-        return self.resid_sq
+        super().__init__(layers, desc)
+        self._create()
 
     def _view(self, ptr: int, numel: int) -> torch.Tensor:
         off = ptr - self.workspace.data_ptr()
@@ -263,25 +294,11 @@ class TuckerPlan:
         """Jacobi sweeps summed over all eigen-solve groups of the last run."""
         return int(self.h.lib.tadmm_tucker_jacobi_sweeps(self._plan))
 
-    def enable_timing(self, on: bool = True):
-        self.h.check(self.h.lib.tadmm_tucker_enable_timing(self._plan, int(on)))
-
     def last_timing(self) -> dict:
         """Instrumented run: eigen-solver launches timed one by one with HIP events on the launch stream."""
         out = (C.c_double * 8)()
         self.h.check(self.h.lib.tadmm_tucker_last_timing(self._plan, out))
         return dict(eig_ms=out[0], eig_launches=int(out[1]), eig_model_flops=out[2], total_ms=out[3], hooi_sweeps=int(out[4]))
-
-    def close(self):
-        if getattr(self, "_plan", None) is not None and self._plan:
-            self.h.lib.tadmm_tucker_destroy(self._plan)
-            self._plan = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class GemmBatch:
@@ -289,7 +306,7 @@ class GemmBatch:
 
     def __init__(self, descs: Sequence[GemmDesc], device):
         self.device = device
-        self.h = Handle.get(device.index if device.index is not None else torch.cuda.current_device())
+        self.h = _handle(device)
         lib = self.h.lib
         n = len(descs)
         arr = (GemmDesc * n)(*descs)
@@ -324,7 +341,7 @@ def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, alp
     d = gemm_desc(a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, a.stride(), b.stride(), out.stride(), alpha, beta,
                   None if bias_n is None else bias_n.data_ptr(), None if bias_m is None else bias_m.data_ptr())
     dev = a.device
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     h.check(h.lib.tadmm_gemm(h.ptr, C.byref(d), _stream(dev)))       # descriptor by value: one launch, no upload
     return out
 
@@ -333,10 +350,7 @@ def mm_nt_bf16(a: torch.Tensor, bt: torch.Tensor, bias_n: Optional[torch.Tensor]
     """a (M,K) @ bt (N,K)^T [+ bias over N] in bf16 with fp32 accumulation; rows contiguous along K."""
     assert a.dim() == 2 and bt.dim() == 2 and a.shape[1] == bt.shape[1]
     for t, what in ((a, "a"), (bt, "bt")):
-        if not t.is_cuda:
-            raise TadmmError(-1, f"{what} must live on a HIP device; there is no CPU path")
-        if t.dtype != torch.bfloat16:
-            raise TadmmError(-1, f"{what} must be bfloat16")
+        _operand(t, "", what, (torch.bfloat16,), layout=None)
         if t.stride(1) != 1:
             raise TadmmError(-1, f"{what} must be contiguous along K")
     M, K = a.shape
@@ -345,7 +359,7 @@ def mm_nt_bf16(a: torch.Tensor, bt: torch.Tensor, bias_n: Optional[torch.Tensor]
     if bias_n is not None:
         bias_n = bias_n.float().contiguous()
     dev = a.device
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     h.check(h.lib.tadmm_gemm_bf16_nt(h.ptr, a.data_ptr(), bt.data_ptr(), out.data_ptr(), M, N, K, a.stride(0),
                                      bt.stride(0), N, None if bias_n is None else bias_n.data_ptr(), _stream(dev)))
     return out
@@ -356,8 +370,7 @@ def _wgrad_operands(a: torch.Tensor, b: torch.Tensor):
     """Validated (a, b, T, M, N, hw) of a weight-gradient product; the only copies are `.contiguous()` of a row tensor
     without unit feature stride or of a non-contiguous image (alignment is the kernel's business)."""
     for t, what in ((a, "a"), (b, "b")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TadmmError(-1, f"wgrad: {what} must live on a HIP device; there is no CPU path")
+        _operand(t, "wgrad", what, layout=None)
     if a.device != b.device:
         raise TadmmError(-1, f"wgrad: operands on different devices ({a.device}, {b.device})")
     if a.dtype != b.dtype:
@@ -410,20 +423,16 @@ def wgrad(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, 
     (`tadmm_wgrad`, csrc/wgrad.hip).  `a`, `b`: two row tensors (T, M) / (T, N) or two NCHW images (B, M, H, W) /
     (B, N, H, W), t = (batch, pixel), both float32 or both bfloat16, read in place; split over T, deterministic."""
     a, b, T, M, N, hw = _wgrad_operands(a, b)
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    elif (not out.is_cuda or out.device != a.device or out.dtype != torch.float32 or tuple(out.shape) != (M, N)
-          or (N > 1 and out.stride(1) != 1)):
-        raise TadmmError(-1, f"wgrad: out must be a float32 ({M}, {N}) device tensor with unit column stride")
+    out = _output(out, (M, N), torch.float32, a.device, "wgrad: out", strided_rows=True)
     if M == 0 or N == 0:
         return out
     d = _wgrad_desc(a, b, T, M, N, hw, alpha)
     d.C, d.ldc = out.data_ptr(), out.stride(0) if M > 1 else max(out.stride(0), N)
     dev = a.device
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     nbytes, slices = C.c_size_t(), C.c_int()
     h.check(h.lib.tadmm_wgrad_workspace_bytes(C.byref(d), C.byref(nbytes), C.byref(slices)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    ws = _scratch(nbytes.value, dev) if nbytes.value else None
     h.check(h.lib.tadmm_wgrad(h.ptr, C.byref(d), None if ws is None else ws.data_ptr(), nbytes.value, _stream(dev)))
     return out
 
@@ -441,8 +450,7 @@ def weight_planes(w: torch.Tensor, planes: int, pad_rows: int = 16, pad_cols: in
         raise TadmmError(-1, f"weight planes are bfloat16 or float16 (got {dtype})")
     if dtype == torch.float16 and planes != 1:
         raise TadmmError(-1, "float16 weights are ONE plane: the three-plane split belongs to float32 activations")
-    if not w.is_cuda:
-        raise TadmmError(-1, "weights must live on a HIP device; there is no CPU path")
+    _operand(w, "", "weights", layout=None)
     N, K = w.shape
     Np, Kp = -(-N // pad_rows) * pad_rows, -(-K // pad_cols) * pad_cols
     flat = torch.zeros(planes, Np, Kp, dtype=dtype, device=w.device)
@@ -484,6 +492,17 @@ class _LruMemo(collections.OrderedDict):
 
 _CHAIN_MEMO = _LruMemo()
 
+
+def _memoised(key, build):
+    """The launch record of `key`: the memo's, else `build()`'s, which is then stored.  A key of None is not memoised."""
+    if key is None:
+        return build()
+    hit = _CHAIN_MEMO.lookup(key)
+    if hit is None:
+        hit = build()
+        _CHAIN_MEMO.store(key, hit)
+    return hit
+
 # activation dtypes whose one 16-bit weight plane runs the single-plane kernels (float16: inference entries only)
 HALF_DTYPES = (torch.bfloat16, torch.float16)
 
@@ -512,14 +531,15 @@ def _out_tensors(out, shapes, like):
     """One contiguous tensor of `like`'s dtype and device per shape: the caller's (`out`: a tensor or a sequence, None
     entries allowed) where given, else a fresh one."""
     given = (out,) if isinstance(out, torch.Tensor) else (tuple(out) if out is not None else ())
-    res = []
-    for shape, t in zip(shapes, given + (None,) * len(shapes)):
-        if t is None:
-            t = torch.empty(shape, dtype=like.dtype, device=like.device)
-        elif tuple(t.shape) != tuple(shape) or t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
-            raise TadmmError(-1, f"conv chain: `out` must be a contiguous {like.dtype} tensor of shape {tuple(shape)}")
-        res.append(t)
-    return res
+    return [_output(t, tuple(shape), like.dtype, like.device, "conv chain: `out`")
+            for shape, t in zip(shapes, given + (None,) * len(shapes))]
+
+
+def _check_planes(planes, nplanes: int, dtype, who: str):
+    """Weight planes as `weight_planes` packs them: `nplanes` contiguous 5-D planes of `dtype`."""
+    if (not isinstance(planes, torch.Tensor) or planes.dtype != dtype or planes.dim() != 5 or planes.shape[0] != nplanes
+            or not planes.is_contiguous()):
+        raise TadmmError(-1, f"{who}: weights must be {nplanes} contiguous {dtype} plane(s) (ops.weight_planes)")
 
 
 def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin: int, n1: int, n_out: int,
@@ -528,8 +548,7 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
     middle-rank vector and the result is (y, h).  Such a launch never enters the memo."""
     if save_rank:
         use_memo = False
-    if not x.is_cuda:
-        raise TadmmError(-1, "x must live on a HIP device; there is no CPU path")
+    _operand(x, "", "x", layout=None)
     if x.dim() == 4:                                   # (B, C, H, W) read in place
         if not x.is_contiguous():
             x = x.contiguous()
@@ -542,11 +561,10 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
     # (the planes' dtype is part of their identity: a bfloat16 view of a binary16 plane shares its address)
     key = (entry, tuple(x.shape), x.stride(0), x.dtype, x.device, win.data_ptr(), win.dtype,
            (0, None) if wout is None else (wout.data_ptr(), wout.dtype), bias_key, kin, n1, n_out, image_out, tile_tokens)
-    memo = _CHAIN_MEMO.lookup(key) if bias_key is not None else None
-    if memo is None:
+
+    def build():
         dtype, planes, pdt = _chain_dtype(x.dtype, "chain")
-        if win.dtype != pdt or win.dim() != 5 or win.shape[0] != planes or not win.is_contiguous():
-            raise TadmmError(-1, f"chain: weights must be {planes} contiguous {pdt} plane(s) (ops.weight_planes)")
+        _check_planes(win, planes, pdt, "chain")
         d = _cabi.ChainDesc()
         if x.dim() == 4:
             B, Cc, H, W = x.shape
@@ -573,18 +591,15 @@ def _chain_call(entry: str, x: torch.Tensor, win: torch.Tensor, wout, bias, kin:
             raise TadmmError(-1, "chain: weight planes do not match the operand shape")
         d.win_plane = win[0].numel()
         if wout is not None:
-            if wout.dtype != pdt or wout.dim() != 5 or wout.shape[0] != planes or not wout.is_contiguous():
-                raise TadmmError(-1, f"chain: weights must be {planes} contiguous {pdt} plane(s) (ops.weight_planes)")
+            _check_planes(wout, planes, pdt, "chain")
             if wout.shape[2] * 32 != n1 or wout.shape[1] * 16 < n_out:
                 raise TadmmError(-1, "chain: output weight planes do not match the middle rank / output size")
             d.wout_plane = wout[0].numel()
         d.dtype, d.tile_tokens = dtype, tile_tokens
-        dev = x.device
-        h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
-        memo = (d, getattr(h.lib, entry), h, yshape, T, (win, wout, bias))     # the tuple keeps the weights alive
-        if bias_key is not None:
-            _CHAIN_MEMO.store(key, memo)
-    d, fn, h, yshape, T, _ = memo
+        h = _handle(x.device)
+        return d, getattr(h.lib, entry), h, yshape, T, (win, wout, bias)     # the tuple keeps the weights alive
+
+    d, fn, h, yshape, T, _ = _memoised(key if bias_key is not None else None, build)
     y = torch.empty(yshape, dtype=x.dtype, device=x.device)
     hbuf, ldh = None, 0
     if save_rank:
@@ -690,47 +705,51 @@ def svd_conv_pays(x: torch.Tensor, rank: int) -> bool:
     return x.dtype in HALF_DTYPES and 0 < rank <= 256
 
 
-def _conv_tile_plan(dtype, rows: int, width: int, r_halo: int, r_tile: int, halo_rows, halo_width: int,
-                    extra_per_pixel: int = 0):
-    """The tile search of the one-launch factorised convolution and of its data gradient: (pixels per workgroup, rows per
-    workgroup, halo tiles, workgroups per image) or None.  A workgroup takes a run of whole rows of the `rows` x `width`
-    plane it writes, at most tm = 64 (else 32) pixels; `halo_rows(tr)` rows of `halo_width` pixels of the plane it reads
-    feed a run of tr rows, in at most three tiles of tm pixels.  The intermediate of rank `r_halo` is held for the halo, that
-    of rank `r_tile` for the tile; `extra_per_pixel`: further LDS bytes per tile pixel."""
-    r_halo, r_tile = -(-r_halo // 32) * 32, -(-r_tile // 32) * 32
-    if r_halo > 256 or r_tile > 256:
+_INT32_MAX = 2 ** 31 - 1
+
+
+@functools.lru_cache(maxsize=256)
+def _conv_plan(x_shape, dtype, r1: int, r2: int, kernel_size, stride, padding, dilation, mode: int):
+    """(pixels per workgroup, rows per workgroup, halo tiles, workgroups per image) of the one-launch factorised
+    convolution (`mode` FWD) or of its data gradient (BWD) on an input of shape x_shape, or None where the launch does
+    not apply: `tadmm_ttconv_fused_plan`, the library's own statement of the tile search (host only; plan_tt_conv in
+    csrc/convchain.hip; tests/test_conv_chain_plan_cpu.py holds an independent statement against it).  The plan reads
+    neither the channel count nor the output features, only that they are positive.  A pure function of hashable
+    arguments, cached: the layers ask on every routed forward, and the ctypes call costs three times the Python loop
+    it replaced (12 us against 4 us)."""
+    dtypes = {torch.float32: _cabi.CHAIN_F32, torch.bfloat16: _cabi.CHAIN_BF16}
+    if mode == _cabi.CONV_CHAIN_FWD:
+        dtypes[torch.float16] = _cabi.CHAIN_F16
+    if len(x_shape) != 4 or dtype not in dtypes:
         return None
-    planes, kc = (3, 64) if dtype == torch.float32 else (1, 128)
-    for tm in (64, 32):                                  # pixels per workgroup: 64, or 32 when 64 does not fit the LDS
-        if width > tm:
-            continue
-        tr, nt = min(rows, tm // width), 0
-        while tr >= 1:
-            nt = -(-(halo_rows(tr) * halo_width) // tm)
-            if nt <= 3:
-                break
-            tr -= 1
-        if tr < 1:
-            continue
-        lds = (2 * planes * tm * (kc + 8) + planes * tm * nt * (r_halo + 8) + planes * tm * (r_tile + 8)) * 2 \
-            + extra_per_pixel * tm
-        if lds <= 160 * 1024:
-            return tm, tr, nt, -(-rows // tr)
-    return None
+    B, Cc, H, W = (int(v) for v in x_shape)
+    geom = tuple(int(v) for pair in (kernel_size, stride, padding, dilation) for v in pair)
+    ranks = (-(-int(r1) // 32) * 32, -(-int(r2) // 32) * 32)
+    # a value ctypes would wrap into an int32 field never reaches the library
+    if max(B, Cc, H, W, *ranks, *(abs(v) for v in geom)) > _INT32_MAX or H <= 0 or W <= 0:
+        return None
+    ho, wo = _conv_out_hw(H, W, geom[0:2], geom[2:4], geom[4:6], geom[6:8])
+    if ho <= 0 or wo <= 0 or max(ho, wo) > _INT32_MAX:
+        return None
+    d = _cabi.ConvChainDesc()
+    d.dtype, d.B, d.C, d.Nout, d.H, d.W, d.Ho, d.Wo = dtypes[dtype], B, Cc, 1, H, W, ho, wo
+    d.R1, d.R2 = ranks
+    d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = geom
+    out = [C.c_int() for _ in range(4)]
+    rc = _cabi.load().tadmm_ttconv_fused_plan(C.byref(d), mode, *[C.byref(v) for v in out], None)
+    if rc == -5:
+        return None
+    if rc < 0:
+        raise TadmmError(rc, "tadmm_ttconv_fused_plan: invalid descriptor")
+    return tuple(v.value for v in out)
 
 
 def _conv_chain_plan(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation):
     """(pixels per workgroup, output rows per workgroup, halo tiles, workgroups per image) of the one-launch factorised
     convolution, or None when it does not apply -- the rule tadmm_ttconv_fused applies.  The tile is a run of output
     rows, its halo the input rows the taps reach."""
-    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return None
-    H, W = x.shape[2], x.shape[3]
-    ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
-    if ho <= 0 or wo <= 0:
-        return None
-    return _conv_tile_plan(x.dtype, ho, wo, r1, r2,
-                           lambda tr: min(H, (tr - 1) * stride[0] + (kernel_size[0] - 1) * dilation[0] + 1), W)
+    return _conv_plan(tuple(x.shape), x.dtype, r1, r2, tuple(kernel_size), tuple(stride), tuple(padding), tuple(dilation),
+                      _cabi.CONV_CHAIN_FWD)
 
 
 def conv_chain_fits(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation) -> bool:
@@ -761,17 +780,10 @@ def conv_core_planes(core: torch.Tensor, planes: int, dtype: torch.dtype = torch
 def _conv_chain_bwd_plan(x_shape, dtype, r1: int, r2: int, kernel_size, stride, padding, dilation):
     """(pixels per workgroup, dX rows per workgroup, halo tiles, workgroups per image) of the one-launch data gradient of
     the factorised convolution of an input of shape x_shape, or None when it does not apply -- the rule
-    `tadmm_ttconv_fused_bwd` applies (`tadmm_ttconv_fused_plan` states it; tests/test_conv_chain_plan_cpu.py holds the
-    two together).  The tile is a run of dX rows, its halo the dY rows the taps reach, and the tap table joins the LDS."""
-    if len(x_shape) != 4 or dtype not in (torch.float32, torch.bfloat16):
-        return None
-    H, W = x_shape[2], x_shape[3]
-    ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
-    if ho <= 0 or wo <= 0 or H <= 0 or W <= 0:
-        return None
-    return _conv_tile_plan(dtype, H, W, r2, r1,
-                           lambda tr: min(ho, (tr - 1 + (kernel_size[0] - 1) * dilation[0]) // stride[0] + 1), wo,
-                           extra_per_pixel=kernel_size[0] * kernel_size[1] * 2)
+    `tadmm_ttconv_fused_bwd` applies.  The tile is a run of dX rows, its halo the dY rows the taps reach, and the tap
+    table joins the LDS.  float32 and bfloat16 only."""
+    return _conv_plan(tuple(x_shape), dtype, r1, r2, tuple(kernel_size), tuple(stride), tuple(padding), tuple(dilation),
+                      _cabi.CONV_CHAIN_BWD)
 
 
 def conv_chain_bwd_fits(x: torch.Tensor, r1: int, r2: int, kernel_size, stride, padding, dilation) -> bool:
@@ -811,8 +823,7 @@ def _conv_chain_desc(B, Cc, H, W, n_out, w1p, w2p, w3p, bias, dtype, kernel_size
     d = _cabi.ConvChainDesc()
     d.dtype, nplanes, pdt = _chain_dtype(dtype, "conv chain")
     for wp in (w1p, w2p, w3p):
-        if wp.dtype != pdt or wp.dim() != 5 or wp.shape[0] != nplanes or not wp.is_contiguous():
-            raise TadmmError(-1, f"conv chain: weights must be {nplanes} contiguous {pdt} plane(s) for {dtype} images")
+        _check_planes(wp, nplanes, pdt, "conv chain")
     ho, wo = _conv_out_hw(H, W, kernel_size, stride, padding, dilation)
     d.W1, d.W2, d.W3 = w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr()
     d.bias = None if bias is None else bias.data_ptr()
@@ -837,29 +848,24 @@ def conv_chain(x: torch.Tensor, w1p: torch.Tensor, w2p: torch.Tensor, w3p: torch
     w1p = weight_planes(W1, P, pad_rows=32), w2p = conv_core_planes(core, P), w3p = weight_planes(W3, P).
     `save_ranks` = (r1, r2): see `conv_chain_save`.  `memo` False: planes packed for this call only stay out of the launch
     memo.  `out`: contiguous tensors to write instead of fresh ones -- y, or (y, H1, H2) with `save_ranks`."""
-    if not x.is_cuda:
-        raise TadmmError(-1, "x must live on a HIP device; there is no CPU path")
-    if not x.is_contiguous():
-        x = x.contiguous()
+    x = _operand(x, "", "x", layout="copy")
     bias, bias_key = _f32_bias(bias)
     if save_ranks is not None or not memo:
         bias_key = None                                 # training: the planes are short-lived -- build, launch, forget
     key = ("conv", tuple(x.shape), x.dtype, x.device, w1p.data_ptr(), w2p.data_ptr(), w3p.data_ptr(),
            (w1p.dtype, w2p.dtype, w3p.dtype), bias_key, n_out, tuple(kernel_size), tuple(stride), tuple(padding), tuple(dilation))
-    memo = _CHAIN_MEMO.lookup(key) if bias_key is not None else None
-    if memo is None:
+
+    def build():
         if x.dim() != 4:
             raise TadmmError(-1, "conv chain: x must be an NCHW image")
         if x.dtype == torch.float16 and save_ranks is not None:
             raise TadmmError(-1, "conv chain: float16 is inference only; the saved intermediates feed the weight gradients")
         B, Cc, H, W = x.shape
         d, ho, wo = _conv_chain_desc(B, Cc, H, W, n_out, w1p, w2p, w3p, bias, x.dtype, kernel_size, stride, padding, dilation)
-        dev = x.device
-        h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
-        memo = (d, h.lib.tadmm_ttconv_fused, h, (B, n_out, ho, wo), (w1p, w2p, w3p, bias))
-        if bias_key is not None:
-            _CHAIN_MEMO.store(key, memo)
-    d, fn, h, yshape, _ = memo
+        h = _handle(x.device)
+        return d, h.lib.tadmm_ttconv_fused, h, (B, n_out, ho, wo), (w1p, w2p, w3p, bias)
+
+    d, fn, h, yshape, _ = _memoised(key if bias_key is not None else None, build)
 
     shapes = [yshape]
     if save_ranks is not None:
@@ -891,19 +897,16 @@ def conv_chain_bwd(dy: torch.Tensor, w3tp: torch.Tensor, w2tp: torch.Tensor, w1t
     conv_core_planes(core.permute(1, 0, 2, 3), P), w1tp = weight_planes(W1.t(), P); nothing is flipped.  `save`: returns
     (dX, dH1 (B, r1, H, W), dH2 (B, r2, Ho, Wo)), the gradients of the two intermediates.  `out`: contiguous tensors to
     write instead of fresh ones -- dX, or (dX, dH1, dH2) with `save`."""
-    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
-        raise TadmmError(-1, "dy must live on a HIP device; there is no CPU path")
-    if dy.dim() != 4 or dy.dtype not in (torch.float32, torch.bfloat16):
-        raise TadmmError(-1, f"conv chain: a float32 or bfloat16 NCHW image is needed (got {dy.dim()}-D {dy.dtype})")
-    if not dy.is_contiguous():
-        dy = dy.contiguous()
+    dy = _operand(dy, "conv chain", "dy", (torch.float32, torch.bfloat16), layout="copy")
+    if dy.dim() != 4:
+        raise TadmmError(-1, f"conv chain: dy must be an NCHW image (got {dy.dim()}-D)")
     B, Cc, H, W = x_shape
     d, ho, wo = _conv_chain_desc(B, Cc, H, W, dy.shape[1], w3tp, w2tp, w1tp, None, dy.dtype, kernel_size, stride, padding,
                                  dilation, bwd=True)
     if tuple(dy.shape) != (B, dy.shape[1], ho, wo) or w1tp.shape[1] * 16 < Cc:
         raise TadmmError(-1, f"conv chain: dy of shape {tuple(dy.shape)} is not the output of x {tuple(x_shape)}")
     dev = dy.device
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     shapes = [tuple(x_shape)] + ([(B, r1, H, W), (B, r2, ho, wo)] if save else [])
     dx, dh1, dh2 = _out_tensors(out, shapes, dy) + [None] * (3 - len(shapes))
     d.X, d.Y = dy.data_ptr(), dx.data_ptr()
@@ -964,34 +967,26 @@ def _core_conv_desc(x_shape, r2: int, dtype, kernel_size, stride, padding, dilat
 def _core_conv_call(entry: str, src: torch.Tensor, planes: torch.Tensor, x_shape, r2: int, kernel_size, stride, padding,
                     dilation, memo: bool):
     """Forward (src = x, result y) or data gradient (src = dy, result dx) of the core convolution on x_shape inputs."""
-    if not isinstance(src, torch.Tensor) or not src.is_cuda:
-        raise TadmmError(-1, "core conv: tensors must live on a HIP device; there is no CPU path")
-    if src.dim() != 4 or src.dtype not in (torch.float32, torch.bfloat16):
-        raise TadmmError(-1, f"core conv: a float32 or bfloat16 NCHW image is needed (got {src.dim()}-D {src.dtype})")
-    if not src.is_contiguous():
-        src = src.contiguous()
+    src = _operand(src, "core conv", "the image", (torch.float32, torch.bfloat16), layout="copy")
+    if src.dim() != 4:
+        raise TadmmError(-1, f"core conv: an NCHW image is needed (got {src.dim()}-D)")
     fwd = entry == "tadmm_core_conv_fwd"
     key = (entry, tuple(x_shape), r2, src.dtype, src.device, planes.data_ptr(), _pair(kernel_size), _pair(stride),
            _pair(padding), _pair(dilation))
-    hit = _CHAIN_MEMO.lookup(key) if memo else None
-    if hit is None:
-        nplanes = 3 if src.dtype == torch.float32 else 1
+
+    def build():
         d = _core_conv_desc(x_shape, r2, src.dtype, kernel_size, stride, padding, dilation)
         rows, cols = (r2, x_shape[1]) if fwd else (x_shape[1], r2)
-        if (planes.dtype != torch.bfloat16 or planes.dim() != 5 or planes.shape[0] != nplanes or not planes.is_contiguous()
-                or planes.shape[1] * 16 < rows or planes.shape[2] != d.kh * d.kw * -(-cols // 32)):
-            raise TadmmError(-1, f"core conv: weights must be {nplanes} contiguous bf16 plane(s) of the tap-major core "
-                                 "(ops.conv_core_planes)")
+        _check_planes(planes, 3 if src.dtype == torch.float32 else 1, torch.bfloat16, "core conv")
+        if planes.shape[1] * 16 < rows or planes.shape[2] != d.kh * d.kw * -(-cols // 32):
+            raise TadmmError(-1, "core conv: weight planes do not match the tap-major core (ops.conv_core_planes)")
         if d.Ho <= 0 or d.Wo <= 0:
             raise TadmmError(-1, "core conv: empty output plane")
         d.Wc, d.wc_plane = planes.data_ptr(), planes[0].numel()
-        dev = src.device
-        h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
-        y_shape = (x_shape[0], r2, d.Ho, d.Wo)
-        hit = (d, getattr(h.lib, entry), h, y_shape, planes)                    # the tuple keeps the planes alive
-        if memo:
-            _CHAIN_MEMO.store(key, hit)
-    d, fn, h, y_shape, _ = hit
+        h = _handle(src.device)
+        return d, getattr(h.lib, entry), h, (x_shape[0], r2, d.Ho, d.Wo), planes     # the tuple keeps the planes alive
+
+    d, fn, h, y_shape, _ = _memoised(key if memo else None, build)
     if tuple(src.shape) != (tuple(x_shape) if fwd else y_shape):
         raise TadmmError(-1, f"core conv: operand of shape {tuple(src.shape)} does not match the geometry")
     out = torch.empty(y_shape if fwd else tuple(x_shape), dtype=src.dtype, device=src.device)
@@ -1024,8 +1019,7 @@ def core_conv_dgrad(dy: torch.Tensor, planes_t: torch.Tensor, x_shape, kernel_si
 
 def _core_wgrad_operands(dy, x, kernel_size, stride, padding, dilation):
     for t, what in ((dy, "dy"), (x, "x")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TadmmError(-1, f"core conv wgrad: {what} must live on a HIP device; there is no CPU path")
+        _operand(t, "core conv wgrad", what, layout=None)
     if dy.dtype != x.dtype or x.dtype not in (torch.float32, torch.bfloat16) or dy.dim() != 4 or x.dim() != 4:
         raise TadmmError(-1, f"core conv wgrad: two NCHW images of one dtype, float32 or bfloat16 (got {dy.dtype}, {x.dtype})")
     if dy.device != x.device:
@@ -1059,12 +1053,12 @@ def core_conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kernel_size, stride=1, pa
     if out.numel() == 0:
         return out
     dev = x.device
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     nbytes = C.c_size_t()
     h.check(h.lib.tadmm_core_conv_wgrad_workspace_bytes(C.byref(d), C.byref(nbytes), None))
     ws = workspace
     if ws is None and nbytes.value:
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = _scratch(nbytes.value, dev)
     h.check(h.lib.tadmm_core_conv_wgrad(h.ptr, C.byref(d), out.data_ptr(), None if ws is None else ws.data_ptr(),
                                         0 if ws is None else ws.numel() * ws.element_size(), _stream(dev)))
     return out
@@ -1073,53 +1067,47 @@ def core_conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kernel_size, stride=1, pa
 # ------------------------------------------------------------------ Gram / eigh (tests, Tucker)
 def gram(a: torch.Tensor):
     """fp64 Gram of a float32 (m,n) matrix: A A^T if m<=n else A^T A.  Returns (N,N) float64."""
-    _require_cuda(a, "A")
-    h = Handle.get(a.device.index)
+    _operand(a, "", "A", (torch.float32,))
+    h = _handle(a.device)
     lib = h.lib
     m, n = a.shape
     npad, ld = C.c_int(), C.c_int()
     N = lib.tadmm_gram_ld(m, n, C.byref(npad), C.byref(ld))
     G = torch.empty(npad.value, ld.value, dtype=torch.float64, device=a.device)
-    sb = lib.tadmm_gram_scratch_bytes(m, n)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=a.device)
-    h.check(lib.tadmm_gram_f64(h.ptr, a.data_ptr(), m, n, G.data_ptr(), ld.value, scratch.data_ptr(), sb,
+    scratch = _scratch(lib.tadmm_gram_scratch_bytes(m, n), a.device)
+    h.check(lib.tadmm_gram_f64(h.ptr, a.data_ptr(), m, n, G.data_ptr(), ld.value, scratch.data_ptr(), scratch.numel(),
                                _stream(a.device)))
     return G[:N, :N]
 
 
-def eigh(G: torch.Tensor):
-    """Symmetric PSD eigen-decomposition (descending).  Returns (evals (N,), evecs (N,N) rows, sweeps)."""
+def _eigh(G: torch.Tensor, r: Optional[int]):
+    """The full solve (r None: N pairs, third result the sweeps) or the leading r pairs (third result the route)."""
     assert G.dtype == torch.float64 and G.is_cuda and G.dim() == 2 and G.shape[0] == G.shape[1]
     G = G.contiguous()
-    h = Handle.get(G.device.index)
-    lib = h.lib
+    h = _handle(G.device)
     N = G.shape[0]
-    ev = torch.empty(N, dtype=torch.float64, device=G.device)
-    vec = torch.empty(N, N, dtype=torch.float64, device=G.device)
-    sb = lib.tadmm_eigh_scratch_bytes(N)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=G.device)
-    sweeps = C.c_int()
-    h.check(lib.tadmm_eigh_f64(h.ptr, G.data_ptr(), N, ev.data_ptr(), vec.data_ptr(), scratch.data_ptr(), sb,
-                               C.byref(sweeps), _stream(G.device)))
-    return ev, vec, int(sweeps.value)
+    rows = N if r is None else max(r, 1)
+    ev = torch.empty(rows, dtype=torch.float64, device=G.device)
+    vec = torch.empty(rows, N, dtype=torch.float64, device=G.device)
+    scratch = _scratch(h.lib.tadmm_eigh_scratch_bytes(N), G.device)
+    info = C.c_int(0 if r is None else -1)
+    tail = (ev.data_ptr(), vec.data_ptr(), scratch.data_ptr(), scratch.numel(), C.byref(info), _stream(G.device))
+    if r is None:
+        h.check(h.lib.tadmm_eigh_f64(h.ptr, G.data_ptr(), N, *tail))
+    else:
+        h.check(h.lib.tadmm_eigh_partial_f64(h.ptr, G.data_ptr(), N, int(r), *tail))
+    return ev, vec, int(info.value)
+
+
+def eigh(G: torch.Tensor):
+    """Symmetric PSD eigen-decomposition (descending).  Returns (evals (N,), evecs (N,N) rows, sweeps)."""
+    return _eigh(G, None)
 
 
 def eigh_partial(G: torch.Tensor, r: int):
     """Leading r pairs of a symmetric PSD G (descending), as the plans solve them.  Returns (evals (r,),
     evecs (r,N) rows, route): route 0 = direct solver, 1 = single-launch Jacobi, 2 = Jacobi tournament."""
-    assert G.dtype == torch.float64 and G.is_cuda and G.dim() == 2 and G.shape[0] == G.shape[1]
-    G = G.contiguous()
-    h = Handle.get(G.device.index)
-    lib = h.lib
-    N = G.shape[0]
-    ev = torch.empty(max(r, 1), dtype=torch.float64, device=G.device)
-    vec = torch.empty(max(r, 1), N, dtype=torch.float64, device=G.device)
-    sb = lib.tadmm_eigh_scratch_bytes(N)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=G.device)
-    route = C.c_int(-1)
-    h.check(lib.tadmm_eigh_partial_f64(h.ptr, G.data_ptr(), N, int(r), ev.data_ptr(), vec.data_ptr(),
-                                       scratch.data_ptr(), sb, C.byref(route), _stream(G.device)))
-    return ev, vec, int(route.value)
+    return _eigh(G, r)
 
 
 # ------------------------------------------------------------------ filtered eigen-solver building blocks (tests)
@@ -1130,11 +1118,10 @@ def dgemm(a: torch.Tensor, b: torch.Tensor, b_transposed: bool = True) -> torch.
     M, K = a.shape
     N = b.shape[0] if b_transposed else b.shape[1]
     out = torch.empty(M, N, dtype=torch.float64, device=a.device)
-    h = Handle.get(a.device.index)
-    sb = h.lib.tadmm_dgemm_scratch_bytes(M, N)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=a.device)
+    h = _handle(a.device)
+    scratch = _scratch(h.lib.tadmm_dgemm_scratch_bytes(M, N), a.device)
     h.check(h.lib.tadmm_dgemm_f64(h.ptr, a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, a.stride(0), b.stride(0),
-                                  N, int(b_transposed), scratch.data_ptr(), sb, _stream(a.device)))
+                                  N, int(b_transposed), scratch.data_ptr(), scratch.numel(), _stream(a.device)))
     return out
 
 
@@ -1144,12 +1131,11 @@ def dgemm3(a: torch.Tensor, g: torch.Tensor, repeats: int = 1) -> torch.Tensor:
     assert a.dtype == torch.float64 and g.dtype == torch.float64 and a.is_cuda and g.is_cuda
     assert a.is_contiguous() and g.is_contiguous() and g.shape[0] == g.shape[1] == a.shape[1]
     M, N = a.shape
-    h = Handle.get(a.device.index)
+    h = _handle(a.device)
     out = torch.empty(M, N, dtype=torch.float64, device=a.device)
-    sb = h.lib.tadmm_dgemm3_scratch_bytes(M, N)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=a.device)
+    scratch = _scratch(h.lib.tadmm_dgemm3_scratch_bytes(M, N), a.device)
     h.check(h.lib.tadmm_dgemm3_f64(h.ptr, a.data_ptr(), g.data_ptr(), out.data_ptr(), M, N, N, N, N, repeats,
-                                   scratch.data_ptr(), sb, _stream(a.device)))
+                                   scratch.data_ptr(), scratch.numel(), _stream(a.device)))
     return out
 
 
@@ -1158,12 +1144,11 @@ def cholqr_(yt: torch.Tensor) -> bool:
     pivot broke down (numerically rank-deficient block)."""
     assert yt.dtype == torch.float64 and yt.is_cuda and yt.is_contiguous()
     n, ncols = yt.shape
-    h = Handle.get(yt.device.index)
-    sb = h.lib.tadmm_cholqr_scratch_bytes(n, ncols)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=yt.device)
+    h = _handle(yt.device)
+    scratch = _scratch(h.lib.tadmm_cholqr_scratch_bytes(n, ncols), yt.device)
     bad = C.c_int(0)
-    h.check(h.lib.tadmm_cholqr_f64(h.ptr, yt.data_ptr(), n, ncols, yt.stride(0), scratch.data_ptr(), sb, C.byref(bad),
-                                   _stream(yt.device)))
+    h.check(h.lib.tadmm_cholqr_f64(h.ptr, yt.data_ptr(), n, ncols, yt.stride(0), scratch.data_ptr(), scratch.numel(),
+                                   C.byref(bad), _stream(yt.device)))
     return bad.value == 0
 
 
@@ -1269,13 +1254,13 @@ class StiefelPlan:
         self.status = torch.zeros(len(descs), dtype=torch.int32, device=dev)
         self._plan = None
         if self.native:
-            self.h = Handle.get(dev.index)
+            self.h = _handle(dev)
             lib = self.h.lib
             n = len(self.native)
             arr = (StiefelDesc * n)(*[descs[i] for i in self.native])
             size = C.c_size_t()
             self.h.check(lib.tadmm_stiefel_workspace_bytes(n, arr, C.byref(size)))
-            self.workspace = torch.empty(int(size.value), dtype=torch.uint8, device=dev)
+            self.workspace = _scratch(size.value, dev)
             plan = C.c_void_p()
             self.h.check(lib.tadmm_stiefel_plan_create(self.h.ptr, n, arr, self.workspace.data_ptr(), int(size.value),
                                                        _stream(dev), C.byref(plan)))
@@ -1528,10 +1513,9 @@ def _ttm_operands(cores, index, who):
         raise TypeError(f"{who}: index must be an int32 or int64 tensor (got {getattr(index, 'dtype', type(index))})")
     dev = cores[0].device
     for k, c in enumerate(cores):
-        if not c.is_cuda or c.device != dev:
-            raise TadmmError(-1, f"{who}: core {k} must live on one HIP device; there is no CPU path")
-        if c.dtype != torch.float32 or not c.is_contiguous():
-            raise TadmmError(-1, f"{who}: core {k} must be contiguous float32")
+        _operand(c, who, f"core {k}", (torch.float32,))
+        if c.device != dev:
+            raise TadmmError(-1, f"{who}: core {k} on {c.device}, core 0 on {dev}")
     if index.device != dev:
         raise TadmmError(-1, f"{who}: index on {index.device}, cores on {dev}")
     flat = index.reshape(-1)
@@ -1552,16 +1536,12 @@ def ttm_gather(cores: Sequence[torch.Tensor], index: torch.Tensor, counter: Opti
     `counter` (one int32 on the device; a fresh zero when None).  Raises for shapes `ttm_gather_fits` refuses."""
     desc, flat, row, dev = _ttm_operands(cores, index, "ttm_gather")
     B = flat.numel()
-    if out is None:
-        out = torch.empty(B, row, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (B, row) or not out.is_contiguous():
-        raise TadmmError(-1, f"ttm_gather: out must be a contiguous float32 ({B}, {row}) tensor on {dev}")
-    if counter is None:
-        counter = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif counter.dtype != torch.int32 or counter.device != dev or counter.numel() != 1:
-        raise TadmmError(-1, "ttm_gather: counter must be one int32 on the cores' device")
+    out = _output(out, (B, row), torch.float32, dev, "ttm_gather: out")
+    # one int32 of any shape: the launch sees its address
+    counter = _output(None if counter is None else counter.reshape(-1), (1,), torch.int32, dev, "ttm_gather: counter",
+                      fresh=torch.zeros)
     desc.Y, desc.bad_count = out.data_ptr(), counter.data_ptr()
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     h.check(h.lib.tadmm_ttm_gather_fwd(h.ptr, C.byref(desc), _stream(dev)))
     return out
 
@@ -1589,7 +1569,7 @@ def ttm_gather_bwd(cores: Sequence[torch.Tensor], index: torch.Tensor, dy: torch
         desc.order[k], desc.offsets[k] = groups[k][0].data_ptr(), groups[k][1].data_ptr()
     desc.dY = dy.data_ptr()
     if any(needs):
-        h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+        h = _handle(dev)
         h.check(h.lib.tadmm_ttm_gather_bwd(h.ptr, C.byref(desc), _stream(dev)))
     return grads
 
@@ -1643,8 +1623,7 @@ def lstm_planes(w_hh: torch.Tensor, transpose: bool = False) -> torch.Tensor:
     TRANSPOSED padded weight (H, 4Hp) -> (3, Hp/16, 4Hp/32, 64, 8), what the backward multiplies dz by."""
     if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1] or w_hh.shape[1] < 1:
         raise ValueError(f"lstm_planes: w_hh must be (4H, H) (got {tuple(w_hh.shape)})")
-    if not w_hh.is_cuda:
-        raise TadmmError(-1, "lstm_planes: the weight must live on a HIP device; there is no CPU path")
+    _operand(w_hh, "lstm_planes", "the weight", layout=None)
     H = w_hh.shape[1]
     Hp = -(-H // 16) * 16
     wp = torch.zeros(4, Hp, H, dtype=torch.float32, device=w_hh.device)
@@ -1654,43 +1633,33 @@ def lstm_planes(w_hh: torch.Tensor, transpose: bool = False) -> torch.Tensor:
 
 
 def _lstm_tensor(t, shape, who, what, optional=False):
+    """A float32 device operand of the recurrence, contiguous (copied if need be); `shape` None: any shape."""
     if t is None:
         if optional:
             return None
         raise TadmmError(-1, f"{who}: {what} is required")
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TadmmError(-1, f"{who}: {what} must live on a HIP device; there is no CPU path")
-    if t.dtype != torch.float32:
-        raise TadmmError(-1, f"{who}: {what} must be float32 (got {t.dtype})")
-    if tuple(t.shape) != tuple(shape):
-        raise TadmmError(-1, f"{who}: {what} must be {tuple(shape)} (got {tuple(t.shape)})")
-    return t if t.is_contiguous() else t.contiguous()
+    return _operand(t, who, what, (torch.float32,), shape, layout="copy")
 
 
 def _lstm_out(out, shape, like, who, what):
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=like.device)
-    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != like.device
-            or tuple(out.shape) != tuple(shape) or not out.is_contiguous()):
-        raise TadmmError(-1, f"{who}: {what} must be a contiguous float32 {tuple(shape)} tensor on {like.device}")
-    return out
+    return _output(out, tuple(shape), torch.float32, like.device, f"{who}: {what}")
 
 
 def _lstm_check_planes(planes, H, transpose, dev, who):
     Hp, Kp = -(-H // 16) * 16, -(-H // 32) * 32
     want = (3, Hp // 16, 4 * Hp // 32, 64, 8) if transpose else (3, 4 * Hp // 16, Kp // 32, 64, 8)
-    if (not isinstance(planes, torch.Tensor) or planes.dtype != torch.bfloat16 or tuple(planes.shape) != want
-            or planes.device != dev or not planes.is_contiguous()):
+    _check_planes(planes, 3, torch.bfloat16, who)
+    if tuple(planes.shape) != want or planes.device != dev:
         raise TadmmError(-1, f"{who}: the weight planes must be `lstm_planes(w_hh, transpose={transpose})`: bfloat16 "
                              f"{want} on {dev}")
 
 
 def _lstm_fwd(entry, xp, planes, h0, c0, sigmoid, save, out):
     who = "lstm_seq_save" if save else "lstm_seq"
-    if not isinstance(xp, torch.Tensor) or xp.dim() != 3 or xp.shape[2] % 4 or xp.shape[2] == 0:
+    xp = _lstm_tensor(xp, None, who, "xp")
+    if xp.dim() != 3 or xp.shape[2] % 4 or xp.shape[2] == 0:
         raise TadmmError(-1, f"{who}: xp must be (T, B, 4H)")
     T, B, H = xp.shape[0], xp.shape[1], xp.shape[2] // 4
-    xp = _lstm_tensor(xp, (T, B, 4 * H), who, "xp")
     dev = xp.device
     if not lstm_fits(H):
         raise TadmmError(-5, f"{who}: H = {H}, the launch takes 1 <= H <= {LSTM_MAX_H}")
@@ -1714,7 +1683,7 @@ def _lstm_fwd(entry, xp, planes, h0, c0, sigmoid, save, out):
         res = (y, hT, cT, g, c)
     if T == 0 or B == 0:
         raise TadmmError(-1, f"{who}: T >= 1 and B >= 1 are required")
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     h.check(getattr(h.lib, entry)(h.ptr, C.byref(d), _stream(dev)))
     return res
 
@@ -1744,10 +1713,10 @@ def lstm_seq_bwd(planes_t: torch.Tensor, g: torch.Tensor, c: torch.Tensor, c0: O
     `wgrad(dZ.view(T*B, 4H), Hprev.view(T*B, H))` with Hprev = [h0, y[0 .. T-2]], the bias gradient `dZ.sum((0, 1))`.
     `dz`: optional tensor to write dZ into."""
     who = "lstm_seq_bwd"
-    if not isinstance(c, torch.Tensor) or c.dim() != 3:
+    c = _lstm_tensor(c, None, who, "C")
+    if c.dim() != 3:
         raise TadmmError(-1, f"{who}: C must be (T, B, H)")
     T, B, H = c.shape
-    c = _lstm_tensor(c, (T, B, H), who, "C")
     dev = c.device
     if T == 0 or B == 0 or H == 0:
         raise TadmmError(-1, f"{who}: T >= 1, B >= 1 and H >= 1 are required")
@@ -1768,7 +1737,7 @@ def lstm_seq_bwd(planes_t: torch.Tensor, g: torch.Tensor, c: torch.Tensor, c0: O
     for name, t in (("c0", c0), ("dY", dy), ("dhT", dhT), ("dcT", dcT)):
         setattr(d, name, None if t is None else t.data_ptr())
     d.T, d.B, d.H, d.sigmoid = T, B, H, int(bool(sigmoid))
-    h = Handle.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     h.check(h.lib.tadmm_lstm_seq_bwd(h.ptr, C.byref(d), _stream(dev)))
     return dz, dh0, dc0
 

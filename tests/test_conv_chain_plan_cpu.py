@@ -1,13 +1,60 @@
-"""`tadmm_ttconv_fused_plan` (host only, no device) against the Python statements of the same rule: `ops._conv_chain_plan`
-for the forward and `ops._conv_chain_bwd_plan` / `ops.conv_chain_bwd_fits` for the data gradient, over a grid of planes,
-kernels, strides, ranks and both dtypes; and the three new symbols in the library."""
+"""`tadmm_ttconv_fused_plan` (host only, no device) -- called raw, and through `ops._conv_chain_plan` for the forward and
+`ops._conv_chain_bwd_plan` / `ops.conv_chain_bwd_fits` for the data gradient -- against the independent Python statement
+of the same tile rule kept in this file, over a grid of planes, kernels, strides, ranks and both dtypes; and the three
+symbols in the library."""
 import ctypes as C
 import itertools
 
+import pytest
 import torch
 
 PLANES = [(7, 7), (8, 8), (14, 14), (28, 28), (56, 56), (6, 10), (2, 64), (2, 65), (64, 7), (65, 65), (9, 33)]
 RANKS = [16, 20, 64, 100, 220, 256, 264]
+
+
+def _conv_tile_plan(dtype, rows: int, width: int, r_halo: int, r_tile: int, halo_rows, halo_width: int,
+                    extra_per_pixel: int = 0):
+    """The tile search of the one-launch factorised convolution and of its data gradient: (pixels per workgroup, rows per
+    workgroup, halo tiles, workgroups per image) or None.  A workgroup takes a run of whole rows of the `rows` x `width`
+    plane it writes, at most tm = 64 (else 32) pixels; `halo_rows(tr)` rows of `halo_width` pixels of the plane it reads
+    feed a run of tr rows, in at most three tiles of tm pixels.  The intermediate of rank `r_halo` is held for the halo, that
+    of rank `r_tile` for the tile; `extra_per_pixel`: further LDS bytes per tile pixel."""
+    r_halo, r_tile = -(-r_halo // 32) * 32, -(-r_tile // 32) * 32
+    if r_halo > 256 or r_tile > 256:
+        return None
+    planes, kc = (3, 64) if dtype == torch.float32 else (1, 128)
+    for tm in (64, 32):                                  # pixels per workgroup: 64, or 32 when 64 does not fit the LDS
+        if width > tm:
+            continue
+        tr, nt = min(rows, tm // width), 0
+        while tr >= 1:
+            nt = -(-(halo_rows(tr) * halo_width) // tm)
+            if nt <= 3:
+                break
+            tr -= 1
+        if tr < 1:
+            continue
+        lds = (2 * planes * tm * (kc + 8) + planes * tm * nt * (r_halo + 8) + planes * tm * (r_tile + 8)) * 2 \
+            + extra_per_pixel * tm
+        if lds <= 160 * 1024:
+            return tm, tr, nt, -(-rows // tr)
+    return None
+
+
+def _py_plan(x_shape, dtype, r1, r2, kernel_size, stride, padding, dilation, bwd):
+    """The rule of the forward (tile: output rows, halo: the input rows the taps reach) and of the data gradient (tile: dX
+    rows, halo: the dY rows the taps reach; the tap table joins the LDS), stated without the library."""
+    from tadmm import ops
+    H, W = x_shape[2], x_shape[3]
+    ho, wo = ops._conv_out_hw(H, W, kernel_size, stride, padding, dilation)
+    if ho <= 0 or wo <= 0 or H <= 0 or W <= 0:
+        return None
+    if not bwd:
+        return _conv_tile_plan(dtype, ho, wo, r1, r2,
+                               lambda tr: min(H, (tr - 1) * stride[0] + (kernel_size[0] - 1) * dilation[0] + 1), W)
+    return _conv_tile_plan(dtype, H, W, r2, r1,
+                           lambda tr: min(ho, (tr - 1 + (kernel_size[0] - 1) * dilation[0]) // stride[0] + 1), wo,
+                           extra_per_pixel=kernel_size[0] * kernel_size[1] * 2)
 
 
 def _c_plan(lib, x_shape, dtype, r1, r2, k, s, p, dl, mode):
@@ -47,9 +94,11 @@ def test_forward_plan_agrees_with_the_python_rule():
     lib = _cabi.load()
     seen = {True: 0, False: 0}
     for x_shape, dtype, r1, r2, geom in _grid():
-        want = ops._conv_chain_plan(torch.empty(x_shape, dtype=dtype, device="meta"), r1, r2, *geom)
+        want = _py_plan(x_shape, dtype, r1, r2, *geom, bwd=False)
         got = _c_plan(lib, x_shape, dtype, r1, r2, *geom, _cabi.CONV_CHAIN_FWD)
         assert got == want, (x_shape, dtype, r1, r2, geom, got, want)
+        via_ops = ops._conv_chain_plan(torch.empty(x_shape, dtype=dtype, device="meta"), r1, r2, *geom)
+        assert via_ops == want, (x_shape, dtype, r1, r2, geom, via_ops, want)
         seen[want is not None] += 1
     assert seen[True] > 100 and seen[False] > 100
 
@@ -59,9 +108,11 @@ def test_backward_plan_agrees_with_the_python_rule():
     lib = _cabi.load()
     seen = {True: 0, False: 0}
     for x_shape, dtype, r1, r2, geom in _grid():
-        want = ops._conv_chain_bwd_plan(x_shape, dtype, r1, r2, *geom)
+        want = _py_plan(x_shape, dtype, r1, r2, *geom, bwd=True)
         got = _c_plan(lib, x_shape, dtype, r1, r2, *geom, _cabi.CONV_CHAIN_BWD)
         assert got == want, (x_shape, dtype, r1, r2, geom, got, want)
+        via_ops = ops._conv_chain_bwd_plan(x_shape, dtype, r1, r2, *geom)
+        assert via_ops == want, (x_shape, dtype, r1, r2, geom, via_ops, want)
         assert ops.conv_chain_bwd_fits(torch.empty(x_shape, dtype=dtype, device="meta"), r1, r2, *geom) == (got is not None)
         seen[want is not None] += 1
     assert seen[True] > 100 and seen[False] > 100
@@ -86,6 +137,20 @@ def test_plan_examples_and_bad_arguments():
     assert lib.tadmm_ttconv_fused_plan(C.byref(d), 1, None, None, None, None, None) == 0           # every output is optional
     d.Ho = 8
     assert lib.tadmm_ttconv_fused_plan(C.byref(d), 0, None, None, None, None, None) == -1          # not the geometry's output
+
+
+@pytest.mark.parametrize("x_shape", [(1, 8, 2 ** 31, 4), (1, 8, 4, 2 ** 31)])
+def test_an_extent_beyond_int32_is_no_plan_and_no_library_call(x_shape, monkeypatch):
+    """ctypes would wrap 2**31 into the descriptor's int32 fields: both plans answer None before the library is asked."""
+    from tadmm import _cabi, ops
+
+    def no_call():
+        raise AssertionError("the library was called")
+    monkeypatch.setattr(_cabi, "load", no_call)
+    g = ((3, 3), (1, 1), (1, 1), (1, 1))
+    assert ops._conv_chain_plan(torch.empty(x_shape, dtype=torch.bfloat16, device="meta"), 32, 32, *g) is None
+    assert ops._conv_chain_bwd_plan(x_shape, torch.bfloat16, 32, 32, *g) is None
+    assert not ops.conv_chain_bwd_fits(torch.empty(x_shape, dtype=torch.bfloat16, device="meta"), 32, 32, *g)
 
 
 def test_symbols_are_exported_and_bound():
