@@ -165,6 +165,9 @@ void launch_gemm_bf16_nt(const void* A, const void* Bt, void* C, int M, int N, i
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 template <typename T> using G = T __attribute__((address_space(1)));
 template <typename T> __device__ __forceinline__ G<T>* gp(T* p) { return (G<T>*)p; }
+// 16 bytes at 4-byte alignment: a wide global load is legal at dword alignment, so one load path serves operands and
+// views whose rows start anywhere
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 #endif
 
 // ---------------------------------------------------------------- forward chains of the factorised layers (chain.hip)

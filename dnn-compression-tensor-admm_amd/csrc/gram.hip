@@ -18,6 +18,7 @@
 // For a Gram both operands are rows of the same matrix: B[k][j] = X[c0+j][k] has the *same* lane
 // map as the A operand of row block c0, so one load serves both roles.
 #include "common.h"
+#include <type_traits>
 
 namespace tadmm {
 
@@ -48,7 +49,8 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const GramDesc* __res
   int ti, tj;
   tile_pair(tp, d.nt, ti, tj);
   const bool diag = (ti == tj);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // (the wave index in a scalar register: the K quarter, and with it every loop bound below, is wave-uniform)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, q = lane >> 4;
 
   const int kbeg = ks * d.kchunk;
@@ -59,97 +61,118 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const GramDesc* __res
   const int wk1 = min(kend, wk0 + per);
 
   double4_t acc00 = {0, 0, 0, 0}, acc01 = {0, 0, 0, 0}, acc10 = {0, 0, 0, 0}, acc11 = {0, 0, 0, 0};
-  const float* A = d.A;
+  const G<const float>* A = gp(d.A);
   const int N = d.N;
   const int ra0 = ti * 32 + r, ra1 = ra0 + 16;   // G-rows of this lane for the A role
   const int rb0 = tj * 32 + r, rb1 = rb0 + 16;   // G-rows for the B role
   const float ma0 = ra0 < N ? 1.f : 0.f, ma1 = ra1 < N ? 1.f : 0.f;
   const float mb0 = rb0 < N ? 1.f : 0.f, mb1 = rb1 < N ? 1.f : 0.f;
   const int64_t ld = d.n;
+  // G-indices beyond N are clamped to N - 1 (a valid row / column of A) and their values multiplied by 0
+  const int ca0 = min(ra0, N - 1), ca1 = min(ra1, N - 1), cb0 = min(rb0, N - 1), cb1 = min(rb1, N - 1);
 
   struct Chunk { float a0[4], a1[4], b0[4], b1[4]; };   // this lane's 4 reduction indices of a 16-wide k chunk
-  // 16 fp64 MFMAs per chunk; the next chunk's loads are issued before them (register double buffer), so the
-  // matrix cores do not wait for HBM/L2 latency
-  auto mma = [&](const Chunk& c) {
+  const int nfull =(wk1 - wk0) >> 4, rem = (wk1 - wk0) & 15;
+  const int ktail = wk0 + 16 * nfull;
+  // The wave's K range [wk0, wk1) is nfull whole chunks of 16 and a tail of rem < 16 (wk0 is a multiple of 16: kchunk is
+  // one of 64).  Whole chunks are fetched by unconditional loads NPF chunks ahead of their MFMAs -- a wave's chunk is
+  // far shorter than a round trip to L2 or HBM, and the plan's launches put one or two workgroups on a CU -- into a ring
+  // of register sets with compile-time indices; chunk indices past the end are clamped to the last whole chunk (a few
+  // repeated loads) instead of guarding the load, so that the same number of loads is in flight on every path and the
+  // waits stay counted.  The tail is fetched first, by 4-byte loads whose k is clamped to wk1 - 1, and consumed last, with
+  // +0 where k >= wk1 (selected where it is consumed: a select next to its load becomes a branch around the load).
+  // Every address is inside A: a clamped row / column index is < N, and k < wk1 <= K.  A diagonal tile (block-uniform,
+  // decided once, outside the loops) loads the A role only.
+  auto body = [&](auto diag_tag, auto trans_tag) {
+    constexpr bool kDiag = decltype(diag_tag)::value, kTrans = decltype(trans_tag)::value;
+    constexpr int NPF = kTrans ? 3 : 4;          // trans: 16 loads per chunk, three chunks stay below the 63 a wave can count
+    // 16 fp64 MFMAs per chunk
+    auto mma = [&](const Chunk& c) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const double da0 = c.a0[e], da1 = c.a1[e];
-      const double db0 = diag ? da0 : (double)c.b0[e], db1 = diag ? da1 : (double)c.b1[e];
-      acc00 = mfma_f64(da0, db0, acc00);
-      acc01 = mfma_f64(da0, db1, acc01);
-      if (!diag) acc10 = mfma_f64(da1, db0, acc10);
-      acc11 = mfma_f64(da1, db1, acc11);
-    }
-  };
-
-  if (!d.trans) {
-    // rows of A are G-indices, reduction runs along the contiguous dimension; lane (r,q) takes k = kk+4q .. +3
-    // (a permutation of the MFMA k order that both operands share)
-    const bool vec = ((ld & 3) == 0) && ((((uintptr_t)A) & 15) == 0);
-    const float* pa0 = A + (int64_t)min(ra0, N - 1) * ld;
-    const float* pa1 = A + (int64_t)min(ra1, N - 1) * ld;
-    const float* pb0 = A + (int64_t)min(rb0, N - 1) * ld;
-    const float* pb1 = A + (int64_t)min(rb1, N - 1) * ld;
-    auto fetch = [&](int kk, Chunk& c) {
-      const int k = kk + 4 * q;
-      if (vec && k + 3 < wk1) {
-        const float4 t0 = *reinterpret_cast<const float4*>(pa0 + k);
-        const float4 t1 = *reinterpret_cast<const float4*>(pa1 + k);
-        c.a0[0] = t0.x * ma0; c.a0[1] = t0.y * ma0; c.a0[2] = t0.z * ma0; c.a0[3] = t0.w * ma0;
-        c.a1[0] = t1.x * ma1; c.a1[1] = t1.y * ma1; c.a1[2] = t1.z * ma1; c.a1[3] = t1.w * ma1;
-        if (!diag) {
-          const float4 t2 = *reinterpret_cast<const float4*>(pb0 + k);
-          const float4 t3 = *reinterpret_cast<const float4*>(pb1 + k);
-          c.b0[0] = t2.x * mb0; c.b0[1] = t2.y * mb0; c.b0[2] = t2.z * mb0; c.b0[3] = t2.w * mb0;
-          c.b1[0] = t3.x * mb1; c.b1[1] = t3.y * mb1; c.b1[2] = t3.z * mb1; c.b1[3] = t3.w * mb1;
-        }
+      for (int e = 0; e < 4; ++e) {
+        const double da0 = c.a0[e], da1 = c.a1[e];
+        const double db0 = kDiag ? da0 : (double)c.b0[e], db1 = kDiag ? da1 : (double)c.b1[e];
+        acc00 = mfma_f64(da0, db0, acc00);
+        acc01 = mfma_f64(da0, db1, acc01);
+        if (!kDiag) acc10 = mfma_f64(da1, db0, acc10);
+        acc11 = mfma_f64(da1, db1, acc11);
+      }
+    };
+    // what the loads returned -> what the MFMAs see: rows beyond N times 0, the K tail +0 (applied when a chunk is
+    // consumed, so that nothing waits for a load where it is issued).  lane k of element e: see fetch / fetch_tail
+    auto cook = [&](const Chunk& c, bool tail) {
+      Chunk o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool ok = !tail || (ktail + (kTrans ? 4 * e + q : 4 * q + e)) < wk1;
+        o.a0[e] = ok ? c.a0[e] * ma0 : 0.f;
+        o.a1[e] = ok ? c.a1[e] * ma1 : 0.f;
+        o.b0[e] = (ok && !kDiag) ? c.b0[e] * mb0 : 0.f;
+        o.b1[e] = (ok && !kDiag) ? c.b1[e] * mb1 : 0.f;
+      }
+      return o;
+    };
+    const G<const float>* pa0 = A + (kTrans ? (int64_t)ca0 : (int64_t)ca0 * ld);
+    const G<const float>* pa1 = A + (kTrans ? (int64_t)ca1 : (int64_t)ca1 * ld);
+    const G<const float>* pb0 = A + (kTrans ? (int64_t)cb0 : (int64_t)cb0 * ld);
+    const G<const float>* pb1 = A + (kTrans ? (int64_t)cb1 : (int64_t)cb1 * ld);
+    auto ld4 = [&](float (&o)[4], const G<const float>* p) {
+      const f4u t = *reinterpret_cast<const G<const f4u>*>(p);
+      o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    };
+    // a whole chunk at kk.  Row-contiguous: rows of A are G-indices and the reduction runs along the contiguous dimension;
+    // lane (r,q) takes k = kk+4q .. +3 (a permutation of the MFMA k order that both operands share), one 16-byte load per
+    // row.  trans: columns of A are G-indices, the reduction runs over rows: lane (r,q) reads A[kk+4e+q][col]
+    auto fetch = [&](Chunk& c, int kk) {
+      if (!kTrans) {
+        const int k = kk + 4 * q;
+        ld4(c.a0, pa0 + k); ld4(c.a1, pa1 + k);
+        if (!kDiag) { ld4(c.b0, pb0 + k); ld4(c.b1, pb1 + k); }
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const bool ok = (k + e) < wk1;
-          c.a0[e] = ok ? pa0[k + e] * ma0 : 0.f;
-          c.a1[e] = ok ? pa1[k + e] * ma1 : 0.f;
-          c.b0[e] = (ok && !diag) ? pb0[k + e] * mb0 : 0.f;
-          c.b1[e] = (ok && !diag) ? pb1[k + e] * mb1 : 0.f;
+          const int64_t ro = (int64_t)(kk + 4 * e + q) * ld;
+          c.a0[e] = pa0[ro]; c.a1[e] = pa1[ro];
+          if (!kDiag) { c.b0[e] = pb0[ro]; c.b1[e] = pb1[ro]; }
         }
       }
     };
-    if (wk0 < wk1) {
-      Chunk cur, nxt;
-      fetch(wk0, cur);
-      for (int kk = wk0; kk < wk1; kk += 16) {
-        const bool more = kk + 16 < wk1;
-        if (more) fetch(kk + 16, nxt);
-        mma(cur);
-        if (more) cur = nxt;
-      }
-    }
-  } else {
-    // columns of A are G-indices, reduction runs over rows: lane (r,q) reads A[kk+4e+q][col]
-    const int ca0 = min(ra0, N - 1), ca1 = min(ra1, N - 1), cb0 = min(rb0, N - 1), cb1 = min(rb1, N - 1);
-    auto fetch = [&](int kk, Chunk& c) {
+    auto fetch_tail = [&](Chunk& c) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int k = kk + 4 * e + q;
-        const bool ok = k < wk1;
-        const float* row = A + (int64_t)min(k, d.K - 1) * ld;
-        c.a0[e] = ok ? row[ca0] * ma0 : 0.f;
-        c.a1[e] = ok ? row[ca1] * ma1 : 0.f;
-        c.b0[e] = (ok && !diag) ? row[cb0] * mb0 : 0.f;
-        c.b1[e] = (ok && !diag) ? row[cb1] * mb1 : 0.f;
+        const int kc = min(ktail + (kTrans ? 4 * e + q : 4 * q + e), wk1 - 1);
+        const int64_t o = kTrans ? (int64_t)kc * ld : (int64_t)kc;
+        c.a0[e] = pa0[o]; c.a1[e] = pa1[o];
+        if (!kDiag) { c.b0[e] = pb0[o]; c.b1[e] = pb1[o]; }
       }
     };
-    if (wk0 < wk1) {
-      Chunk cur, nxt;
-      fetch(wk0, cur);
-      for (int kk = wk0; kk < wk1; kk += 16) {
-        const bool more = kk + 16 < wk1;
-        if (more) fetch(kk + 16, nxt);
-        mma(cur);
-        if (more) cur = nxt;
+    Chunk tail = {};
+    if (rem) fetch_tail(tail);
+    if (nfull > 0) {
+      const int last = nfull - 1;
+      Chunk R[NPF] = {};
+#pragma unroll
+      for (int u = 0; u < NPF; ++u) fetch(R[u], wk0 + 16 * min(u, last));
+      int c = 0;
+      for (; c + NPF <= nfull; c += NPF) {
+#pragma unroll
+        for (int u = 0; u < NPF; ++u) {
+          const Chunk cur = cook(R[u], false);
+          fetch(R[u], wk0 + 16 * min(c + u + NPF, last));
+          __builtin_amdgcn_sched_barrier(0);   // the loads go out before the MFMAs
+          mma(cur);
+        }
       }
+#pragma unroll
+      for (int u = 0; u < NPF - 1; ++u)          // chunks c .. nfull - 1 sit in R[0], R[1], ...
+        if (c + u < nfull) mma(cook(R[u], false));
     }
-  }
+    if (rem) mma(cook(tail, true));
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (!d.trans) { if (diag) body(T(), F()); else body(F(), F()); }
+  else          { if (diag) body(T(), T()); else body(F(), T()); }
 
   // cross-wave reduction in a fixed order
 #pragma unroll
