@@ -455,7 +455,8 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   e.XT = XT; e.N = N; e.Npad = Npad; e.ld = ld; e.nb = geo.nb; e.off = offs; e.done = done; e.lam = lam; e.order = order;
   e.sigma = sigma; e.r = r; e.mode = 2; e.out_a = nullptr; e.out_b = nullptr; e.evec_out = evecs_out;
   e.sblk = sblk;
-  const EigMaps maps = eig_maps(L, ev, false);
+  EigMaps maps;
+  if (const int rc = eig_maps(h, L, ev, false, maps)) return rc;
   const std::vector<BlockRef>* mv[4] = {&maps.tick, &maps.norm, &maps.ext, &maps.self};
   HIP_OK(h, hipMemcpyAsync(edev, &e, sizeof e, hipMemcpyHostToDevice, s));
   for (int i = 0; i < 4; ++i) {
@@ -464,7 +465,8 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
     HIP_OK(h, hipMemcpyAsync(base + o_map[i], mv[i]->data(), mv[i]->size() * sizeof(BlockRef), hipMemcpyHostToDevice, s));
   }
   HIP_OK(h, hipStreamSynchronize(s));
-  const int mode = L.mode, units = L.players[0];
+  const bool super = L.kernel == EigTick::SuperPairs;
+  const int units = L.players[0];
   const BlockRef* m_tick = (const BlockRef*)(base + L.tick.map_off);
   const BlockRef* m_self = (const BlockRef*)(base + L.self.map_off);
   const double tol = 1e-9;
@@ -494,11 +496,11 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   int hdone = 0;
   for (; gs < 40 && !conv; ++gs) {
     for (int t = 0; t < units - 1; ++t, ++tick) {
-      if (mode >= 2) {
-        if (t == 0) HIP_OK(h, launch_jacobi_self(edev, m_self, L.self.nblocks, tick, tol, 1, ld, s));
+      if (super) {
+        if (t == 0) HIP_OK(h, launch_jacobi_self(edev, m_self, L.self.nblocks, tick, tol, ld, s));
         HIP_OK(h, launch_jacobi_tick3(edev, m_tick, L.tick.nblocks, tick, tol, ld, s));
       } else {
-        HIP_OK(h, launch_jacobi_tick(edev, m_tick, L.tick.nblocks, tick, tol, 1, L.tick_lds, mode == 1, s));
+        HIP_OK(h, launch_jacobi_tick(edev, m_tick, L.tick.nblocks, tick, tol, L.tick_lds, s));
       }
     }
     HIP_OK(h, hipMemcpyAsync(hoff, offs, 24, hipMemcpyDeviceToHost, s));

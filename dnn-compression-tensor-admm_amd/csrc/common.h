@@ -95,26 +95,25 @@ constexpr int kJacobiMaxN = 8160;
 bool jacobi_size_supported(int n);
 size_t jacobi_tick_stream_lds_bytes();
 size_t jacobi_tick_lds_bytes(int ld_max);    // dynamic LDS of a tick1 launch whose largest problem has row length ld_max
-size_t jacobi_tick2_lds_bytes(int ld_max);   // same for the LDS-resident super-pair kernel
-bool jacobi_tick2_fits(int ld_max);
-// super=false: one workgroup per pair of 8-column blocks (nb/2 per problem, nb-1 ticks per sweep)
-// super=true : one workgroup per pair of 16-column super-blocks (nb/4 per problem, nb/2-1 ticks per sweep)
+// pair kernel: one workgroup per pair of 8-column blocks (nb/2 per problem, nb-1 ticks per sweep); LDS resident, or
+// streamed when lds_bytes (= jacobi_tick_lds_bytes of the group) exceeds the 160 KiB of a workgroup
 hipError_t launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                              int inner_sweeps, size_t lds_bytes, bool super, hipStream_t s);
+                              size_t lds_bytes, hipStream_t s);
 void dump_stamps();
 size_t jacobi_tick3_lds_bytes(int ld_max);
 bool jacobi_tick3_fits(int ld_max);
-// tick3: super-pair kernel with carried self-Grams (one cross-Gram per launch, round-2 solve overlapped with the
-// round-1 update).  Needs launch_jacobi_self on the first tick of every sweep (it refreshes EigDesc::sblk).
+// tick3: super-pair kernel with carried self-Grams, one workgroup per pair of 16-column super-blocks (nb/4 per problem,
+// nb/2-1 ticks per sweep; one cross-Gram per launch, round-2 solve overlapped with the round-1 update).  Needs launch_jacobi_self on the first tick of every sweep (it refreshes EigDesc::sblk).
 hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
                                int ld_max, hipStream_t s);
-// rows of an eigen-solver image are whole 1 KiB chunks (128 doubles: LDS-DMA loads).  The LDS-resident pair kernel
+// rows of an eigen-solver image are whole 1 KiB chunks (128 doubles): the tick kernels have no other loader than the
+// LDS-DMA one, and eig_maps (host.h) refuses a descriptor whose ld is not such a multiple.  The LDS-resident pair kernel
 // holds 16 such rows up to ld = 1152; longer rows go through the streamed pair kernel.
 constexpr int kLdResidentMax = 1152;
 static inline int eig_ld(int N) { return (N + 127) / 128 * 128; }
 // once-per-sweep companion of tick3 (tick1 in self mode): within-block pairs + refresh of the carried self-Grams
 hipError_t launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                              int inner_sweeps, int ld_max, hipStream_t s);
+                              int ld_max, hipStream_t s);
 // whole eigen-solve of small problems (Npad <= 64) in one launch, one workgroup per problem; converged flags go to
 // verdict_pinned[1 + p]
 bool jacobi_small_fits(int npad_max);

@@ -254,16 +254,17 @@ static inline void xcd_by_key(std::vector<BlockRef>& m, KeyFn key) {
   m.swap(out);
 }
 
-// Which Jacobi kernel a group of problems whose longest row is ld_max uses:
-// 3 = tick3 (carried self-Grams) + self pass, 1 = LDS super-pair, 0 = plain pair kernel.
-// TADMM_JACOBI_MODE (0 | 1 | 3) overrides the preference, never the capacity checks.
-static inline int choose_jacobi_mode(int ld_max) {
+// Which tick kernel a group of problems uses.
+enum class EigTick {
+  Pairs,        // one workgroup per pair of 8-column blocks: jacobi_tick_kernel, or the streamed kernel for long rows
+  SuperPairs,   // one workgroup per pair of 16-column super-blocks: jacobi_tick3_kernel + the self pass once per sweep
+};
+// Super-pairs whenever 32 columns of the group's longest row fit the LDS (ld_max <= 512).  TADMM_JACOBI_MODE=0 asks for
+// pairs (A/B measurements); any other value means the default.
+static inline EigTick choose_eig_tick(int ld_max) {
   const char* em = getenv("TADMM_JACOBI_MODE");
-  int want = em ? atoi(em) : 3;
-  if (want != 0 && want != 1) want = 3;
-  if (want == 3 && (!jacobi_tick3_fits(ld_max) || ld_max % 64)) want = 1;
-  if (want == 1 && !jacobi_tick2_fits(ld_max)) want = 0;
-  return want;
+  const bool want_pairs = em && atoi(em) == 0;
+  return (!want_pairs && jacobi_tick3_fits(ld_max)) ? EigTick::SuperPairs : EigTick::Pairs;
 }
 
 // One sweep period for every problem of a tick3 group (EigDesc::period); TADMM_JACOBI_ALIGN=0 restores per-problem periods.
@@ -308,9 +309,9 @@ struct EigGroup {
   int neig = 0;
   const int* players = nullptr;     // per problem: tournament players (super-blocks or blocks)
   int gsteps = 0;                   // ticks per global sweep = max(players - 1)
-  int mode = 0;
+  EigTick kernel = EigTick::Pairs;
   int ld_max = 0;
-  size_t tick_lds = 0;
+  size_t tick_lds = 0;              // Pairs: dynamic LDS of the tick launches
   const BlockRef* tick_map = nullptr; int tick_blocks = 0;
   const BlockRef* self_map = nullptr; int self_blocks = 0;
   double* prev_dev = nullptr;       // [neig] scratch of the convergence kernel
@@ -336,9 +337,9 @@ struct EigLayout {
   std::vector<int> mid;           // per problem: 128 / 192 when it may take the direct route of tridiag_mid.hip, else 0
   int neig = 0;
   int gsteps = 0;                 // ticks per global sweep = max(players - 1)
-  int mode = 0;                   // 0: pairs (tick1), 1: LDS super-pairs (tick2), 3: tick3 + self pass
+  EigTick kernel = EigTick::Pairs;
   int ld_max = 0, npad_max = 0;
-  size_t tick_lds = 0;            // dynamic LDS of the tick launches
+  size_t tick_lds = 0;            // Pairs: dynamic LDS of the tick launches
   bool aligned = false;           // every EigDesc carries period = gsteps
   size_t prev_off = 0;            // [neig] doubles of the convergence kernel (taken by the caller)
   int last_sweeps = 0;            // global sweeps the previous run needed
@@ -351,7 +352,7 @@ struct EigLayout {
     EigGroup g;
     g.ed = (const EigDesc*)(ws + tick.desc_off); g.neig = neig;
     g.players = players.data(); g.row_len = row_len.data(); g.mid_sizes = mid.data();
-    g.gsteps = gsteps; g.mode = mode; g.aligned = aligned;
+    g.gsteps = gsteps; g.kernel = kernel; g.aligned = aligned;
     g.ld_max = ld_max; g.npad_max = npad_max; g.tick_lds = tick_lds;
     g.tick_map = (const BlockRef*)(ws + tick.map_off); g.tick_blocks = tick.nblocks;
     g.self_map = (const BlockRef*)(ws + self.map_off); g.self_blocks = self.nblocks;
@@ -373,17 +374,22 @@ struct EigLayout {
 
 // Kernel choice, players and the four block maps of a group (counts go into the layout's phases, offsets do not).
 // `align` (tick3 groups, unless TADMM_JACOBI_ALIGN=0): stamp one sweep period on every problem.
+// Every eigen-solver descriptor of the library passes through here, so this is where the premise of the tick kernels'
+// loader is checked: rows of whole 1 KiB pieces (eig_ld).
 struct EigMaps { std::vector<BlockRef> tick, self, norm, ext; };
-static inline EigMaps eig_maps(EigLayout& l, std::vector<EigDesc>& descs, bool align) {
-  EigMaps m;
+static inline int eig_maps(tadmm_handle h, EigLayout& l, std::vector<EigDesc>& descs, bool align, EigMaps& m) {
+  for (const EigDesc& e : descs)
+    if (e.ld <= 0 || e.ld % 128)
+      CTX_FAIL(h, TADMM_ERR_INVALID, "internal: eigen-problem (N = %d) with rows of %d doubles; the Jacobi kernels need a "
+               "multiple of 128", e.N, e.ld);
   l.neig = (int)descs.size();
   l.ld_max = l.npad_max = l.gsteps = 0;
   l.players.clear(); l.row_len.clear(); l.mid.clear();
   for (const EigDesc& e : descs) { l.ld_max = std::max(l.ld_max, e.ld); l.npad_max = std::max(l.npad_max, e.Npad); }
   // tick shape of the group: LDS-resident super-pairs when every problem fits, else plain pairs
-  l.mode = descs.empty() ? 0 : choose_jacobi_mode(l.ld_max);
-  const bool super = l.mode >= 1;
-  l.tick_lds = l.mode == 1 ? jacobi_tick2_lds_bytes(l.ld_max) : jacobi_tick_lds_bytes(l.ld_max);
+  l.kernel = descs.empty() ? EigTick::Pairs : choose_eig_tick(l.ld_max);
+  const bool super = l.kernel == EigTick::SuperPairs;
+  l.tick_lds = jacobi_tick_lds_bytes(l.ld_max);
   for (int pq = 0; pq < l.neig; ++pq) {
     const EigDesc& e = descs[pq];
     const int units = super ? e.nb / 2 : e.nb;       // players of the tournament
@@ -392,27 +398,31 @@ static inline EigMaps eig_maps(EigLayout& l, std::vector<EigDesc>& descs, bool a
     l.mid.push_back((e.scratch && eig_mid_direct_size(e.N) && e.N == e.Npad) ? e.N : 0);
     l.gsteps = std::max(l.gsteps, units - 1);
     for (int b = 0; b < units / 2; ++b) m.tick.push_back(BlockRef{pq, b});
-    if (l.mode >= 2) for (int b = 0; b < units; ++b) m.self.push_back(BlockRef{pq, b});
+    if (super) for (int b = 0; b < units; ++b) m.self.push_back(BlockRef{pq, b});
     for (int b = 0; b < (e.Npad + 3) / 4; ++b) m.norm.push_back(BlockRef{pq, b});
     for (int b = 0; b < (e.r + 3) / 4; ++b) m.ext.push_back(BlockRef{pq, b});
   }
   xcd_group(m.tick);
   xcd_group(m.self);
-  l.aligned = l.mode >= 2 && align && align_sweeps_on();
+  l.aligned = super && align && align_sweeps_on();
   if (l.aligned) for (EigDesc& e : descs) e.period = l.gsteps;
   l.tick.nprob = l.self.nprob = l.norm.nprob = l.ext.nprob = l.neig;
   l.tick.nblocks = (int)m.tick.size(); l.self.nblocks = (int)m.self.size();
   l.norm.nblocks = (int)m.norm.size(); l.ext.nblocks = (int)m.ext.size();
-  return m;
+  return TADMM_OK;
 }
 
 // eig_maps + placement: descriptors and tick map, then the self, norm and ext maps, in that order from `da`
-static inline void build_eig_layout(EigLayout& l, std::vector<EigDesc>& descs, bool align, Arena& da, HostImage* img) {
-  const EigMaps m = eig_maps(l, descs, align);
+static inline int build_eig_layout(tadmm_handle h, EigLayout& l, std::vector<EigDesc>& descs, bool align, Arena& da,
+                                   HostImage* img) {
+  EigMaps m;
+  const int rc = eig_maps(h, l, descs, align, m);
+  if (rc != TADMM_OK) return rc;
   place_phase(l.tick, da, img, descs.data(), descs.size() * sizeof(EigDesc), l.neig, m.tick);
   place_map_like(l.self, l.tick, da, img, m.self);
   place_map_like(l.norm, l.tick, da, img, m.norm);
   place_map_like(l.ext, l.tick, da, img, m.ext);
+  return TADMM_OK;
 }
 
 // Runs jacobi_init + sweeps until every problem of the group has its `done` flag.
@@ -424,9 +434,9 @@ static inline void build_eig_layout(EigLayout& l, std::vector<EigDesc>& descs, b
 // for small problems that are long finished.
 // Small groups (every problem <= 64 columns) run in ONE launch (jacobi_small_kernel decides convergence itself);
 // *small_pending is set and the caller, after queueing the group's finalize launches, calls check_small_group.
-static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll, double tol, int inner_sweeps,
-                                int max_sweeps, bool debug, hipStream_t s, int* sweeps_out, bool* small_pending,
-                                JacobiTiming* jt = nullptr) {
+static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll, double tol, int max_sweeps, bool debug,
+                                hipStream_t s, int* sweeps_out, bool* small_pending, JacobiTiming* jt = nullptr) {
+  const bool super = g.kernel == EigTick::SuperPairs;
   *sweeps_out = 0;
   *small_pending = false;
   if (g.neig == 0) return TADMM_OK;
@@ -463,7 +473,7 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
   // (tridiag_mid.hip), ONE launch per size instead of ~80; what it solves and verifies has its `done` word set and the
   // tournament below skips it -- if that is every problem of the group the tournament is not queued at all.  The host has
   // to know, so this costs one stream round trip per group.
-  if (g.mode >= 2 && g.mid_sizes && eig_mid_direct_on()) {
+  if (super && g.mid_sizes && eig_mid_direct_on()) {
     bool any192 = false, any128 = false;
     for (int q = 0; q < g.neig; ++q) { any192 = any192 || g.mid_sizes[q] == 192; any128 = any128 || g.mid_sizes[q] == 128; }
     if (any192 || any128) {
@@ -498,11 +508,11 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
   };
   for (; gs < max_sweeps && !all_done; ++gs) {
     for (int t = 0; t < g.gsteps; ++t, ++tick) {
-      if (g.mode >= 2) {
+      if (super) {
         bool any_first = false;     // does any unfinished problem start a sweep of its own at this tick?
         for (int q = 0; q < g.neig && !any_first; ++q)
           any_first = !known_done[q] && g.players[q] > 1 && (tick % (g.aligned ? g.gsteps : g.players[q] - 1)) == 0;
-        if (any_first) HIP_OK(h, launch_jacobi_self(g.ed, g.self_map, g.self_blocks, tick, tol, inner_sweeps, g.ld_max, s));
+        if (any_first) HIP_OK(h, launch_jacobi_self(g.ed, g.self_map, g.self_blocks, tick, tol, g.ld_max, s));
         const bool timed = jt && jt->on;
         if (timed) (void)hipEventRecord(jt->a, s);
         HIP_OK(h, launch_jacobi_tick3(g.ed, g.tick_map, g.tick_blocks, tick, tol, g.ld_max, s));
@@ -525,10 +535,10 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
           }
         }
       } else {
-        HIP_OK(h, launch_jacobi_tick(g.ed, g.tick_map, g.tick_blocks, tick, tol, inner_sweeps, g.tick_lds, g.mode == 1, s));
+        HIP_OK(h, launch_jacobi_tick(g.ed, g.tick_map, g.tick_blocks, tick, tol, g.tick_lds, s));
       }
     }
-    launch_jacobi_conv(g.ed, g.neig, tick, tol, g.mode >= 1, g.prev_dev, poll.host + (size_t)(gs & 1) * poll.stride, s);
+    launch_jacobi_conv(g.ed, g.neig, tick, tol, super, g.prev_dev, poll.host + (size_t)(gs & 1) * poll.stride, s);
     {   // a failed launch (LDS attribute not set on this device, bad configuration) must surface, not spin to max_sweeps
       const hipError_t le = hipGetLastError();
       if (le != hipSuccess) CTX_FAIL(h, TADMM_ERR_HIP, "Jacobi launch failed: %s", hipGetErrorString(le));
@@ -572,8 +582,8 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
   if (debug) {
     int pmax = 0;
     for (int q = 0; q < g.neig; ++q) pmax = std::max(pmax, g.players[q]);
-    fprintf(stderr, "[tadmm] eig group: neig=%d players_max=%d ticks/sweep=%d wgs/tick=%d sweeps=%d ticks=%d mode=%d\n",
-            g.neig, pmax, g.gsteps, g.tick_blocks, all_done ? needed : gs, tick, g.mode);
+    fprintf(stderr, "[tadmm] eig group: neig=%d players_max=%d ticks/sweep=%d wgs/tick=%d sweeps=%d ticks=%d kernel=%s\n",
+            g.neig, pmax, g.gsteps, g.tick_blocks, all_done ? needed : gs, tick, super ? "super-pairs" : "pairs");
   }
   if (!all_done) CTX_FAIL(h, TADMM_ERR_NOCONVERGE, "Jacobi did not converge in %d sweeps", max_sweeps);
   *sweeps_out = needed;

@@ -19,11 +19,12 @@
 //          carries the two self-Grams from launch to launch, computes ONE cross-Gram tile, and runs 2 rounds of
 //          2 concurrent 16x16 sub-problems (see the header of jacobi_tick3_kernel); the within-super-block
 //          pairs are rotated once per sweep by tick1 in "self mode", which also refreshes the carried Grams;
-//   tick2 (fallback, ld <= ~590): the same super-pair shape, every Gram recomputed from the columns;
-//   tick1 (any ld that fits 16 columns in LDS): a workgroup owns one pair (16 columns);
+//   tick1 (fallback, ld > 512): a workgroup owns one pair (16 columns), LDS resident up to ld = 1152
+//          (jacobi_tick_kernel), streamed through the LDS in chunks beyond (jacobi_tick_stream_kernel);
 //   small (Npad <= 64): the whole eigen-solve in one launch, one workgroup per problem (jacobi_small_kernel).
-// Index pairs inside a block (tick1) / inside a super-block (tick2) are rotated on the first tick of a
-// sweep only, when every (super-)block is in exactly one pair.
+// Index pairs inside a block are rotated on the first tick of a sweep only, when every block is in exactly one pair.
+// Every row length is a multiple of 128 doubles (checked where the descriptors are grouped, host.h: eig_maps): the
+// columns enter the LDS in whole 1 KiB pieces.
 //
 // Convergence.  Every pair visit records, *before* rotating, max_ij |h_ij| / (sqrt(h_ii h_jj) * w_ij) with
 // w_ij = max(1, 1e-14/tol * lambda_max/min(lambda_i, lambda_j)): columns with small eigenvalues carry fp64
@@ -97,19 +98,25 @@ __device__ __forceinline__ PairScratch carve_scratch(double* base) {
   return s;
 }
 
-// H partial of one wave: rows `lrow(r)` of the LDS slab, columns [i0, i1) (multiple of 8 long)
-__device__ __forceinline__ void pair_gram_partial(const double* __restrict__ Xs, int ldp, int lrow_r, int i0, int i1,
-                                                  int q, double* __restrict__ red_w, int lane) {
-  const double* row = Xs + lrow_r * ldp;
+// One wave's share of H = Xp^T Xp: lane (r, q) feeds row r of the pair (`row` points at it), 8 columns per step, into
+// two accumulators (over .x / .y) that are summed at the end; element e of the sum is H[q + 4e][r] (MFMA D layout).
+struct GramAcc {
   double4_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
-  for (int i = i0; i < i1; i += 8) {
-    const double2_t v = *reinterpret_cast<const double2_t*>(row + i + 2 * q);
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, v.x, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, v.y, acc1, 0, 0, 0);
+  // columns [i0, i1) of the row (a multiple of 8 long)
+  __device__ __forceinline__ void add(const double* __restrict__ row, int i0, int i1, int q) {
+    for (int i = i0; i < i1; i += 8) {
+      const double2_t v = *reinterpret_cast<const double2_t*>(row + i + 2 * q);
+      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, v.x, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, v.y, acc1, 0, 0, 0);
+    }
   }
+  __device__ __forceinline__ double sum(int e) const { return acc0[e] + acc1[e]; }
+  // the wave's partial for pair_gram_reduce
+  __device__ __forceinline__ void store_partial(double* __restrict__ red_w, int lane) const {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) red_w[lane * 4 + e] = acc0[e] + acc1[e];
-}
+    for (int e = 0; e < 4; ++e) red_w[lane * 4 + e] = sum(e);
+  }
+};
 
 // 256 threads (t = 0..255) fold the 4 wave partials into H and reset Q = I
 __device__ __forceinline__ void pair_gram_reduce(const PairScratch& S, int t) {
@@ -151,11 +158,12 @@ __device__ __forceinline__ float wave_max_f32(float v) {
   return fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
 }
 
+// -DTADMM_STAMPS: thread 0 of the middle workgroup adds the cycles since `t0` to slot i (dump_stamps prints the slots)
 #ifdef TADMM_STAMPS
 __device__ unsigned long long g_stamps[32];
-#define SSTAMP(i) do { if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) { const unsigned long long tn = clock64(); g_stamps[i] += tn - ts; ts = tn; } } while (0)
+#define STAMP(i, t0) do { if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) g_stamps[i] += clock64() - (t0); } while (0)
 #else
-#define SSTAMP(i) do {} while (0)
+#define STAMP(i, t0) do {} while (0)
 #endif
 // Inner solve, row formulation: two-sided cyclic Jacobi on the 16x16 symmetric H, carried as the pair
 //   Y = Q^T H0   (rows rotated only)      and      Qt = Q^T,
@@ -176,7 +184,7 @@ __device__ __forceinline__ double pair_inner_solve_fast(const PairScratch& S, in
   double (*Hs)[kHP] = S.H;
   double (*Qs)[kHP] = S.Q;
 #ifdef TADMM_STAMPS
-  unsigned long long ts = clock64();
+  const unsigned long long ts = clock64();
 #endif
   const double inv_hmax = hmax > 0.0 ? 1.0 / hmax : 1.0;
   double mx = 0.0;
@@ -199,7 +207,7 @@ __device__ __forceinline__ double pair_inner_solve_fast(const PairScratch& S, in
     }
     mx = (double)wave_max_f32(mxf);
   }
-  SSTAMP(10);
+  STAMP(10, ts);
   int did = 0;
   if (!kMeasure || mx > 1e-15) {
     const int g8 = lane >> 3, l8 = lane & 7;
@@ -262,7 +270,7 @@ __device__ __forceinline__ double pair_inner_solve_fast(const PairScratch& S, in
       *yp = vp; *tp = up;
       wave_lds_fence();
     }
-    SSTAMP(11);
+    STAMP(11, ts);
     // within-block pairs (self pass only)
     for (int st = 0; within && st < kJB - 1; ++st) {
       int a2, b2;
@@ -313,120 +321,162 @@ __device__ __forceinline__ double pair_inner_solve_fast(const PairScratch& S, in
     for (int k = 0; k < 4; ++k) { const int e = lane * 4 + k; hcur_out[e] = Hs[e >> 4][e & 15]; }
   }
   if (lane == 0) *S.rotated = did;
-  SSTAMP(12);
+  STAMP(12, ts);
   return mx;
+}
+
+constexpr int kSuper = 2 * kPair;   // 32 rows in the slab of a super-pair
+
+// row of the slab / index inside a 32-column super-pair of entry k of the sub-pair made of the 8-blocks (u, v)
+__device__ __forceinline__ int sub_index(int u, int v, int k) { return (k < kJB) ? (u * kJB + k) : (v * kJB + (k - kJB)); }
+
+// Where a tick launch stands in the tournament of its problem, and the two rules every tick kernel applies to the
+// sweep slots EigDesc::off[0..1].  players: blocks (pair kernels) or super-blocks; period: ticks per sweep of the group's
+// schedule (EigDesc::period), 0 = the problem's own players - 1.  step >= steps: idle tick of a group schedule.
+struct TickPos {
+  int sweep, step, steps;
+  __device__ __forceinline__ TickPos(int tick, int players, int period) {
+    steps = players - 1;
+    const int per = period > 0 ? period : steps;
+    sweep = tick / per;
+    step = tick - sweep * per;
+  }
+  // A finished problem, or one whose previous sweep saw nothing left to rotate: the leader thread then sets the sticky
+  // flag.  Uniform over the workgroup.
+  __device__ __forceinline__ bool retired(const EigDesc& d, double tol, bool leader) const {
+    if (*d.done) return true;
+    if (step == 0 && sweep > 0 && d.off[(sweep - 1) & 1] < tol) {
+      if (leader) *d.done = 1;
+      return true;
+    }
+    return false;
+  }
+  // Last step of a sweep: clear the slot of the NEXT sweep.  Called behind a barrier, when every thread of the
+  // workgroup has taken its `retired` decision.
+  __device__ __forceinline__ void clear_next(const EigDesc& d, bool leader) const {
+    if (step == steps - 1 && leader) d.off[(sweep + 1) & 1] = 0.0;
+  }
+};
+
+// The rows of an LDS slab as columns of the global image XT (row j of XT = column j of X, ld doubles long): slab row k
+// is row a*half + k (k < half) or b*half + (k - half) of XT -- the two blocks (half = kJB) or super-blocks (half = kPair)
+// that meet in this workgroup -- from element c0 on (c0 > 0: the chunks of the streamed kernel).
+struct SlabCols {
+  double* XT;
+  int ld, a, b, half, c0;
+  __device__ __forceinline__ int64_t at(int k) const {
+    return (int64_t)((k < half) ? (a * half + k) : (b * half + (k - half))) * ld + c0;
+  }
+};
+
+// LDS-DMA (global_load_lds_dwordx4) of `len` elements of all 2*half slab rows: a wave moves 1 KiB pieces of a column
+// straight into LDS -- 64 lanes x 16 bytes land at consecutive LDS addresses behind a wave-uniform base, no staging
+// registers, so every piece of a wave is in flight at once (the phase is latency-, not bandwidth-bound).  Rows are whole
+// 1 KiB pieces (len % 128 == 0) and an LDS row starts 16 bytes after the previous one ends (ldp = row length + 2).
+// Wave `wave` of `nwaves` takes every nwaves-th piece.  The caller waits (s_waitcnt) before the barrier that publishes
+// the slab, and before any exit: no DMA may still target a workgroup's LDS when it ends.
+__device__ __forceinline__ void dma_load_slab(double* Xs, int ldp, const SlabCols& g, int len, int wave, int nwaves,
+                                              int lane) {
+  const int cpr = len >> 7;                          // pieces per row
+  const int npiece = 2 * g.half * cpr;
+  for (int c = wave; c < npiece; c += nwaves) {
+    const int row = c / cpr, ch = c - row * cpr;
+    const double* src = g.XT + g.at(row) + ch * 128 + lane * 2;
+    double* dst = Xs + row * ldp + ch * 128;         // wave-uniform
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+  }
+}
+
+// X[:, sub-pair (u,v)] <- X[:, (u,v)] * Q for the 16-column tiles it = wi, wi + nw, ... of the first `ncol` slab
+// columns, i.e. on the rows of the transposed slab  Y[a][:] = sum_b Q[b][a] * X[b][:]:  four MFMAs per tile, k-steps
+// t = 0..3, A[m=a][k=b] = Q[b][a], B[k=b][n=i] = slab row sub_index(u, v, b).
+// kQt: Q is passed TRANSPOSED, as the inner solve leaves it with kKeepQt.  The result goes
+//   Slab:        back into the slab, in place (a tile is touched by one wave only);
+//   Global:      to the global column image g (16 lanes write 128 contiguous bytes of one column);
+//   GlobalAgent: the same as relaxed agent-scope stores (tick3: straight from the accumulators to HBM).
+enum class QDst { Slab, Global, GlobalAgent };
+template <bool kQt, QDst kDst>
+__device__ __forceinline__ void apply_q_tiles(double* Xs, int ldp, int ncol, const double (*Q)[kHP], int u, int v, int wi,
+                                              int nw, int lane, const SlabCols& g = SlabCols{}) {
+  const int r = lane & 15, q = lane >> 4;
+  double qa[4];
+  int rowk[4];
+  int64_t growk[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    qa[t] = kQt ? Q[r][4 * t + q] : Q[4 * t + q][r];
+    const int row = sub_index(u, v, 4 * t + q);               // k = 4t+q (B operand row) and D row q+4e share this map
+    rowk[t] = row * ldp;
+    growk[t] = (kDst == QDst::Slab) ? 0 : g.at(row);
+  }
+  const int ntile = ncol >> 4;
+  for (int it = wi; it < ntile; it += nw) {
+    const int col = it * 16 + r;
+    double4_t acc = {0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[t], Xs[rowk[t] + col], acc, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (kDst == QDst::Slab) Xs[rowk[e] + col] = acc[e];
+      else if (kDst == QDst::Global) g.XT[growk[e] + col] = acc[e];
+      else __hip_atomic_store(g.XT + growk[e] + col, acc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 // Dynamic LDS layout of tick1 (doubles): X[16][ldp] | PairScratch
 __global__ __launch_bounds__(256) void jacobi_tick_kernel(const EigDesc* __restrict__ descs,
                                                           const BlockRef* __restrict__ map, int tick, double tol,
-                                                          int inner_sweeps, int self_mode) {
+                                                          int self_mode) {
   // self_mode: companion of jacobi_tick3_kernel.  The tournament runs over nb/2 super-blocks of 16
   // columns; this kernel acts only on the first tick of a sweep, one workgroup per super-block, and
   // rotates all 120 index pairs inside it (blocks 2*local and 2*local+1, `within` rotations included).
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const BlockRef br = map[blockIdx.x];
   const EigDesc d = descs[br.prob];
-  if (*d.done) return;
-  const int nb = self_mode ? (d.nb >> 1) : d.nb;
-  const int steps = nb - 1;
-  const int period = (self_mode && d.period > 0) ? d.period : steps;
-  const int sweep = tick / period;
-  const int step = tick - sweep * period;
+  const TickPos pos(tick, self_mode ? (d.nb >> 1) : d.nb, self_mode ? d.period : 0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (step == 0 && sweep > 0) {
-    if (d.off[(sweep - 1) & 1] < tol) {           // previous sweep saw nothing left to rotate
-      if (br.local == 0 && tid == 0) *d.done = 1;
-      return;
-    }
-  }
-  if (self_mode && step != 0) return;
+  const bool leader = br.local == 0 && tid == 0;
+  if (pos.retired(d, tol, leader)) return;
+  if (self_mode && pos.step != 0) return;
   const int ld = d.ld, ldp = ld + 2;
   double* Xs = smem;
   const PairScratch S = carve_scratch(Xs + kPair * ldp);
 
   int ba, bb;
   if (self_mode) { ba = 2 * br.local; bb = ba + 1; }
-  else rr_pair(nb, step, br.local, ba, bb);
+  else rr_pair(d.nb, pos.step, br.local, ba, bb);
   const int r = lane & 15, q = lane >> 4;
-  double* __restrict__ XT = d.XT;
+  const SlabCols cols{d.XT, ld, ba, bb, kJB, 0};
 
   // ---- 0. stage the pair's 16 columns (rows of XT) in LDS ----
-  if ((ld & 127) == 0) {
-    // LDS-DMA, 1 KiB chunks, every chunk of a wave in flight at once (see jacobi_tick3_kernel)
-    const int cpr = ld >> 7;
-    const int nchunk = kPair * cpr;
-    for (int c = wave; c < nchunk; c += 4) {
-      const int row = c / cpr, ch = c - row * cpr;
-      const int grow = (row < kJB) ? (ba * kJB + row) : (bb * kJB + (row - kJB));
-      const double* src = XT + (int64_t)grow * ld + ch * 128 + lane * 2;
-      double* dst = Xs + row * ldp + ch * 128;        // wave-uniform
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-  } else {
-    const int c2n = ld >> 1;                       // double2 chunks per row
-    const int total = kPair * c2n;
-    constexpr int kBatch = 8;                      // 16-byte loads in flight per thread (latency-bound phase)
-    for (int base = tid; base < total; base += 256 * kBatch) {
-      double2_t v[kBatch];
-      int dst[kBatch];
-#pragma unroll
-      for (int k = 0; k < kBatch; ++k) {
-        const int idx = base + k * 256;
-        const bool ok = idx < total;
-        const int row = ok ? idx / c2n : 0, c2 = ok ? idx - row * c2n : 0;
-        const int grow = (row < kJB) ? (ba * kJB + row) : (bb * kJB + (row - kJB));
-        dst[k] = ok ? row * ldp + 2 * c2 : -1;
-        v[k] = *reinterpret_cast<const double2_t*>(XT + (int64_t)grow * ld + 2 * c2);
-      }
-#pragma unroll
-      for (int k = 0; k < kBatch; ++k)
-        if (dst[k] >= 0) *reinterpret_cast<double2_t*>(Xs + dst[k]) = v[k];
-    }
-  }
+  dma_load_slab(Xs, ldp, cols, ld, wave, 4, lane);
+  __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-  // every thread has taken its convergence decision by now: safe to clear the slot of the NEXT sweep
-  // (in self mode the tick3 launch of the same tick does it)
-  if (!self_mode && step == steps - 1 && br.local == 0 && tid == 0) d.off[(sweep + 1) & 1] = 0.0;
+  // (in self mode the tick3 launch of the same tick clears the next sweep's slot)
+  if (!self_mode) pos.clear_next(d, leader);
 
-  const int per = ld >> 2;                         // ld is a multiple of 32 -> per % 8 == 0
-  pair_gram_partial(Xs, ldp, r, wave * per, (wave + 1) * per, q, S.red + wave * 256, lane);
+  // ---- 1. H = Xp^T Xp, a quarter of the rows per wave ----
+  const int per = ld >> 2;                         // ld is a multiple of 128 -> per % 8 == 0
+  GramAcc h;
+  h.add(Xs + r * ldp, wave * per, (wave + 1) * per, q);
+  h.store_partial(S.red + wave * 256, lane);
   __syncthreads();
   pair_gram_reduce(S, tid);
   __syncthreads();
+  // ---- 2. the 16x16 rotation ----
   if (wave == 0) {
     double* hcur = (self_mode && d.sblk) ? d.sblk + (int64_t)br.local * (kPair * kPair) : nullptr;
-    const double mx = pair_inner_solve_fast(S, lane, d.off[2], tol, step == 0, hcur);
+    const double mx = pair_inner_solve_fast(S, lane, d.off[2], tol, pos.step == 0, hcur);
     if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned long long*>(&d.off[sweep & 1]), (unsigned long long)__double_as_longlong(mx));
+      atomicMax(reinterpret_cast<unsigned long long*>(&d.off[pos.sweep & 1]), (unsigned long long)__double_as_longlong(mx));
   }
   __syncthreads();
   if (!*S.rotated) return;
 
-  // ---- 3. Xp <- Xp * Q, i.e. rows of XT:  Y[a][:] = sum_b Q[b][a] * X[b][:]  ----
-  {
-    double qa[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) qa[t] = S.Q[4 * t + q][r];     // A operand: A[m=a][k=b] = Q[b][a]
-    int64_t orow[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int a = q + 4 * e;                                  // D row = (l>>4) + 4*reg
-      orow[e] = (int64_t)((a < kJB) ? (ba * kJB + a) : (bb * kJB + (a - kJB))) * ld;
-    }
-    const int ntile = ld >> 4;
-    for (int it = wave; it < ntile; it += 4) {
-      const int col = it * 16 + r;
-      double4_t acc = {0, 0, 0, 0};
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[t], Xs[(4 * t + q) * ldp + col], acc, 0, 0, 0);   // B[k=b][n=i]
-#pragma unroll
-      for (int e = 0; e < 4; ++e) XT[orow[e] + col] = acc[e];
-    }
-  }
+  // ---- 3. Xp <- Xp * Q ----
+  apply_q_tiles<false, QDst::Global>(Xs, ldp, ld, S.Q, 0, 1, wave, 4, lane, cols);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -435,27 +485,11 @@ __global__ __launch_bounds__(256) void jacobi_tick_kernel(const EigDesc* __restr
 // and block map as jacobi_tick_kernel (self_mode = 0); the columns pass through the LDS in chunks of
 // kStreamChunk rows twice -- once for H = Xp^T Xp (the four waves keep their partial tiles in
 // registers across chunks), once for Xp <- Xp Q (second read mostly from L2 / Infinity Cache).
+// A chunk is 128 KiB per workgroup, every piece of a wave in flight at once: the pass is bound by what one CU pulls
+// from L2 / Infinity Cache, not by a handful of register loads per thread.
 // Dynamic LDS (doubles): X[16][kStreamChunk + 2] | PairScratch
 // ------------------------------------------------------------------------------------------------
 constexpr int kStreamChunk = 1024;
-
-// LDS-DMA, 1 KiB pieces, every piece of a wave in flight at once (128 KiB per workgroup): the pass is bound by
-// what one CU pulls from L2 / Infinity Cache, not by a handful of register loads per thread
-__device__ __forceinline__ void stream_load_chunk(double* __restrict__ Xs, const double* __restrict__ XT, int ld,
-                                                  int ba, int bb, int c0, int len, int wave, int lane) {
-  constexpr int ldp = kStreamChunk + 2;
-  const int cpr = len >> 7;                        // 1 KiB pieces per row of the chunk (len % 128 == 0)
-  const int npiece = kPair * cpr;
-  for (int c = wave; c < npiece; c += 4) {
-    const int row = c / cpr, ch = c - row * cpr;
-    const int grow = (row < kJB) ? (ba * kJB + row) : (bb * kJB + (row - kJB));
-    const double* src = XT + (int64_t)grow * ld + c0 + ch * 128 + lane * 2;
-    double* dst = Xs + row * ldp + ch * 128;       // wave-uniform
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-  }
-  __builtin_amdgcn_s_waitcnt(0);
-}
 
 __global__ __launch_bounds__(256) void jacobi_tick_stream_kernel(const EigDesc* __restrict__ descs,
                                                                  const BlockRef* __restrict__ map, int tick,
@@ -463,215 +497,57 @@ __global__ __launch_bounds__(256) void jacobi_tick_stream_kernel(const EigDesc* 
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const BlockRef br = map[blockIdx.x];
   const EigDesc d = descs[br.prob];
-  if (*d.done) return;
-  const int nb = d.nb;
-  const int steps = nb - 1;
-  const int sweep = tick / steps;
-  const int step = tick - sweep * steps;
+  const TickPos pos(tick, d.nb, 0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (step == 0 && sweep > 0) {
-    if (d.off[(sweep - 1) & 1] < tol) {
-      if (br.local == 0 && tid == 0) *d.done = 1;
-      return;
-    }
-  }
+  const bool leader = br.local == 0 && tid == 0;
+  if (pos.retired(d, tol, leader)) return;
   constexpr int ldp = kStreamChunk + 2;
   const int ld = d.ld;
   double* Xs = smem;
   const PairScratch S = carve_scratch(Xs + kPair * ldp);
   int ba, bb;
-  rr_pair(nb, step, br.local, ba, bb);
+  rr_pair(d.nb, pos.step, br.local, ba, bb);
   const int r = lane & 15, q = lane >> 4;
-  double* __restrict__ XT = d.XT;
+  SlabCols cols{d.XT, ld, ba, bb, kJB, 0};
 
   // ---- 1. H = Xp^T Xp over all chunks ----
-  double4_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+  GramAcc h;
   for (int c0 = 0; c0 < ld; c0 += kStreamChunk) {
-    const int len = min(kStreamChunk, ld - c0);    // multiple of 128 (eig_ld)
+    const int len = min(kStreamChunk, ld - c0);    // multiple of 128
     if (c0) __syncthreads();                       // the previous chunk has been consumed
-    stream_load_chunk(Xs, XT, ld, ba, bb, c0, len, wave, lane);
+    cols.c0 = c0;
+    dma_load_slab(Xs, ldp, cols, len, wave, 4, lane);
+    __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     const int per = len >> 2;                      // rows of the chunk per wave (multiple of 8)
-    const double* row = Xs + r * ldp;
-    for (int i = wave * per; i < (wave + 1) * per; i += 8) {
-      const double2_t v = *reinterpret_cast<const double2_t*>(row + i + 2 * q);
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, v.x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, v.y, acc1, 0, 0, 0);
-    }
+    h.add(Xs + r * ldp, wave * per, (wave + 1) * per, q);
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) S.red[wave * 256 + lane * 4 + e] = acc0[e] + acc1[e];
-  if (step == steps - 1 && br.local == 0 && tid == 0) d.off[(sweep + 1) & 1] = 0.0;
+  h.store_partial(S.red + wave * 256, lane);
+  pos.clear_next(d, leader);
   __syncthreads();
   pair_gram_reduce(S, tid);
   __syncthreads();
   if (wave == 0) {
-    const double mx = pair_inner_solve_fast(S, lane, d.off[2], tol, step == 0, nullptr);
+    const double mx = pair_inner_solve_fast(S, lane, d.off[2], tol, pos.step == 0, nullptr);
     if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned long long*>(&d.off[sweep & 1]), (unsigned long long)__double_as_longlong(mx));
+      atomicMax(reinterpret_cast<unsigned long long*>(&d.off[pos.sweep & 1]), (unsigned long long)__double_as_longlong(mx));
   }
   __syncthreads();
   if (!*S.rotated) return;
 
   // ---- 2. Xp <- Xp * Q chunk by chunk ----
-  double qa[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) qa[t] = S.Q[4 * t + q][r];
-  int64_t orow[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int a = q + 4 * e;
-    orow[e] = (int64_t)((a < kJB) ? (ba * kJB + a) : (bb * kJB + (a - kJB))) * ld;
-  }
   const int last0 = ((ld - 1) / kStreamChunk) * kStreamChunk;     // the chunk still in the LDS
   for (int c0 = last0; c0 >= 0; c0 -= kStreamChunk) {             // backwards: the resident chunk first
     const int len = min(kStreamChunk, ld - c0);
+    cols.c0 = c0;
     if (c0 != last0) {
       __syncthreads();
-      stream_load_chunk(Xs, XT, ld, ba, bb, c0, len, wave, lane);
+      dma_load_slab(Xs, ldp, cols, len, wave, 4, lane);
+      __builtin_amdgcn_s_waitcnt(0);
       __syncthreads();
     }
-    const int ntile = len >> 4;
-    for (int it = wave; it < ntile; it += 4) {
-      const int col = it * 16 + r;
-      double4_t acc = {0, 0, 0, 0};
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[t], Xs[(4 * t + q) * ldp + col], acc, 0, 0, 0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) XT[orow[e] + c0 + col] = acc[e];
-    }
+    apply_q_tiles<false, QDst::Global>(Xs, ldp, len, S.Q, 0, 1, wave, 4, lane, cols);
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// tick2: one workgroup (512 threads) = one super-pair of 2 x 16 columns, LDS resident.
-// Dynamic LDS (doubles): X[32][ldp] | PairScratch[2]
-// Sub-blocks of 8 rows in the slab: 0,1 = super-block A ; 2,3 = super-block B.
-// ------------------------------------------------------------------------------------------------
-constexpr int kSuper = 2 * kPair;   // 32 rows in the slab
-
-#ifdef TADMM_STAMPS
-#define STAMP(i) do { if (blockIdx.x == gridDim.x / 2 && tid == 0) g_stamps[i] += clock64() - t0; } while (0)
-#else
-#define STAMP(i) do {} while (0)
-#endif
-
-__global__ __launch_bounds__(512) void jacobi_tick2_kernel(const EigDesc* __restrict__ descs,
-                                                           const BlockRef* __restrict__ map, int tick, double tol,
-                                                           int inner_sweeps) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const BlockRef br = map[blockIdx.x];
-  const EigDesc d = descs[br.prob];
-  if (*d.done) return;
-  const int nbs = d.nb >> 1;                       // super-blocks of 16 columns
-  const int steps = nbs - 1;
-  const int sweep = tick / steps;
-  const int step = tick - sweep * steps;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = wave >> 2, wv = wave & 3, th = tid & 255;
-  if (step == 0 && sweep > 0) {
-    if (d.off[(sweep - 1) & 1] < tol) {
-      if (br.local == 0 && tid == 0) *d.done = 1;
-      return;
-    }
-  }
-  const int ld = d.ld, ldp = ld + 2;
-#ifdef TADMM_STAMPS
-  const unsigned long long t0 = clock64();
-  if (blockIdx.x == gridDim.x / 2 && tid == 0) g_stamps[31] += 1;
-#endif
-  double* Xs = smem;
-  const PairScratch S = carve_scratch(Xs + kSuper * ldp + half * kPairScratchDoubles);
-
-  int sa, sb;
-  rr_pair(nbs, step, br.local, sa, sb);
-  const int r = lane & 15, q = lane >> 4;
-  double* __restrict__ XT = d.XT;
-
-  // ---- load the 32 columns once ----
-  {
-    const int c2n = ld >> 1;
-    const int total = kSuper * c2n;
-#pragma unroll 4
-    for (int idx = tid; idx < total; idx += 512) {
-      const int row = idx / c2n, c2 = idx - row * c2n;
-      const int grow = (row < kPair) ? (sa * kPair + row) : (sb * kPair + (row - kPair));
-      const double2_t v = *reinterpret_cast<const double2_t*>(XT + (int64_t)grow * ld + 2 * c2);
-      *reinterpret_cast<double2_t*>(Xs + row * ldp + 2 * c2) = v;
-    }
-  }
-  __syncthreads();
-  STAMP(0);
-  if (step == steps - 1 && br.local == 0 && tid == 0) d.off[(sweep + 1) & 1] = 0.0;
-
-  const double hmax = d.off[2];
-  const int per = ld >> 2;
-  double mxall = 0.0;
-  int any_rot = 0;
-  // rounds: (first tick of a sweep only) inside the super-blocks: (0,1) | (2,3) incl. the pairs inside
-  //         each block of 8;   round 1: (0,2) | (1,3);   round 2: (0,3) | (1,2)
-  const int first_round = (step == 0) ? 0 : 1;
-  for (int round = first_round; round < 3; ++round) {
-    int u, v;
-    if (round == 0) { u = half ? 2 : 0; v = half ? 3 : 1; }
-    else if (round == 1) { u = half ? 1 : 0; v = half ? 3 : 2; }
-    else { u = half ? 1 : 0; v = half ? 2 : 3; }
-    const int lrow_r = (r < kJB) ? (u * kJB + r) : (v * kJB + (r - kJB));
-    pair_gram_partial(Xs, ldp, lrow_r, wv * per, (wv + 1) * per, q, S.red + wv * 256, lane);
-    __syncthreads();
-    STAMP(1 + 4 * round);
-    pair_gram_reduce(S, th);
-    __syncthreads();
-    STAMP(2 + 4 * round);
-    if (wv == 0) {
-      const double mx = pair_inner_solve_fast(S, lane, hmax, tol, round == 0);
-      mxall = fmax(mxall, mx);
-    }
-    __syncthreads();
-    STAMP(3 + 4 * round);
-    if (*S.rotated) {
-      any_rot = 1;
-      double qa[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) qa[t] = S.Q[4 * t + q][r];
-      int rowk[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {       // k = 4t+q (B operand row) and D row q+4e share this map
-        const int b = 4 * t + q;
-        rowk[t] = ((b < kJB) ? (u * kJB + b) : (v * kJB + (b - kJB))) * ldp;
-      }
-      const int ntile = ld >> 4;
-      for (int it = wv; it < ntile; it += 4) {
-        const int col = it * 16 + r;
-        double4_t acc = {0, 0, 0, 0};
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[t], Xs[rowk[t] + col], acc, 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Xs[rowk[e] + col] = acc[e];   // in place: this tile is touched by this wave only
-      }
-    }
-    __syncthreads();
-    STAMP(4 + 4 * round);
-  }
-  if (wv == 0 && lane == 0)
-    atomicMax(reinterpret_cast<unsigned long long*>(&d.off[sweep & 1]), (unsigned long long)__double_as_longlong(mxall));
-  // ---- store back (skipped when nothing rotated in this workgroup) ----
-  any_rot = __syncthreads_or(any_rot);
-  if (!any_rot) return;
-  {
-    const int c2n = ld >> 1;
-    const int total = kSuper * c2n;
-#pragma unroll 4
-    for (int idx = tid; idx < total; idx += 512) {
-      const int row = idx / c2n, c2 = idx - row * c2n;
-      const int grow = (row < kPair) ? (sa * kPair + row) : (sb * kPair + (row - kPair));
-      *reinterpret_cast<double2_t*>(XT + (int64_t)grow * ld + 2 * c2) =
-          *reinterpret_cast<const double2_t*>(Xs + row * ldp + 2 * c2);
-    }
-  }
-  STAMP(20);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -690,58 +566,6 @@ __global__ __launch_bounds__(512) void jacobi_tick2_kernel(const EigDesc* __rest
 //                        per half: H[16][18] Q1[16][18] Q2[16][18] | flags
 // ------------------------------------------------------------------------------------------------
 constexpr int kH32 = kSuper + 2;    // leading dimension of the 32x32 LDS image
-
-__device__ __forceinline__ int sub_index(int u, int v, int k) { return (k < kJB) ? (u * kJB + k) : (v * kJB + (k - kJB)); }
-
-// (Q is passed TRANSPOSED, as the inner solve leaves it.)
-// X[:, sub-pair (u,v)] <- X[:, (u,v)] * Q  for the tiles it = wi, wi+nw, ...   (rows of the transposed slab)
-__device__ __forceinline__ void apply_q_tiles(double* __restrict__ Xs, int ldp, int ld, const double (*Q)[kHP], int u,
-                                              int v, int wi, int nw, int lane) {
-  const int r = lane & 15, q = lane >> 4;
-  double qa[4];
-  int rowk[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    qa[t] = Q[r][4 * t + q];                                  // A operand: A[m=a][k=b] = Q[b][a] = Qt[a][b]
-    rowk[t] = sub_index(u, v, 4 * t + q) * ldp;               // k = 4t+q (B operand row) and D row q+4e share this map
-  }
-  const int ntile = ld >> 4;
-  for (int it = wi; it < ntile; it += nw) {
-    const int col = it * 16 + r;
-    double4_t acc = {0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[t], Xs[rowk[t] + col], acc, 0, 0, 0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) Xs[rowk[e] + col] = acc[e];   // in place: a tile is touched by one wave only
-  }
-}
-
-// Same product, result written to the global column image (XT[j][:] = column j) instead of LDS: 16 lanes write
-// 128 contiguous bytes of one column.
-__device__ __forceinline__ void apply_q_tiles_store(const double* __restrict__ Xs, int ldp, int ld, const double (*Q)[kHP],
-                                                    int u, int v, int wi, int nw, int lane, double* __restrict__ XT, int sa,
-                                                    int sb) {
-  const int r = lane & 15, q = lane >> 4;
-  double qa[4];
-  int rowk[4];
-  int64_t growk[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    qa[t] = Q[r][4 * t + q];
-    const int row = sub_index(u, v, 4 * t + q);
-    rowk[t] = row * ldp;
-    growk[t] = (int64_t)((row < kPair) ? (sa * kPair + row) : (sb * kPair + (row - kPair))) * ld;
-  }
-  const int ntile = ld >> 4;
-  for (int it = wi; it < ntile; it += nw) {
-    const int col = it * 16 + r;
-    double4_t acc = {0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[t], Xs[rowk[t] + col], acc, 0, 0, 0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) __hip_atomic_store(XT + growk[e] + col, acc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
 
 // Convergence measure of the 16x16 subproblem (u,v) read from the 32x32 image (same formula as the preamble of
 // `pair_inner_solve_fast`); executed by a wave that is not solving, off the critical path.
@@ -805,14 +629,11 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const BlockRef br = map[blockIdx.x];
   const EigDesc d = descs[br.prob];
-  const int nbs = d.nb >> 1;
-  const int steps = nbs - 1;
-  const int period = d.period > 0 ? d.period : steps;
-  const int sweep = tick / period;
-  const int step = tick - sweep * period;
-  if (step >= steps) return;                     // idle tick of the group's schedule (this problem has fewer players)
+  const TickPos pos(tick, d.nb >> 1, d.period);
+  if (pos.step >= pos.steps) return;             // idle tick of the group's schedule (this problem has fewer players)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = wave >> 2, wv = wave & 3, th = tid & 255;
+  const bool leader = br.local == 0 && tid == 0;
   const int ld = d.ld, ldp = ld + 2;
 #ifdef TADMM_STAMPS
   const unsigned long long t0 = clock64();
@@ -830,69 +651,23 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
   int* flags = reinterpret_cast<int*>(R + 2048 + 2 * (3 * kPair * kHP));   // [0..1] rotated round 1, [2..3] round 2
 
   int sa, sb;
-  rr_pair(nbs, step, br.local, sa, sb);
+  rr_pair(d.nb >> 1, pos.step, br.local, sa, sb);
   const int r = lane & 15, q = lane >> 4;
-  double* __restrict__ XT = d.XT;
+  const SlabCols cols{d.XT, ld, sa, sb, kPair, 0};
 
-  // ---- load the 32 columns ----
-  const bool dma = (ld & 127) == 0;
-  if (dma) {
-    // LDS-DMA (global_load_lds_dwordx4): a wave moves 1 KiB chunks of a column straight into LDS -- 64 lanes x
-    // 16 bytes land at consecutive LDS addresses behind a wave-uniform base, no staging registers, so all 16
-    // chunks of a wave are in flight at once (the phase is latency-, not bandwidth-bound).  Rows are whole
-    // 1 KiB chunks (ld % 128 == 0) and an LDS row starts 16 bytes after the previous one ends (ldp = ld + 2).
-    // Issued before the convergence flags are even read: their load latency hides behind the columns'.
-    const int cpr = ld >> 7;                          // chunks per column
-    const int nchunk = kSuper * cpr;
-    for (int c = wave; c < nchunk; c += 8) {
-      const int row = c / cpr, ch = c - row * cpr;
-      const int grow = (row < kPair) ? (sa * kPair + row) : (sb * kPair + (row - kPair));
-      const double* src = XT + (int64_t)grow * ld + ch * 128 + lane * 2;
-      double* dst = Xs + row * ldp + ch * 128;        // wave-uniform
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    }
-  }
-  {
-    bool quit = *d.done != 0;
-    if (!quit && step == 0 && sweep > 0 && d.off[(sweep - 1) & 1] < tol) {
-      if (br.local == 0 && tid == 0) *d.done = 1;
-      quit = true;
-    }
-    if (quit) {                                       // uniform over the workgroup
-      if (dma) __builtin_amdgcn_s_waitcnt(0);         // no DMA may still target this workgroup's LDS at exit
-      return;
-    }
+  // ---- load the 32 columns: issued before the convergence flags are even read, their load latency hides behind the
+  // columns' ----
+  dma_load_slab(Xs, ldp, cols, ld, wave, 8, lane);
+  if (pos.retired(d, tol, leader)) {
+    __builtin_amdgcn_s_waitcnt(0);                    // no DMA may still target this workgroup's LDS at exit
+    return;
   }
   // the two carried self-Grams go to registers
   const double sreg = d.sblk[(int64_t)(tid < 256 ? sa : sb) * (kPair * kPair) + th];
-  if (dma) {
-    __builtin_amdgcn_s_waitcnt(0);
-  } else {
-    constexpr int kLoadBatch = 8;
-    // register-staged path: keep kLoadBatch x 16 bytes per thread in flight
-    const int c2n = ld >> 1;
-    const int total = kSuper * c2n;
-    for (int base = tid; base < total; base += 512 * kLoadBatch) {
-      double2_t v[kLoadBatch];
-      int dst[kLoadBatch];
-#pragma unroll
-      for (int k = 0; k < kLoadBatch; ++k) {
-        const int idx = base + k * 512;
-        const bool ok = idx < total;
-        const int row = ok ? idx / c2n : 0, c2 = ok ? idx - row * c2n : 0;
-        const int grow = (row < kPair) ? (sa * kPair + row) : (sb * kPair + (row - kPair));
-        dst[k] = ok ? row * ldp + 2 * c2 : -1;
-        v[k] = *reinterpret_cast<const double2_t*>(XT + (int64_t)grow * ld + 2 * c2);
-      }
-#pragma unroll
-      for (int k = 0; k < kLoadBatch; ++k)
-        if (dst[k] >= 0) *reinterpret_cast<double2_t*>(Xs + dst[k]) = v[k];
-    }
-  }
+  __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-  STAMP(0);
-  if (step == steps - 1 && br.local == 0 && tid == 0) d.off[(sweep + 1) & 1] = 0.0;
+  STAMP(0, t0);
+  pos.clear_next(d, leader);
 
   // ---- cross Gram C = X_A^T X_B : every wave reduces ld/8 rows ----
   {
@@ -926,7 +701,7 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
     H32[kPair + (th >> 4)][kPair + (th & 15)] = sreg;               // S_B
   }
   __syncthreads();
-  STAMP(1);
+  STAMP(1, t0);
 
   const double hmax = d.off[2];
   double mxall = 0.0;
@@ -946,7 +721,7 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
     }
     __syncthreads();
   }
-  STAMP(2);
+  STAMP(2, t0);
   // ---- H32 <- Q1^T H32 Q1 ; extract round 2: (0,3) | (1,2) ----
   {
     double (*Qa)[kHP] = half ? Q1o : Q1;       // rotation of sub-pair (0,2)
@@ -957,7 +732,7 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
     Q2[th >> 4][th & 15] = ((th >> 4) == (th & 15)) ? 1.0 : 0.0;
     __syncthreads();
   }
-  STAMP(3);
+  STAMP(3, t0);
   // ---- round-2 solves on waves 0 and 4, round-1 column update on the other six waves ----
   if (wv == half) {
     PairScratch S;
@@ -969,13 +744,13 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
     if (wv == mwave) mxall = fmax(mxall, pair_measure_h32(H32, half ? 1 : 0, half ? 2 : 3, lane, hmax, tol));
     const int u = half ? 1 : 0, v = half ? 3 : 2;                   // this half's round-1 sub-pair
     const int wi = (wv > half) ? wv - 1 : wv;                       // 0..2 among the three non-solver waves
-    if (flags[half]) apply_q_tiles(Xs, ldp, ld, Q1, u, v, wi, 3, lane);
+    if (flags[half]) apply_q_tiles<true, QDst::Slab>(Xs, ldp, ld, Q1, u, v, wi, 3, lane);
   }
   __syncthreads();
-  STAMP(4);
+  STAMP(4, t0);
   // ---- final self-Grams, then the round-2 column update straight from the MFMA accumulators to HBM ----
   if (wv == mwave && lane == 0)
-    atomicMax(reinterpret_cast<unsigned long long*>(&d.off[sweep & 1]), (unsigned long long)__double_as_longlong(mxall));
+    atomicMax(reinterpret_cast<unsigned long long*>(&d.off[pos.sweep & 1]), (unsigned long long)__double_as_longlong(mxall));
   const int any_rot = flags[0] | flags[1] | flags[2] | flags[3];
   if (!any_rot) return;
   {
@@ -983,16 +758,16 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
     double (*Qb)[kHP] = half ? Q2 : Q2o;       // (1,2)
     transform_h32<0, 3, 1, 2>(H32, Qa, Qb, tid);
   }
-  STAMP(5);
+  STAMP(5, t0);
   d.sblk[(int64_t)(tid < 256 ? sa : sb) * (kPair * kPair) + th] =
       (tid < 256) ? H32[th >> 4][th & 15] : H32[kPair + (th >> 4)][kPair + (th & 15)];
   {
     // the two halves' round-2 sub-pairs (0,3) and (1,2) cover all 32 columns; a sub-pair that was not rotated
     // in round 2 has Q2 = I and the product is an exact copy of what round 1 left in LDS
     const int u = half ? 1 : 0, v = half ? 2 : 3;
-    apply_q_tiles_store(Xs, ldp, ld, Q2, u, v, wv, 4, lane, XT, sa, sb);
+    apply_q_tiles<true, QDst::GlobalAgent>(Xs, ldp, ld, Q2, u, v, wv, 4, lane, cols);
   }
-  STAMP(20);
+  STAMP(20, t0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1087,16 +862,11 @@ __global__ __launch_bounds__(256) void jacobi_small_kernel(const EigDesc* __rest
       if (wave < pairs) {
         int a, b;
         rr_pair(nb, step, wave, a, b);
-        const double* row = Xs + sub_index(a, b, r) * ldp;
-        double4_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
-        for (int i = 0; i < Npad; i += 8) {
-          const double2_t v = *reinterpret_cast<const double2_t*>(row + i + 2 * q);
-          acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, v.x, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, v.y, acc1, 0, 0, 0);
-        }
+        GramAcc h;
+        h.add(Xs + sub_index(a, b, r) * ldp, 0, Npad, q);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          Hs[q + 4 * e][r] = acc0[e] + acc1[e];
+          Hs[q + 4 * e][r] = h.sum(e);
           Qs[q + 4 * e][r] = (q + 4 * e == r) ? 1.0 : 0.0;
         }
         wave_lds_fence();
@@ -1104,7 +874,7 @@ __global__ __launch_bounds__(256) void jacobi_small_kernel(const EigDesc* __rest
         S.H = Hs; S.Q = Qs; S.rotated = flags + wave;
         mx_sweep = fmax(mx_sweep, pair_inner_solve_fast<true, true>(S, lane, hmax, tol, step == 0));
         wave_lds_fence();
-        if (flags[wave]) apply_q_tiles(Xs, ldp, Npad, Qs, a, b, 0, 1, lane);
+        if (flags[wave]) apply_q_tiles<true, QDst::Slab>(Xs, ldp, Npad, Qs, a, b, 0, 1, lane);
       }
       __syncthreads();
     }
@@ -1165,7 +935,7 @@ hipError_t launch_jacobi_small(const EigDesc* descs_dev, int nprob, int npad_max
   // X image | 4 wave scratches | red[8] + flags (8 doubles) | second image (warm start only)
   const size_t lds = ((size_t)npad_max * (npad_max + 2) * (warm ? 2 : 1) + 4 * kSmallWaveScratch + 16) * 8;
   if (lds > 64 * 1024) {                     // two images of a 64-column problem: above the default dynamic-LDS cap
-    // the kernel carries 16 bytes of static LDS (warm_bad): as for tick2, the full 160 KiB as dynamic LDS is refused
+    // the kernel carries 16 bytes of static LDS (warm_bad): the full 160 KiB as dynamic LDS is refused (invalid argument)
     static DynLdsOptIn allow_lds;
     const hipError_t e = allow_lds(jacobi_small_kernel, 160 * 1024 - 256);
     if (e != hipSuccess) return e;
@@ -1180,13 +950,11 @@ void dump_stamps() {
   unsigned long long h[32];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps), sizeof h) != hipSuccess) return;
   const double n = h[31] ? (double)h[31] : 1.0;
-  fprintf(stderr, "[stampsS] per launch (2 solves): preamble=%.0f loop=%.0f epilogue=%.0f\n", h[10] / n, h[11] / n, h[12] / n);
+  // slots 10..12: cumulative inside pair_inner_solve_fast (after the measure, the cross pairs, the end); 0..5, 20: tick3
+  fprintf(stderr, "[stampsS] per launch (2 solves): preamble=%.0f loop=%.0f epilogue=%.0f\n", h[10] / n, (h[11] - h[10]) / n,
+          (h[12] - h[11]) / n);
   fprintf(stderr, "[stamps3] launches=%llu cumulative: load=%.0f gram=%.0f solve1=%.0f xform=%.0f solve2||apply1=%.0f apply2+xform=%.0f end=%.0f\n",
           h[31], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[5] / n, h[20] / n);
-  fprintf(stderr, "[stamps] launches=%llu  cumulative cycles/launch: load=%.0f", h[31], h[0] / n);
-  for (int r = 0; r < 3; ++r)
-    fprintf(stderr, " | r%d gram=%.0f red=%.0f inner=%.0f upd=%.0f", r, h[1 + 4 * r] / n, h[2 + 4 * r] / n, h[3 + 4 * r] / n, h[4 + 4 * r] / n);
-  fprintf(stderr, " | end=%.0f\n", h[20] / n);
 }
 #else
 void dump_stamps() {}
@@ -1355,45 +1123,36 @@ hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev
             jacobi_tick3_lds_bytes(ld_max));
   return hipSuccess;
 }
-size_t jacobi_tick2_lds_bytes(int ld_max) { return ((size_t)kSuper * (ld_max + 2) + 2 * kPairScratchDoubles) * 8; }
-bool jacobi_tick2_fits(int ld_max) { return jacobi_tick2_lds_bytes(ld_max) <= 160 * 1024 - 256; }
 
 static DynLdsOptIn allow_tick_lds;      // jacobi_tick_kernel has two launchers: the self pass and the plain pair tick
 
 hipError_t launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                              int inner_sweeps, int ld_max, hipStream_t s) {
+                              int ld_max, hipStream_t s) {
   if (nblocks <= 0) return hipSuccess;
   const hipError_t e = allow_tick_lds(jacobi_tick_kernel, 160 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), jacobi_tick_lds_bytes(ld_max), s, descs_dev, map_dev,
-                     tick, tol, inner_sweeps, 1);
+                     tick, tol, 1);
   return hipSuccess;
 }
 
 hipError_t launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                              int inner_sweeps, size_t lds_bytes, bool super, hipStream_t s) {
+                              size_t lds_bytes, hipStream_t s) {
   if (nblocks <= 0) return hipSuccess;
   hipError_t e;
-  if (super) {
-    // tick2 carries 256 bytes of static LDS: asking for the full 160 KiB as dynamic LDS is refused (invalid argument)
-    static DynLdsOptIn allow_lds;
-    if ((e = allow_lds(jacobi_tick2_kernel, 160 * 1024 - 256)) != hipSuccess) return e;
-    hipLaunchKernelGGL(jacobi_tick2_kernel, dim3(nblocks), dim3(512), lds_bytes, s, descs_dev, map_dev, tick, tol,
-                       inner_sweeps);
-  } else if (lds_bytes > 160 * 1024) {  // rows too long for an LDS-resident pair: streamed pair kernel
+  if (lds_bytes > 160 * 1024) {  // rows too long for an LDS-resident pair: streamed pair kernel
     static DynLdsOptIn allow_lds;
     if ((e = allow_lds(jacobi_tick_stream_kernel, 160 * 1024)) != hipSuccess) return e;
     hipLaunchKernelGGL(jacobi_tick_stream_kernel, dim3(nblocks), dim3(256), jacobi_tick_stream_lds_bytes(), s, descs_dev,
                        map_dev, tick, tol);
   } else {
     if ((e = allow_tick_lds(jacobi_tick_kernel, 160 * 1024)) != hipSuccess) return e;
-    hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), lds_bytes, s, descs_dev, map_dev, tick, tol,
-                       inner_sweeps, 0);
+    hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), lds_bytes, s, descs_dev, map_dev, tick, tol, 0);
   }
   e = hipPeekAtLastError();
   if (e != hipSuccess)
-    fprintf(stderr, "[tadmm] jacobi tick launch failed: %s (blocks=%d lds=%zu super=%d)\n", hipGetErrorString(e),
-            nblocks, lds_bytes, (int)super);
+    fprintf(stderr, "[tadmm] jacobi tick launch failed: %s (blocks=%d lds=%zu)\n", hipGetErrorString(e), nblocks,
+            lds_bytes);
   return hipSuccess;
 }
 void launch_eig_norms(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, hipStream_t s,

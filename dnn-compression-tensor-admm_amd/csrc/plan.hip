@@ -145,7 +145,6 @@ struct tadmm_plan_s {
   double last_ms[8] = {0};
   int last_sweeps = 0;
   double tol = 1e-9;
-  int inner_sweeps = 1;
   bool debug = false;
   int max_global_sweeps = 40;
   // filtered eigen-solver statistics of the last run
@@ -454,9 +453,9 @@ static int layout_plan(tadmm_plan_s* P, const float* const* W, float* const* U, 
         ed[p] = e;
       }
     }
-    build_eig_layout(sp.main, ed, true, da, img);
+    if (const int rc = build_eig_layout(h, sp.main, ed, true, da, img)) return rc;
     sp.fb.prev_off = ar.take((size_t)std::max<size_t>(1, ed_fb.size()) * 8);
-    build_eig_layout(sp.fb, ed_fb, true, da, img);
+    if (const int rc = build_eig_layout(h, sp.fb, ed_fb, true, da, img)) return rc;
     place_phase(sp.proj, da, img, pd.data(), pd.size() * sizeof(GemmDesc), neig, m_proj);
   }
 
@@ -932,7 +931,7 @@ static int single_run(tadmm_plan p, int update_u, int use_u, double* resid_sq_de
   // one eigen group of a level: the tournament (or the single-launch solver) and its finalize launches
   auto solve_group = [&](EigLayout& L, const EigGroup& eg, bool* small_pending) -> int {
     int gs = 0;
-    const int rc = run_eig_group(h, eg, p->poll, p->tol, p->inner_sweeps, p->max_global_sweeps, p->debug, s, &gs,
+    const int rc = run_eig_group(h, eg, p->poll, p->tol, p->max_global_sweeps, p->debug, s, &gs,
                                  small_pending, &p->jtm);
     if (rc != TADMM_OK) return rc;
     L.last_sweeps = gs;     // main: the next run's `expected`; fallback: informational (its expected stays 0)
@@ -1072,7 +1071,7 @@ int tadmm_plan_set_jacobi(tadmm_plan p, double tol, int inner_sweeps, int max_sw
   if (!p) return TADMM_ERR_INVALID;
   if (p->lanes) for (int i = 0; i < 2; ++i) tadmm_plan_set_jacobi(p->lanes->sub[i], tol, inner_sweeps, max_sweeps);
   if (tol > 0) p->tol = tol;
-  if (inner_sweeps > 0) p->inner_sweeps = inner_sweeps;
+  (void)inner_sweeps;    // ignored: the 16x16 rotation solve is one cyclic sweep (include/tadmm.h)
   if (max_sweeps > 0) p->max_global_sweeps = max_sweeps;
   return TADMM_OK;
 }

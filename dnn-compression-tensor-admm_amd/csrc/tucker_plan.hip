@@ -172,7 +172,7 @@ struct tadmm_tucker_plan_s {
   PollCtx poll;          // Jacobi verdicts
   PollCtx hooi;          // HOOI verdicts
   double jtol = 1e-9;
-  int inner = 1, max_sweeps = 40, n_iter_max = 100;
+  int max_sweeps = 40, n_iter_max = 100;
   bool debug = false;
   int last_hooi = 0, last_jacobi_sweeps = 0;
   // instrumented runs (tadmm_tucker_enable_timing): every launch of the eigen-solver timed on the launch stream
@@ -401,7 +401,7 @@ static int tucker_layout(tadmm_tucker_plan_s* P, char* base, const float* const*
                      [&](const BlockRef& a, const BlockRef& b) { return gp_cost[a.prob] > gp_cost[b.prob]; });
     place_phase(v.gram_p, da, img, gd.data(), gd.size() * sizeof(GramDesc), n, m_gp);
     place_map_like(v.gram_r, v.gram_p, da, img, m_gr);
-    build_eig_layout(v.eig, ed, false, da, img);     // (all four phases keep per-problem sweep periods)
+    if (const int rc = build_eig_layout(h, v.eig, ed, false, da, img)) return rc;     // (all four phases keep per-problem sweep periods)
     v.eig.prev_off = P->prev_off;
     place_phase(v.xg, da, img, xg.data(), xg.size() * sizeof(GemmDesc), n, m_xg);
   }
@@ -547,7 +547,7 @@ int tadmm_tucker_run(tadmm_tucker_plan p, int update_u, int use_u, double* resid
     int gs = 0;
     bool small_pending = false;
     p->jtm.small_n = v.players_n.empty() ? nullptr : v.players_n.data();
-    const int rc = run_eig_group(h, eg, p->poll, p->jtol, p->inner, p->max_sweeps, p->debug, s, &gs, &small_pending, &p->jtm);
+    const int rc = run_eig_group(h, eg, p->poll, p->jtol, p->max_sweeps, p->debug, s, &gs, &small_pending, &p->jtm);
     if (rc != TADMM_OK) return rc;
     jac_sweeps += gs;
     v.eig.sort(ws, s, sk);

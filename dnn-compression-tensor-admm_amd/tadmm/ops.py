@@ -173,6 +173,7 @@ class ProjectionPlan(_LayerPlan):
         self._create(Cp)
 
     def set_jacobi(self, tol=0.0, inner_sweeps=0, max_sweeps=0):
+        """Jacobi tunables (<= 0 keeps a value).  `inner_sweeps` is ignored: a 16x16 sub-problem gets one cyclic sweep."""
         self.h.check(self.h.lib.tadmm_plan_set_jacobi(self._plan, float(tol), int(inner_sweeps), int(max_sweeps)))
 
     def last_timing(self):

@@ -112,9 +112,9 @@ int tadmm_plan_singular_values(tadmm_plan p, int layer, int step, double* out_ho
 int tadmm_plan_last_timing(tadmm_plan p, double out_ms[8]);
 int tadmm_plan_enable_timing(tadmm_plan p, int on);
 /* Jacobi tunables: tol = largest relative off-diagonal a sweep may observe and still be the last one
- * (quadratic convergence leaves ~tol^2 afterwards; default 1e-9), inner_sweeps = reserved (the 16x16
- * sub-problems always get one cyclic sweep per visit), max_sweeps = cap before TADMM_ERR_NOCONVERGE.
- * <=0 keeps a value. */
+ * (quadratic convergence leaves ~tol^2 afterwards; default 1e-9), inner_sweeps = ignored (the 16x16
+ * sub-problems always get one cyclic sweep per visit; the argument stays for ABI compatibility), max_sweeps = cap
+ * before TADMM_ERR_NOCONVERGE.  <=0 keeps a value. */
 int tadmm_plan_set_jacobi(tadmm_plan p, double tol, int inner_sweeps, int max_sweeps);
 /* Filtered eigen-solver statistics (csrc/filter.hip): out[0] = eigen-problems of the plan served by the Chebyshev-
  * filtered subspace path (those whose kept rank is a fraction of their size), and for the LAST run out[1] = filtered

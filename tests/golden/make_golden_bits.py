@@ -6,6 +6,11 @@ for equal hashes.
     python tests/golden/make_golden_bits.py <commit id>        (on the MI355X, from the repository root, after build())
 
 `cases()` is shared with the test: it yields (name, inputs sha256, output array) and is the only definition of the cases.
+
+A second list, `eigh_cases()`, covers the Jacobi eigen-solver the same way (g13_eigh_bits.json, tests/test_gpu_eigh_bits.py):
+every launch shape of csrc/jacobi.hip through `ops.eigh`, `ops.eigh_partial` and two `ProjectionPlan`s.
+
+    python tests/golden/make_golden_bits.py <commit id> [output file] eigh
 """
 import hashlib
 import json
@@ -16,6 +21,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE = os.path.join(HERE, "g12_gemm_gram_bits.json")
+EIGH_FIXTURE = os.path.join(HERE, "g13_eigh_bits.json")
 
 MM_SHAPES = [(1, 5, 3), (64, 64, 16), (64, 64, 64), (70, 90, 65), (130, 33, 77), (75, 70, 200), (257, 129, 333)]
 LAYOUT_SHAPES = [(70, 90, 65), (130, 33, 77)]
@@ -166,6 +172,89 @@ def cases():
     yield lambda: _plan_case("plan_tt3_two_iterations")
 
 
+# N of `ops.eigh`: 48 single-launch solver | 96 .. 500 super-pair kernel + self pass (ld 128 .. 512; 500 pads to 512, the
+# largest that fits) | 520, 1100 resident pair kernel (ld 640, 1152: smallest and largest) | 1160, 2080 streamed pair
+# kernel (ld 1280 = one full chunk + 256, ld 2176 = two full chunks + 128)
+EIGH_N = [48, 96, 130, 288, 500, 520, 1100, 1160, 2080]
+EIGH_LOW_RANK_N = [130, 520]
+# one plan, four TT-linear layers: the level of the (r1 n2) x (n3 n4) unfoldings holds full solves of 96, 128 and 160 columns
+# (6, 8 and 10 super-block players: an aligned period with idle ticks, problems finishing at different sweeps) and, for the
+# 384-column layer, the filter's 96-column Rayleigh-Ritz problem
+PLAN_SUPER = [((96, 96), [8, 12, 12, 8], [1, 8, 24, 8, 1]), ((128, 128), [8, 16, 16, 8], [1, 8, 32, 8, 1]),
+              ((160, 160), [8, 20, 20, 8], [1, 8, 40, 8, 1]), ((384, 384), [16, 24, 24, 16], [1, 16, 64, 16, 1])]
+# the 640-column full solve (rank 400: no filter) puts its whole group on the pair kernel
+PLAN_PAIRS = [((640, 640), [20, 32, 32, 20], [1, 20, 400, 20, 1])]
+
+
+def _eigh_gram(name, N, kind):
+    """Symmetric PSD test matrix: "gauss" / "decay" as tests/test_gpu_kernels.py::test_eigh_jacobi, "rank4" = exactly
+    rank N/4 (unrotated pairs, the weighted measure, workgroups that return before the update).  The factor is rounded to
+    a grid (2^-16 of entries below 8, 2^-20 of entries below 1) on which every product and every partial sum of a a^T is
+    an fp64 number, so G does not depend on the order in which the host's BLAS adds."""
+    rng = np.random.default_rng(_seed(name))
+    if kind == "gauss":
+        a, grid = rng.standard_normal((N, 3 * N)), 2.0 ** 16
+    elif kind == "decay":
+        q, _ = np.linalg.qr(rng.standard_normal((N, N)))
+        a, grid = q * np.exp(-6.0 * np.arange(N) / N), 2.0 ** 20
+    else:
+        a, grid = rng.standard_normal((N, N // 4)), 2.0 ** 16
+    a = np.round(a * grid) / grid
+    G = a @ a.T
+    return 0.5 * (G + G.T)
+
+
+def _eigh_case(N, kind, r=None):
+    import torch
+    from tadmm import ops
+    name = "eigh_%d_%s" % (N, kind) if r is None else "eigh_partial_%d_r%d_%s" % (N, r, kind)
+    G = _eigh_gram(name, N, kind)
+    g = torch.from_numpy(G).to("cuda:0")
+    ev, vec, info = ops.eigh(g) if r is None else ops.eigh_partial(g, r)
+    torch.cuda.synchronize()
+    # eigenvalues, eigenvectors, and the sweep count (eigh) / the route (eigh_partial)
+    out = np.concatenate([ev.cpu().numpy().ravel(), vec.cpu().numpy().ravel(), np.array([float(info)])])
+    return name, _sha(G), out
+
+
+def _tt_linear_plan_case(name, table):
+    """TT-linear layers through one ProjectionPlan, two iterations with update_u=True: the residuals, Z and U."""
+    import torch
+    from tadmm import ops
+    from tadmm._cabi import KIND_TT_LINEAR
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(_seed(name))
+    layers, ins = [], []
+    for shape, tts, ranks in table:
+        wh = (0.1 * rng.standard_normal(shape)).astype(np.float32)
+        w = torch.from_numpy(wh).to(dev)
+        layers.append(dict(kind=KIND_TT_LINEAR, W=w, U=torch.zeros_like(w), Z=torch.zeros_like(w), tt_shapes=tts,
+                           ranks=ranks))
+        ins.append(wh)
+    plan = ops.ProjectionPlan(layers)
+    parts = []
+    for _ in range(2):
+        r = plan.run(update_u=True)
+        torch.cuda.synchronize()
+        parts.append(r.detach().cpu().numpy().astype(np.float64).view(np.uint8))
+    for L in layers:
+        parts.append(L["Z"].cpu().numpy().view(np.uint8).ravel())
+        parts.append(L["U"].cpu().numpy().view(np.uint8).ravel())
+    plan.close()
+    return name, _sha(*ins), np.concatenate([p.ravel() for p in parts])
+
+
+def eigh_cases():
+    for N in EIGH_N:
+        for kind in ("gauss", "decay"):
+            yield lambda a=(N, kind): _eigh_case(*a)
+    for N in EIGH_LOW_RANK_N:
+        yield lambda n=N: _eigh_case(n, "rank4")
+    yield lambda: _eigh_case(130, "gauss", r=20)
+    yield lambda: _tt_linear_plan_case("plan_super_pairs_6_8_10_players_and_rr96", PLAN_SUPER)
+    yield lambda: _tt_linear_plan_case("plan_pairs_640", PLAN_PAIRS)
+
+
 def samples(out):
     """64 evenly spaced entries of the flattened output, as (index, hex of the bytes) for diagnostics."""
     flat = np.ascontiguousarray(out).ravel()
@@ -176,13 +265,14 @@ def samples(out):
 def main():
     commit = sys.argv[1] if len(sys.argv) > 1 else "unknown"
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "dnn-compression-tensor-admm_amd"))
+    eigh = len(sys.argv) > 3 and sys.argv[3] == "eigh"
     doc = {"commit": commit, "cases": {}}
-    for make in cases():
+    for make in (eigh_cases() if eigh else cases()):
         name, in_sha, out = make()
         doc["cases"][name] = {"inputs_sha256": in_sha, "output_sha256": _sha(out), "dtype": str(out.dtype),
                               "numel": int(out.size), "samples": samples(out)}
         print(name, doc["cases"][name]["output_sha256"][:16], flush=True)
-    with open(sys.argv[2] if len(sys.argv) > 2 else FIXTURE, "w") as f:
+    with open(sys.argv[2] if len(sys.argv) > 2 else (EIGH_FIXTURE if eigh else FIXTURE), "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
 
