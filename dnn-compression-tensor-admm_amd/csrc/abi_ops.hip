@@ -666,4 +666,89 @@ int tadmm_cholqr_f64(tadmm_handle h, double* YT, int n, int ncols, int ldy, void
   return TADMM_OK;
 }
 
+// ---- the filter's tile product and daxpby, launched as the filter launches them (tests) ----
+int tadmm_dgemm_tile_prob_bytes(void) { return (int)sizeof(tadmm_dgemm_tile_prob); }
+
+static const char* dgemm_tile_refusal(int nprob, const tadmm_dgemm_tile_prob* p, int tile_m, int tile_n, int axpby) {
+  if (nprob <= 0 || nprob > 64 || !p) return "1 .. 64 problems";
+  if (!((tile_m == 32 && tile_n == 32) || (tile_m == 64 && (tile_n == 32 || tile_n == 64))))
+    return "(tile_m, tile_n) is (32, 32), (64, 32) or (64, 64)";
+  for (int i = 0; i < nprob; ++i) {
+    const tadmm_dgemm_tile_prob& q = p[i];
+    auto named = [&](int sel, const void* ptr) {
+      if (sel < 0) return ptr != nullptr;
+      return sel <= 2 && q.ring[0] && q.ring[1] && q.ring[2];
+    };
+    if (q.M <= 0 || q.N <= 0 || q.K <= 0 || q.M % 32 || q.N % 32 || q.K % 32) return "M, N, K positive multiples of 32";
+    if ((q.lda & 1) || (q.ldb & 1) || (q.ldc & 1) || q.lda < q.K || q.ldb < q.K || q.ldc < q.N)
+      return "even leading dimensions, lda, ldb >= K, ldc >= N";
+    if (q.mode < 0 || q.mode > 3) return "mode 0 .. 3";
+    if (!named(q.selC, q.C)) return "C is not named (explicit pointer, or sel 0 .. 2 with a full ring)";
+    if (axpby) {
+      if (!named(q.selP, q.P) || !q.coef) return "axpby needs P and coef";
+    } else {
+      if (!named(q.selA, q.A) || !named(q.selB, q.B)) return "A or B is not named";
+      if (q.mode >= 1 && !named(q.selP, q.P)) return "modes 1 .. 3 need P";
+      if (q.selQ > 2) return "selQ <= 2";
+      if (q.selQ >= 0 && !(q.ring[0] && q.ring[1] && q.ring[2])) return "selQ >= 0 needs a full ring";
+      if (q.mode == 1 && !q.coef) return "mode 1 needs coef";
+      if (q.mode == 3 && !q.theta) return "mode 3 needs theta";
+      if (q.mode >= 2 && !q.rowpart) return "modes 2, 3 need rowpart";
+    }
+  }
+  return nullptr;
+}
+
+static size_t dgemm_tile_blocks(const tadmm_dgemm_tile_prob& q, int tile_m, int tile_n, int axpby) {
+  if (axpby) return (size_t)(((int64_t)q.M * q.ldc + 1023) / 1024);
+  return (size_t)((q.M + tile_m - 1) / tile_m) * (size_t)((q.N + tile_n - 1) / tile_n);
+}
+
+int tadmm_dgemm_tile_check(int nprob, const tadmm_dgemm_tile_prob* probs, int tile_m, int tile_n, int axpby) {
+  return dgemm_tile_refusal(nprob, probs, tile_m, tile_n, axpby) ? TADMM_ERR_INVALID : TADMM_OK;
+}
+
+size_t tadmm_dgemm_tile_scratch_bytes(int nprob, const tadmm_dgemm_tile_prob* probs) {
+  if (nprob <= 0 || !probs) return 0;
+  size_t blocks = 0;
+  for (int i = 0; i < nprob; ++i)
+    blocks += std::max(dgemm_tile_blocks(probs[i], 32, 32, 0), dgemm_tile_blocks(probs[i], 32, 32, 1));
+  return align_up((size_t)nprob * sizeof(DgemmDesc), 256) + align_up(blocks * sizeof(BlockRef), 256);
+}
+
+int tadmm_dgemm_tile_f64(tadmm_handle h, int nprob, const tadmm_dgemm_tile_prob* probs, int tile_m, int tile_n, int axpby,
+                         void* scratch, size_t scratch_bytes, void* stream_) {
+  DeviceGuard device_guard(h);
+  if (!h || !scratch) return TADMM_ERR_INVALID;
+  if (const char* why = dgemm_tile_refusal(nprob, probs, tile_m, tile_n, axpby))
+    CTX_FAIL(h, TADMM_ERR_INVALID, "tadmm_dgemm_tile_f64: %s", why);
+  if (scratch_bytes < tadmm_dgemm_tile_scratch_bytes(nprob, probs)) CTX_FAIL(h, TADMM_ERR_WORKSPACE, "dgemm tile scratch too small");
+  hipStream_t s = (hipStream_t)stream_;
+  std::vector<DgemmDesc> descs((size_t)nprob);
+  std::vector<BlockRef> map;
+  for (int i = 0; i < nprob; ++i) {
+    const tadmm_dgemm_tile_prob& q = probs[i];
+    DgemmDesc& g = descs[(size_t)i];
+    memset(&g, 0, sizeof g);
+    g.A = q.A; g.B = q.B; g.C = q.C; g.P = q.P; g.Q = q.Q;
+    g.ring[0] = q.ring[0]; g.ring[1] = q.ring[1]; g.ring[2] = q.ring[2]; g.rot = q.rot;
+    g.selA = q.selA; g.selB = q.selB; g.selC = q.selC; g.selP = q.selP; g.selQ = q.selQ;
+    g.M = q.M; g.N = q.N; g.K = q.K; g.lda = q.lda; g.ldb = q.ldb; g.ldc = q.ldc;
+    g.tiles_m = q.M / 32; g.tiles_n = q.N / 32; g.mode = q.mode;
+    g.coef = q.coef; g.theta = q.theta; g.rowpart = q.rowpart; g.gate = q.gate; g.gate_min = q.gate_min;
+    const int nb = (int)dgemm_tile_blocks(q, tile_m, tile_n, axpby);
+    for (int b = 0; b < nb; ++b) map.push_back(BlockRef{i, b});
+  }
+  DgemmDesc* gd = (DgemmDesc*)scratch;
+  BlockRef* md = (BlockRef*)((char*)scratch + align_up((size_t)nprob * sizeof(DgemmDesc), 256));
+  HIP_OK(h, hipMemcpyAsync(gd, descs.data(), descs.size() * sizeof(DgemmDesc), hipMemcpyHostToDevice, s));
+  HIP_OK(h, hipMemcpyAsync(md, map.data(), map.size() * sizeof(BlockRef), hipMemcpyHostToDevice, s));
+  HIP_OK(h, hipStreamSynchronize(s));
+  if (axpby) launch_daxpby(gd, md, (int)map.size(), s);
+  else launch_dgemm_nt64(gd, md, (int)map.size(), s, tile_n, tile_m);
+  HIP_OK(h, hipStreamSynchronize(s));
+  HIP_OK(h, hipGetLastError());
+  return TADMM_OK;
+}
+
 }  // extern "C"

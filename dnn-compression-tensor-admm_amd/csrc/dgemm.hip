@@ -69,6 +69,18 @@ __device__ long long g_dstamps[64];
 #define DSTAMP(i) do { } while (0)
 #endif
 
+// Gate word and ring base of a launch, as every kernel here starts: false = the problem is gated off.  `gate` and `rot`
+// come out of the descriptor without an address space, and `*d.gate`, `*d.rot` were flat VECTOR loads of one uniform word,
+// each with a full `vmcnt(0) lgkmcnt(0)` wait and the second behind the first one's branch.  Read through gp() from an
+// address that is always valid (no gate: the block's own map entry, no ring: the gate's word) they are two scalar loads.
+__device__ __forceinline__ bool dg_open(const DgemmArgs& d, const BlockRef* __restrict__ map, int& base) {
+  const G<const int32_t>* gw = gp(d.gate ? d.gate : &map[blockIdx.x].prob);
+  const G<const int32_t>* rw = d.rot ? gp(d.rot) : gw;
+  const int gv = *gw, rv = *rw;
+  base = d.rot ? rv : 0;
+  return !(d.gate && gv < d.gate_min);
+}
+
 template <bool kBT>
 __global__ __launch_bounds__(256) void dgemm_kernel(const DgemmDesc* __restrict__ descs,
                                                     const BlockRef* __restrict__ map) {
@@ -76,8 +88,8 @@ __global__ __launch_bounds__(256) void dgemm_kernel(const DgemmDesc* __restrict_
   __shared__ double rowred[32][33];
   const BlockRef br = map[blockIdx.x];
   const DgemmArgs d = dg_args(descs + br.prob);
-  if (d.gate && *d.gate < d.gate_min) return;
-  const int base = d.rot ? *d.rot : 0;
+  int base;
+  if (!dg_open(d, map, base)) return;
   const double* __restrict__ A = dg_sel(d, d.selA, d.A, base);
   const double* __restrict__ B = dg_sel(d, d.selB, d.B, base);
   double* __restrict__ C = const_cast<double*>(dg_sel(d, d.selC, d.C, base));
@@ -228,6 +240,17 @@ constexpr int kDT = 64, kDK = 32, kDLd = kDK + 2;
 // workgroup's duration is its share of the fp64 matrix rate of ONE CU (a 64 x 32 x 480 tile is 2 MFLOP = 11 us at the
 // ~176 GFLOP/s a CU issues), and a product launch of the critical chain has 45 - 135 such workgroups on 256 CUs: the
 // smaller tile buys latency with operand traffic (each workgroup still streams its 32 rows of G).
+//
+// Order of a workgroup's memory traffic (a launch of the filter is about one workgroup per CU, so every dependent round
+// trip of this list is exposed in the launch's duration):
+//   map entry -> descriptor -> gate, rot -> operand pointers
+//   loads of K chunks 0 and 1 -> LDS store of chunk 0 -> loads of chunk 2
+//   loads of the epilogue operands of the thread's own CPT outputs: coef[0..2], theta[row], P, Q (TN = 32; with TN = 64
+//     they would cost a workgroup per CU in registers and go out after the K loop instead)
+//   K loop
+//   every K slice stores its accumulators to an LDS image of its own, one barrier, and the epilogue thread adds the KW
+//     images of an element in the fixed order (((0.0 + slice KW-1) + slice KW-2) + ...) + slice 0
+//   epilogue arithmetic on operands that are already in registers, stores.
 template <int TN, int KW, int TM = kDT>
 __global__ __launch_bounds__(128 * (TM / 32) * KW) void dgemm_nt_tile_kernel(const DgemmDesc* __restrict__ descs,
                                                                             const BlockRef* __restrict__ map) {
@@ -243,13 +266,18 @@ __global__ __launch_bounds__(128 * (TM / 32) * KW) void dgemm_nt_tile_kernel(con
   static_assert(AP >= 1 && BP >= 1 && CPT >= 2, "tile / thread layout");
   __shared__ __attribute__((aligned(16))) double smem[2 * kBuf > TM * (TN + 1) ? 2 * kBuf : TM * (TN + 1)];
   __shared__ double rowred[TM][TPR];
+  static_assert(KW * TM * (TN + 1) <= (2 * kBuf > TM * (TN + 1) ? 2 * kBuf : TM * (TN + 1)), "one LDS image per K slice");
   const BlockRef br = map[blockIdx.x];
   const DgemmArgs d = dg_args(descs + br.prob);
-  if (d.gate && *d.gate < d.gate_min) return;
-  const int base = d.rot ? *d.rot : 0;
+  int base;
+  if (!dg_open(d, map, base)) return;
   const G<const double>* __restrict__ A = gp(dg_sel(d, d.selA, d.A, base));
   const G<const double>* __restrict__ B = gp(dg_sel(d, d.selB, d.B, base));
   G<double>* __restrict__ C = gp(const_cast<double*>(dg_sel(d, d.selC, d.C, base)));
+  const int mode = d.mode;
+  const bool hasQ = mode == 1 && (d.selQ >= 0 || d.Q != nullptr);
+  const G<const double>* __restrict__ P = gp((mode >= 1) ? dg_sel(d, d.selP, d.P, base) : nullptr);
+  const G<const double>* __restrict__ Q = gp(hasQ ? dg_sel(d, d.selQ, d.Q, base) : nullptr);
   const int tiles_n = (d.N + TN - 1) / TN;
   const int tm = br.local / tiles_n, tn = br.local - tm * tiles_n;
   const int m0 = tm * TM, n0 = tn * TN;
@@ -329,8 +357,41 @@ __global__ __launch_bounds__(128 * (TM / 32) * KW) void dgemm_nt_tile_kernel(con
 #pragma unroll
   for (int u = 0; u < NPF; ++u)
     if (u < nch) gload(R[u], u * kDK);
+  // Epilogue operands.  None of them depends on the product, so their loads go out here, behind the loads of the first
+  // chunks and the first LDS store (vmcnt retires in order: the store waits for its chunk only), and they arrive while
+  // the K loop runs; the epilogue used to pay two to three dependent round trips for them after the fold (coef, then
+  // P, then Q once s2 was known).  Every load is unconditional on an address that is always valid: rows and columns
+  // beyond an edge are clamped as the operand rows are, and an operand the mode does not have reads the head of A's
+  // image instead (K >= 32 > CPT doubles).  Q is read whenever mode 1 names one, whatever s2 turns out to be;
+  // `if (s2 != 0.0)` still decides whether it is added.
+  // Early is safe: a thread reads exactly the elements of P and Q whose C element it alone writes, and in the filter
+  // C's ring slot is never A's, P's or Q's (selC = k % 3, selA = selP = (k-1) % 3, selQ = (k-2) % 3).
+  // TN = 64 holds 2 * CPT = 32 doubles per thread: carried through the K loop they would take the kernel from four
+  // waves per SIMD to two (one workgroup per CU), so there the loads go out after the loop, in front of the fold.
+  constexpr bool kEarly = CPT <= 8;
+  const int row = (tid & 255) / TPR, c0 = ((tid & 255) % TPR) * CPT;     // the epilogue's layout (its 256 threads)
+  const bool rok = m0 + row < d.M;
+  const int64_t ldc = d.ldc;
+  const int64_t gclamp = (int64_t)min(m0 + row, d.M - 1) * ldc + min(n0 + c0, d.N - CPT);
+  const G<const double>* cf = gp((mode == 1) ? d.coef : reinterpret_cast<const double*>(descs));   // (global, not flat: see gp())
+  double cf0, cf1, cf2, th;
+  double2_t pv[CPT / 2], qv[CPT / 2];
+  auto epilogue_loads = [&]() {
+    cf0 = cf[0]; cf1 = cf[1]; cf2 = cf[2];
+    if (NT == 256 || __builtin_amdgcn_readfirstlane(wave) < 4) {        // (a scalar branch: waves 4 .. 7 have no epilogue)
+      const G<const double>* pp = P ? P + gclamp : A;
+      const G<const double>* qp = Q ? Q + gclamp : A;
+      const G<const double>* tp = (mode == 3) ? gp(d.theta) + min(m0 + row, d.M - 1) : A;
+#pragma unroll
+      for (int u = 0; u < CPT / 2; ++u) pv[u] = *reinterpret_cast<const G<const double2_t>*>(pp + 2 * u);
+#pragma unroll
+      for (int u = 0; u < CPT / 2; ++u) qv[u] = *reinterpret_cast<const G<const double2_t>*>(qp + 2 * u);
+      th = *tp;
+    }
+  };
   sstore(R[0], 0);
   if (NPF < nch) gload(R[0], NPF * kDK);
+  if (kEarly) epilogue_loads();
   __syncthreads();
   DSTAMP(1);
   for (int c = 0; c < nch; c += NPF) {
@@ -349,49 +410,47 @@ __global__ __launch_bounds__(128 * (TM / 32) * KW) void dgemm_nt_tile_kernel(con
       }
     }
   }
-  // accumulators -> LDS tile [64][TN+1] (aliases the staging buffers; the loop's last barrier has passed)
-  double (*Ct)[TN + 1] = reinterpret_cast<double (*)[TN + 1]>(smem);
-  // the K slices fold their sums through LDS: the last slice writes, the others add in turn, slice 0 last
+  // accumulators -> one LDS image [TM][TN+1] per K slice (they alias the staging buffers; the loop's last barrier has
+  // passed), ONE barrier, and the epilogue thread adds the slices of its elements in the order the serial fold through
+  // LDS had: (((0.0 + slice KW-1) + slice KW-2) + ...) + slice 0
+  constexpr int kImg = TM * (TN + 1);
+  if (!kEarly) epilogue_loads();
+  {
+    double (*Ck)[TN + 1] = reinterpret_cast<double (*)[TN + 1]>(smem + kh * kImg);
 #pragma unroll
-  for (int h = KW - 1; h >= 0; --h) {
-    if (kh == h) {
+    for (int e = 0; e < 4; ++e)
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            double* c = &Ct[32 * wm + 16 * i + q + 4 * e][WN * wn + 16 * j + r];
-            *c = (h == KW - 1 ? 0.0 : *c) + acc[i][j][e];
-          }
-    }
-    __syncthreads();
+        for (int j = 0; j < NB; ++j) Ck[32 * wm + 16 * i + q + 4 * e][WN * wn + 16 * j + r] = acc[i][j][e];
   }
+  __syncthreads();
   if (NT > 256 && tid >= 256) return;   // the epilogue is laid out for 256 threads
-  const int mode = d.mode;
   double s0 = 1.0, s1 = 0.0, s2 = 0.0;
-  if (mode == 1) { s0 = d.coef[0]; s1 = d.coef[1]; s2 = d.coef[2]; }
-  const G<const double>* __restrict__ P = gp((mode >= 1) ? dg_sel(d, d.selP, d.P, base) : nullptr);
-  const G<const double>* __restrict__ Q = gp((mode == 1 && s2 != 0.0) ? dg_sel(d, d.selQ, d.Q, base) : nullptr);
-  const int64_t ldc = d.ldc;
-  const int row = tid / TPR, c0 = (tid % TPR) * CPT;
-  const bool rok = m0 + row < d.M;
+  if (mode == 1) { s0 = cf0; s1 = cf1; s2 = cf2; }
+  const double (*Ct)[TN + 1] = reinterpret_cast<const double (*)[TN + 1]>(smem);
+  auto folded = [&](int rr, int cc) {
+    double v = 0.0 + Ct[(KW - 1) * TM + rr][cc];                         // (image h = rows h TM .. of the [.][TN+1] view)
+#pragma unroll
+    for (int h = KW - 2; h >= 0; --h) v = v + Ct[h * TM + rr][cc];
+    return v;
+  };
   double part = 0.0;
   if (rok && n0 + c0 < d.N) {                                            // N % 16 == 0: a thread's columns are in or out together
-    const double th = (mode == 3) ? d.theta[m0 + row] : 0.0;
+    if (mode != 3) th = 0.0;
 #pragma unroll
     for (int u = 0; u < CPT; u += 2) {
       const int col = c0 + u;
       const int64_t gi = (int64_t)(m0 + row) * ldc + n0 + col;
-      const double v0 = Ct[row][col], v1 = Ct[row][col + 1];
+      const double v0 = folded(row, col), v1 = folded(row, col + 1);
       if (mode == 0) {
         *reinterpret_cast<G<double2_t>*>(C + gi) = double2_t{v0, v1};
       } else {
-        const double2_t p = *reinterpret_cast<const G<const double2_t>*>(P + gi);
+        const double2_t p = pv[u / 2];
         if (mode == 1) {
           double o0 = s0 * v0 + s1 * p.x, o1 = s0 * v1 + s1 * p.y;
-          if (Q) {
-            const double2_t qq = *reinterpret_cast<const G<const double2_t>*>(Q + gi);
+          if (s2 != 0.0 && hasQ) {
+            const double2_t qq = qv[u / 2];
             o0 += s2 * qq.x; o1 += s2 * qq.y;
           }
           *reinterpret_cast<G<double2_t>*>(C + gi) = double2_t{o0, o1};
@@ -450,8 +509,8 @@ void launch_dgemm_nt64(const DgemmDesc* descs_dev, const BlockRef* map_dev, int 
 __global__ __launch_bounds__(256) void daxpby_kernel(const DgemmDesc* __restrict__ descs, const BlockRef* __restrict__ map) {
   const BlockRef br = map[blockIdx.x];
   const DgemmArgs d = dg_args(descs + br.prob);
-  if (d.gate && *d.gate < d.gate_min) return;
-  const int base = d.rot ? *d.rot : 0;
+  int base;
+  if (!dg_open(d, map, base)) return;
   double* __restrict__ C = const_cast<double*>(dg_sel(d, d.selC, d.C, base));
   const double* __restrict__ P = dg_sel(d, d.selP, d.P, base);
   const double s0 = d.coef[0], s1 = d.coef[1];

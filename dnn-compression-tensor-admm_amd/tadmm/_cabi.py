@@ -96,6 +96,20 @@ class StiefelDesc(C.Structure):
     ]
 
 
+class DgemmTileProb(C.Structure):
+    """tadmm_dgemm_tile_prob: one problem of the filter's tile product / daxpby as the filter describes it (tests)."""
+    _fields_ = [
+        ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("P", C.c_void_p), ("Q", C.c_void_p),
+        ("ring", C.c_void_p * 3), ("rot", C.c_void_p),
+        ("selA", C.c_int32), ("selB", C.c_int32), ("selC", C.c_int32), ("selP", C.c_int32), ("selQ", C.c_int32),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("lda", C.c_int32), ("ldb", C.c_int32), ("ldc", C.c_int32),
+        ("mode", C.c_int32),
+        ("coef", C.c_void_p), ("theta", C.c_void_p), ("rowpart", C.c_void_p),
+        ("gate", C.c_void_p), ("gate_min", C.c_int32),
+    ]
+
+
 TTM_MAX_D = 4
 
 
@@ -255,6 +269,11 @@ ABI = {
                                    C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tadmm_dgemm_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tadmm_dgemm_tile_prob_bytes": (C.c_int, []),
+    "tadmm_dgemm_tile_check": (C.c_int, [C.c_int, C.POINTER(DgemmTileProb), C.c_int, C.c_int, C.c_int]),
+    "tadmm_dgemm_tile_scratch_bytes": (C.c_size_t, [C.c_int, C.POINTER(DgemmTileProb)]),
+    "tadmm_dgemm_tile_f64": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(DgemmTileProb), C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "tadmm_cholqr_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_cholqr_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                    C.POINTER(C.c_int), C.c_void_p]),
@@ -322,6 +341,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_lstm_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
+        if lib.tadmm_dgemm_tile_prob_bytes() != C.sizeof(DgemmTileProb):
+            raise TadmmLibraryError(f"{path}: tadmm_dgemm_tile_prob layout mismatch")
         _lib = lib
         return lib
 

@@ -1126,6 +1126,40 @@ def dgemm(a: torch.Tensor, b: torch.Tensor, b_transposed: bool = True) -> torch.
     return out
 
 
+def dgemm_tile_probs(probs):
+    """The C array of `tadmm_dgemm_tile_prob` for a list of dicts (tests).  Keys: A, B, C, P, Q, rot, coef, theta,
+    rowpart, gate (device tensors or None; of A, B, C, P the data pointer and of A, B, C the row stride are taken),
+    ring (three tensors shaped like C), selA .. selQ (default -1), M, N, K, mode, gate_min, and lda / ldb / ldc where no
+    tensor gives them."""
+    from ._cabi import DgemmTileProb
+    arr = (DgemmTileProb * len(probs))()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    for q, p in zip(arr, probs):
+        ring = p.get("ring")
+        for name in ("A", "B", "C", "P", "Q", "rot", "coef", "theta", "rowpart", "gate"):
+            setattr(q, name, ptr(p.get(name)))
+        if ring is not None:
+            q.ring[0], q.ring[1], q.ring[2] = (t.data_ptr() for t in ring)
+        for name in ("selA", "selB", "selC", "selP", "selQ"):
+            setattr(q, name, int(p.get(name, -1)))
+        q.M, q.N, q.K, q.mode, q.gate_min = int(p["M"]), int(p["N"]), int(p["K"]), int(p.get("mode", 0)), int(p.get("gate_min", 0))
+        for ld, name, sel in (("lda", "A", "selA"), ("ldb", "B", "selB"), ("ldc", "C", "selC")):
+            t = p.get(name) if p.get(sel, -1) < 0 else ring[0]
+            setattr(q, ld, int(p[ld]) if ld in p else (0 if t is None else t.stride(0)))
+    return arr
+
+
+def dgemm_tile(probs, tile_m: int, tile_n: int, axpby: bool = False, device=None) -> None:
+    """One grouped launch of the filter's NT tile product (or of its daxpby) on `probs` (see `dgemm_tile_probs`), with
+    (tile_m, tile_n) = (32, 32), (64, 32) or (64, 64); results land in the tensors the problems name.  For tests."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    arr = dgemm_tile_probs(probs)
+    h = _handle(device)
+    scratch = _scratch(max(256, h.lib.tadmm_dgemm_tile_scratch_bytes(len(probs), arr)), device)
+    h.check(h.lib.tadmm_dgemm_tile_f64(h.ptr, len(probs), arr, tile_m, tile_n, int(axpby), scratch.data_ptr(),
+                                       scratch.numel(), _stream(device)))
+
+
 def dgemm3(a: torch.Tensor, g: torch.Tensor, repeats: int = 1) -> torch.Tensor:
     """a (M, N) @ g (N, N)^T at fp32 accuracy on the bf16 matrix cores (float64 in / out): the product the early
     stages of the filtered eigen-solver use (csrc/dgemm3.hip)."""

@@ -628,6 +628,32 @@ int tadmm_dgemm3_f64(tadmm_handle h, const double* A, const double* G, double* C
 size_t tadmm_cholqr_scratch_bytes(int n, int ncols);
 int tadmm_cholqr_f64(tadmm_handle h, double* YT, int n, int ncols, int ldy, void* scratch, size_t scratch_bytes,
                      int* bad_out_host, void* stream);
+/* One grouped launch of the filter's NT tile product (dgemm_nt_tile_kernel) or of daxpby_kernel on `nprob` problems
+ * exactly as the filter describes them, for tests: C = epilogue(A * B^T) with the epilogue modes, the ring of three
+ * buffers addressed as (*rot + sel) % 3 (sel < 0: the explicit pointer) and the gate word of csrc/dgemm.hip.
+ * (tile_m, tile_n) = (32, 32), (64, 32) or (64, 64).  M, N multiples of 32, K of 32, even leading dimensions;
+ * rowpart (modes 2, 3) holds ceil(N / tile_n) * M doubles.  axpby = 1: C <- coef[0]*C + coef[1]*P over M * ldc elements
+ * instead of the product.  Synchronous. */
+typedef struct {
+  const double* A; const double* B; double* C;
+  const double* P; const double* Q;
+  double* ring[3];
+  const int32_t* rot;                         /* device word, nullable */
+  int32_t selA, selB, selC, selP, selQ;
+  int32_t M, N, K;
+  int32_t lda, ldb, ldc;
+  int32_t mode;                               /* 0 .. 3 */
+  const double* coef;                         /* device, mode 1 and axpby */
+  const double* theta;                        /* device, mode 3 */
+  double* rowpart;                            /* device, modes 2 and 3 */
+  const int32_t* gate; int32_t gate_min;      /* device word, nullable */
+} tadmm_dgemm_tile_prob;
+int tadmm_dgemm_tile_prob_bytes(void);
+/* host only, no device needed: TADMM_OK, or TADMM_ERR_INVALID for arguments tadmm_dgemm_tile_f64 refuses */
+int tadmm_dgemm_tile_check(int nprob, const tadmm_dgemm_tile_prob* probs, int tile_m, int tile_n, int axpby);
+size_t tadmm_dgemm_tile_scratch_bytes(int nprob, const tadmm_dgemm_tile_prob* probs);
+int tadmm_dgemm_tile_f64(tadmm_handle h, int nprob, const tadmm_dgemm_tile_prob* probs, int tile_m, int tile_n, int axpby,
+                         void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }
