@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -27,6 +27,7 @@ def __getattr__(name):
         "TTEmbedding": ("emb_layers", "TTEmbedding"), "TTMEmbedding": ("emb_layers", "TTMEmbedding"),
         "SVDEmbedding": ("emb_layers", "SVDEmbedding"),
         "TTLSTM": ("rnn_layers", "TTLSTM"),
+        "DistillationLoss": ("losses", "DistillationLoss"),
         "stiefel_step": ("ops", "stiefel_step"), "stiefel_project_": ("ops", "stiefel_project_"),
     }
     if name in table:

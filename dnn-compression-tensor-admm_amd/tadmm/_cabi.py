@@ -134,6 +134,25 @@ class LstmDesc(C.Structure):
     ]
 
 
+DISTILL_BASE_NONE, DISTILL_BASE_INDEX, DISTILL_BASE_DENSE = 0, 1, 2
+DISTILL_KD_NONE, DISTILL_KD_SOFT_KL, DISTILL_KD_HARD, DISTILL_KD_SOFT_CE = 0, 1, 2, 3
+
+
+class DistillDesc(C.Structure):
+    _fields_ = [
+        ("s", C.c_void_p), ("k", C.c_void_p), ("t", C.c_void_p),
+        ("s_ld", C.c_int64), ("k_ld", C.c_int64), ("t_ld", C.c_int64),
+        ("labels", C.c_void_p), ("dense", C.c_void_p), ("dense_ld", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("loss_dev", C.c_void_p), ("loss_f32_dev", C.c_void_p), ("counts_dev", C.c_void_p),
+        ("grad_s", C.c_void_p), ("grad_k", C.c_void_p),
+        ("ignore_index", C.c_int64),
+        ("eps", C.c_double), ("alpha", C.c_double), ("tau", C.c_double),
+        ("B", C.c_int32), ("C", C.c_int32), ("dtype", C.c_int32),
+        ("base_kind", C.c_int32), ("kd_kind", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -247,6 +266,9 @@ ABI = {
     "tadmm_lstm_seq_fwd": (C.c_int, [C.c_void_p, C.POINTER(LstmDesc), C.c_void_p]),
     "tadmm_lstm_seq_fwd_save": (C.c_int, [C.c_void_p, C.POINTER(LstmDesc), C.c_void_p]),
     "tadmm_lstm_seq_bwd": (C.c_int, [C.c_void_p, C.POINTER(LstmDesc), C.c_void_p]),
+    "tadmm_distill_desc_bytes": (C.c_int, []),
+    "tadmm_distill_workspace_bytes": (C.c_int, [C.POINTER(DistillDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_distill_loss": (C.c_int, [C.c_void_p, C.POINTER(DistillDesc), C.c_void_p]),
     "tadmm_core_conv_desc_bytes": (C.c_int, []),
     "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
     "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
@@ -339,6 +361,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_ttm_desc layout mismatch")
         if lib.tadmm_lstm_desc_bytes() != C.sizeof(LstmDesc):
             raise TadmmLibraryError(f"{path}: tadmm_lstm_desc layout mismatch")
+        if lib.tadmm_distill_desc_bytes() != C.sizeof(DistillDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_distill_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         if lib.tadmm_dgemm_tile_prob_bytes() != C.sizeof(DgemmTileProb):

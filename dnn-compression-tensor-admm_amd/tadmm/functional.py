@@ -761,3 +761,199 @@ def lstm_sequence(xp: torch.Tensor, w_hh: torch.Tensor, h0: torch.Tensor = None,
         return lstm_sequence_composed(xp, w_hh, h0, c0, gate)
     y, hT, cT = _LstmSeq.apply(xp, w_hh, h0, c0, gate == "sigmoid")
     return y, (hT, cT)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Distillation loss (csrc/distill.hip): the criterion of losses.py: DistillationLoss -- base cross entropy, the
+# distillation term and the gradients of both logit tensors in two launches -- and task_distill.py: soft_cross_entropy.
+# ---------------------------------------------------------------------------------------------------------------
+DISTILL_BASES = ("none", "index", "dense")
+DISTILL_KDS = ("none", "soft", "hard", "soft_ce")
+
+
+def _same_memory(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return a.data_ptr() == b.data_ptr() and a.stride() == b.stride() and a.shape == b.shape and a.dtype == b.dtype
+
+
+class _DistillFn(torch.autograd.Function):
+    """The forward computes the value and the float32 gradients of both logit tensors; the backward multiplies them by the
+    incoming gradient and only then rounds to the logits' type (a float16 gradient of a 1000-class row is below float16's
+    normal range before GradScaler's 2^16 is applied)."""
+
+    @staticmethod
+    def forward(ctx, outputs, outputs_kd, teacher, target, cfg, counts_box):
+        base, kd, alpha, tau, smoothing, ignore_index = cfg
+        want_s = ctx.needs_input_grad[0] and base != "none"
+        want_k = ctx.needs_input_grad[1] and kd != "none"
+        ref = outputs if base != "none" else outputs_kd
+        ctx.same = want_s and want_k and _same_memory(outputs, outputs_kd)
+        out = {}
+        if ctx.same:
+            flat = torch.empty((1,) + tuple(ref.shape), dtype=torch.float32, device=ref.device)
+            out = {"grad_s": flat[0], "grad_k": flat[0]}
+        elif want_s or want_k:
+            flat = torch.empty((int(want_s) + int(want_k),) + tuple(ref.shape), dtype=torch.float32, device=ref.device)
+            out = {"grad_s": flat[0]} if want_s else {}
+            if want_k:
+                out["grad_k"] = flat[-1]
+        else:
+            flat = None
+        loss, counts, _, _ = ops.distill_loss(outputs, outputs_kd, teacher, target, base=base, kd=kd, alpha=alpha, tau=tau,
+                                              smoothing=smoothing, ignore_index=ignore_index, grad=(want_s, want_k),
+                                              out=out)
+        if counts_box is not None:
+            counts_box.append(counts)
+        ctx.flat, ctx.wants, ctx.dtype = flat, (want_s, want_k), ref.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        flat = ctx.flat
+        if flat is None:
+            return (None,) * 6
+        g = gout if gout.dtype == torch.float32 else gout.float()
+        if ctx.dtype == torch.float32:
+            res = flat * g
+        else:          # scale in float32, round once on the store
+            res = torch.empty(flat.shape, dtype=ctx.dtype, device=flat.device)
+            torch.mul(flat, g, out=res)
+        want_s, want_k = ctx.wants
+        gs = res[0] if want_s else None
+        gk = res[-1] if (want_k and not ctx.same) else None       # same memory: the sum went to the first
+        return gs, gk, None, None, None, None
+
+
+def _distill_args(outputs, outputs_kd, teacher, target, base, kd, who):
+    if base not in DISTILL_BASES or kd not in DISTILL_KDS:
+        raise ValueError(f"{who}: base is one of {DISTILL_BASES}, kd one of {DISTILL_KDS} (got {base!r}, {kd!r})")
+    if base == "none" and kd == "none":
+        raise ValueError(f"{who}: base and kd are both 'none'")
+    logits = [(n, t) for n, t, used in (("outputs", outputs, base != "none"), ("outputs_kd", outputs_kd, kd != "none"),
+                                        ("teacher", teacher, kd != "none")) if used]
+    for n, t in logits:
+        if not isinstance(t, torch.Tensor):
+            raise TadmmError(-1, f"{who}: {n} must be a tensor (got {type(t).__name__})")
+    n0, t0 = logits[0]
+    if t0.dim() != 2 or t0.shape[0] < 1 or t0.shape[1] < 1:
+        raise ValueError(f"{who}: {n0} must be (B >= 1, C >= 1) (got {tuple(t0.shape)})")
+    for n, t in logits:
+        if not t.is_cuda:
+            raise TadmmError(-1, f"{who}: {n} must live on the HIP device (got {t.device}); there is no CPU path")
+        if t.dtype not in ops.DISTILL_DTYPES:
+            raise TadmmError(-1, f"{who}: {n} must be float32, bfloat16 or float16 (got {t.dtype})")
+        if t.dtype != t0.dtype:
+            raise TadmmError(-1, f"{who}: {n} is {t.dtype}, {n0} is {t0.dtype}; one type per call")
+        if t.device != t0.device:
+            raise TadmmError(-1, f"{who}: {n} on {t.device}, {n0} on {t0.device}")
+        if t.shape != t0.shape:
+            raise ValueError(f"{who}: {n} is {tuple(t.shape)}, {n0} is {tuple(t0.shape)}")
+    if base != "none":
+        if not isinstance(target, torch.Tensor) or not target.is_cuda:
+            where = target.device if isinstance(target, torch.Tensor) else type(target).__name__
+            raise TadmmError(-1, f"{who}: target must live on the HIP device (got {where}); there is no CPU path")
+        if target.device != t0.device:
+            raise TadmmError(-1, f"{who}: target on {target.device}, {n0} on {t0.device}")
+        if base == "index":
+            if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+                raise TypeError(f"{who}: integer labels are required for base='index' (got {target.dtype})")
+            if tuple(target.shape) != (t0.shape[0],):
+                raise ValueError(f"{who}: target must be ({t0.shape[0]},) (got {tuple(target.shape)})")
+            target = target if target.dtype == torch.int64 else target.to(torch.int64)
+        else:
+            if not target.dtype.is_floating_point:
+                raise TypeError(f"{who}: dense target rows must be of a floating type (got {target.dtype})")
+            if target.shape != t0.shape:
+                raise ValueError(f"{who}: target must be {tuple(t0.shape)} (got {tuple(target.shape)})")
+            target = target if target.dtype == torch.float32 else target.float()
+    return target
+
+
+def distillation_loss_composed(outputs, outputs_kd, teacher, target, *, base: str = "index", kd: str = "soft",
+                               alpha: float = 0.5, tau: float = 1.0, smoothing: float = 0.0, ignore_index=-100,
+                               counts=None) -> torch.Tensor:
+    """`distillation_loss` as the reference composes it (losses.py:35-61, task_distill.py:721-724) from torch
+    operations on the device, under autograd, in float32 whatever the logits' type: the route where
+    `ops.distill_loss_pays` says the launch is not ahead, and the yardstick of tests/test_gpu_distill.py and
+    scripts/bench_distill.py.  Labels outside [0, C) are mapped to the ignored label first (torch would fault on them)
+    and counted into `counts` (a list that receives the int64 [kept rows, bad labels] tensor) when that is given."""
+    target = _distill_args(outputs, outputs_kd, teacher, target, base, kd, "distillation_loss_composed")
+    base_loss = None
+    if base == "index":
+        C = outputs.shape[1]
+        ign = ops.DISTILL_NO_IGNORE if ignore_index is None else int(ignore_index)
+        valid = (target != ign) & (target >= 0) & (target < C)
+        fill = ign if ignore_index is not None else -100
+        safe = torch.where(valid, target, torch.full_like(target, fill))
+        base_loss = F.cross_entropy(outputs.float(), safe, ignore_index=fill, label_smoothing=float(smoothing))
+        if counts is not None:
+            counts.append(torch.stack([valid.sum(), ((target != ign) & ~valid).sum()]))
+    elif base == "dense":
+        base_loss = F.cross_entropy(outputs.float(), target, label_smoothing=float(smoothing))
+    if base != "index" and counts is not None:
+        ref = outputs if base != "none" else outputs_kd
+        counts.append(torch.tensor([ref.shape[0], 0], dtype=torch.int64, device=ref.device))
+    if kd == "none":
+        return base_loss
+    k, t, T = outputs_kd.float(), teacher.float(), float(tau)
+    if kd == "soft":
+        kd_loss = F.kl_div(F.log_softmax(k / T, dim=1), F.log_softmax(t / T, dim=1), reduction="sum",
+                           log_target=True) * (T * T) / k.numel()
+    elif kd == "hard":
+        kd_loss = F.cross_entropy(k, t.argmax(dim=1))
+    else:
+        kd_loss = (-F.softmax(t / T, dim=-1) * F.log_softmax(k / T, dim=-1)).mean()
+    if base_loss is None:
+        return kd_loss * alpha
+    return base_loss * (1 - alpha) + kd_loss * alpha
+
+
+def distillation_loss(outputs, outputs_kd, teacher, target, *, base: str = "index", kd: str = "soft", alpha: float = 0.5,
+                      tau: float = 1.0, smoothing: float = 0.0, ignore_index=-100, route: str = None,
+                      counts=None) -> torch.Tensor:
+    """The training criterion of losses.py: DistillationLoss as one differentiable call, float32 0-dim:
+
+        base  "index": cross entropy of `outputs` (B, C) against integer labels `target` (B,), label smoothing
+                       `smoothing`, mean over the rows whose label is neither `ignore_index` (None: ignore nothing) nor
+                       outside [0, C) -- the latter are counted, contribute nothing and are never used as an address;
+              "dense": soft-target cross entropy against float rows `target` (B, C), mean over B;
+              "none":  no base term (`outputs`, `target` unused)
+        kd    "soft":  KL(softmax(teacher / tau) || softmax(outputs_kd / tau)) * tau^2 / (B C)   (losses.py:51-56)
+              "hard":  cross entropy of outputs_kd against the teacher's argmax                  (losses.py:58)
+              "soft_ce": mean over B C of -softmax(teacher / tau) log_softmax(outputs_kd / tau)  (task_distill.py:721)
+              "none":  the base term alone
+        loss = (1 - alpha) base + alpha kd       (kd "none": base; base "none": alpha kd)
+
+    The logits are float32, bfloat16 or float16 HIP tensors of one type, unit column stride (row slices of a wider
+    tensor are read in place); `outputs_kd` may be `outputs`.  Differentiable in `outputs` and `outputs_kd`; the teacher
+    gets no gradient.  `route`: None (by the measured rule `ops.distill_loss_pays`), "launch" (csrc/distill.hip: value
+    and gradients in two launches, the backward one or two more) or "composed" (torch operations).  `counts`: a list
+    that receives the int64 device tensor [kept rows, bad labels] of the call.  Nothing synchronises."""
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"distillation_loss: route is None, 'launch' or 'composed' (got {route!r})")
+    target = _distill_args(outputs, outputs_kd, teacher, target, base, kd, "distillation_loss")
+    ref = outputs if base != "none" else outputs_kd
+    if route is None:
+        grad = torch.is_grad_enabled() and _needs_grad(*[t for t in (outputs, outputs_kd) if isinstance(t, torch.Tensor)])
+        launch = ops.distill_loss_pays(ref.shape[0], ref.shape[1], ref.dtype, grad)
+    else:
+        launch = route == "launch"
+    kw = dict(base=base, kd=kd, alpha=alpha, tau=tau, smoothing=smoothing, ignore_index=ignore_index)
+    if not launch:
+        return distillation_loss_composed(outputs, outputs_kd, teacher, target, counts=counts, **kw)
+    cfg = (base, kd, float(alpha), float(tau), float(smoothing), ignore_index)
+    s = outputs if base != "none" else None
+    k = outputs_kd if kd != "none" else None
+    return _DistillFn.apply(s, k, None if teacher is None else teacher.detach(), target, cfg, counts)
+
+
+def soft_cross_entropy(predicts: torch.Tensor, targets: torch.Tensor, temperature: float = 1.0,
+                       route: str = None) -> torch.Tensor:
+    """task_distill.py:721-724 with the division of :833 folded in: mean over all elements of
+    -softmax(targets / temperature) * log_softmax(predicts / temperature), class dimension last; float32 0-dim,
+    differentiable in `predicts`."""
+    if not isinstance(predicts, torch.Tensor) or not isinstance(targets, torch.Tensor) or predicts.dim() < 1:
+        raise TadmmError(-1, "soft_cross_entropy: predicts and targets must be tensors with a class dimension")
+    C = predicts.shape[-1]
+    p = predicts if predicts.dim() == 2 else predicts.reshape(-1, C)
+    t = targets if targets.dim() == 2 else targets.reshape(-1, C)
+    return distillation_loss(None, p, t.detach(), None, base="none", kd="soft_ce", alpha=1.0, tau=temperature, route=route)

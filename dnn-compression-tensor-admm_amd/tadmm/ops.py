@@ -1785,3 +1785,108 @@ def lstm_seq_pays(T: int, B: int, H: int, grad: bool = False) -> bool:
     training step (3.3x - 30.6x); the smallest margin is H = 256, T = 6, B = 256.  No class of the table goes the other
     way, so every shape the launch takes is sent to it.  Batches beyond 256 rows were not measured."""
     return True
+
+
+# ------------------------------------------------------------------ distillation loss (csrc/distill.hip)
+DISTILL_BASES = {"none": _cabi.DISTILL_BASE_NONE, "index": _cabi.DISTILL_BASE_INDEX, "dense": _cabi.DISTILL_BASE_DENSE}
+DISTILL_KDS = {"none": _cabi.DISTILL_KD_NONE, "soft": _cabi.DISTILL_KD_SOFT_KL, "hard": _cabi.DISTILL_KD_HARD,
+               "soft_ce": _cabi.DISTILL_KD_SOFT_CE}
+DISTILL_DTYPES = {torch.float32: _cabi.CHAIN_F32, torch.bfloat16: _cabi.CHAIN_BF16, torch.float16: _cabi.CHAIN_F16}
+DISTILL_NO_IGNORE = -2 ** 63         # an ignore_index no label can equal out of range by accident: "ignore nothing"
+
+
+def distill_workspace_bytes(B: int) -> int:
+    """Bytes of the row-term workspace of `tadmm_distill_loss` for B rows (`tadmm_distill_workspace_bytes`).  Host only."""
+    d = _cabi.DistillDesc()
+    d.B = int(B)
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_distill_workspace_bytes(C.byref(d), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_distill_workspace_bytes: B = {B}")
+    return int(size.value)
+
+
+def _distill_rows(t, who, what, shape, dtypes):
+    """A (B, C) operand read by rows: unit column stride and a row stride >= C as it stands (a row slice of a wider
+    tensor), anything else as a contiguous copy.  Returns (tensor, row stride)."""
+    t = _operand(t, who, what, dtypes, shape, layout=None)
+    B, Cc = t.shape
+    if (Cc > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < Cc):
+        t = t.contiguous()
+    return t, (max(int(t.stride(0)), Cc) if B > 1 else Cc)
+
+
+def distill_loss(outputs, outputs_kd, teacher, target, *, base: str, kd: str, alpha: float = 0.5, tau: float = 1.0,
+                 smoothing: float = 0.0, ignore_index: Optional[int] = -100, grad=True, out: Optional[dict] = None):
+    """(loss, counts, grad_s, grad_k) of `tadmm_distill_loss`: the base criterion on `outputs` (B, C), the distillation
+    term of `outputs_kd` against `teacher`, mixed as (1-alpha) base + alpha kd (`kd="none"`: the base alone;
+    `base="none"`: alpha kd), in two launches, gradients included.  base: "none", "index" (`target` int64 (B,); labels
+    equal to `ignore_index` or outside [0, C) are dropped from the mean, the latter counted; `ignore_index=None`: nothing
+    is ignored), "dense" (`target` float32 (B, C) rows).  kd: "none", "soft" (KL at temperature tau, times tau^2 / (B C)),
+    "hard" (cross entropy against the teacher's first argmax), "soft_ce" (task_distill.py:721-724 at temperature tau).
+    The logits are float32, bfloat16 or float16, all of one type, with unit column stride and any row stride >= C (no
+    copy is made of such views).  loss: float32 0-dim; counts: int64 [kept rows, bad labels]; grad_s, grad_k: float32
+    (B, C) gradients with respect to `outputs` / `outputs_kd` (`grad`: a bool or a pair of bools; None where not asked
+    for).  `out`: optional {"grad_s", "grad_k"} tensors to write them into; handing the same tensor for both yields the
+    sum of the two in it (what a caller wants when `outputs_kd` is `outputs`).  Nothing synchronises."""
+    who = "distill_loss"
+    if base not in DISTILL_BASES or kd not in DISTILL_KDS:
+        raise ValueError(f"{who}: base is one of {sorted(DISTILL_BASES)}, kd one of {sorted(DISTILL_KDS)} "
+                         f"(got {base!r}, {kd!r})")
+    if base == "none" and kd == "none":
+        raise ValueError(f"{who}: base and kd are both 'none'")
+    first = outputs if base != "none" else outputs_kd
+    first = _operand(first, who, "outputs" if base != "none" else "outputs_kd", tuple(DISTILL_DTYPES), layout=None)
+    if first.dim() != 2 or first.shape[0] < 1 or first.shape[1] < 1:
+        raise TadmmError(-1, f"{who}: the logits must be (B >= 1, C >= 1) (got {tuple(first.shape)})")
+    B, Cc = first.shape
+    dev, dt = first.device, first.dtype
+    d = _cabi.DistillDesc()
+    keep = []
+    for name, field, t, used in (("outputs", "s", outputs, base != "none"), ("outputs_kd", "k", outputs_kd, kd != "none"),
+                                 ("teacher", "t", teacher, kd != "none")):
+        if not used:
+            continue
+        t, ld = _distill_rows(t, who, name, (B, Cc), (dt,))
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: {name} on {t.device}, the other logits on {dev}")
+        keep.append(t)
+        setattr(d, field, t.data_ptr())
+        setattr(d, field + "_ld", ld)
+    if base == "index":
+        target = _operand(target, who, "target", (torch.int64,), (B,), layout="copy")
+        d.labels = target.data_ptr()
+    elif base == "dense":
+        target, d.dense_ld = _distill_rows(target, who, "target", (B, Cc), (torch.float32,))
+        d.dense = target.data_ptr()
+    if base != "none" and target.device != dev:
+        raise TadmmError(-1, f"{who}: target on {target.device}, the logits on {dev}")
+    want_s, want_k = (bool(grad), bool(grad)) if isinstance(grad, bool) else (bool(grad[0]), bool(grad[1]))
+    out = dict(out or {})
+    gs = _output(out.get("grad_s"), (B, Cc), torch.float32, dev, f"{who}: grad_s") if want_s and base != "none" else None
+    gk = _output(out.get("grad_k"), (B, Cc), torch.float32, dev, f"{who}: grad_k") if want_k and kd != "none" else None
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    wide = torch.empty(3, dtype=torch.int64, device=dev)          # [loss as double | kept rows | bad labels]
+    nbytes = distill_workspace_bytes(B)
+    ws = _scratch(nbytes, dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+    d.loss_dev, d.counts_dev, d.loss_f32_dev = wide.data_ptr(), wide.data_ptr() + 8, loss.data_ptr()
+    d.grad_s = None if gs is None else gs.data_ptr()
+    d.grad_k = None if gk is None else gk.data_ptr()
+    d.ignore_index = DISTILL_NO_IGNORE if ignore_index is None else int(ignore_index)
+    d.eps, d.alpha, d.tau = float(smoothing), float(alpha), float(tau)
+    d.B, d.C, d.dtype = B, Cc, DISTILL_DTYPES[dt]
+    d.base_kind, d.kd_kind = DISTILL_BASES[base], DISTILL_KDS[kd]
+    h = _handle(dev)
+    h.check(h.lib.tadmm_distill_loss(h.ptr, C.byref(d), _stream(dev)))
+    return loss, wide[1:], gs, gk
+
+
+def distill_loss_pays(B: int, C: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.distillation_loss` sends a call to the launch and not to the composed torch route.  A pure
+    function of the batch, the class count, the logit type and whether gradients will be asked for.  Measured
+    (scripts/bench_distill.py) at (B, C) from (32, 2) to (1024, 1000), soft and hard distillation,
+    float32 and float16, value only and value + backward: the launch's slowest window is below the composed route's
+    fastest in all 48 classes (2.1x - 4.2x; both routes are bound by the host at these sizes), so the rule is a
+    constant.  Batches beyond 1024 rows and class counts beyond 1000 were not measured."""
+    return True

@@ -585,6 +585,56 @@ int tadmm_lstm_seq_fwd(tadmm_handle h, const tadmm_lstm_desc* d, void* stream);
 int tadmm_lstm_seq_fwd_save(tadmm_handle h, const tadmm_lstm_desc* d, void* stream);
 int tadmm_lstm_seq_bwd(tadmm_handle h, const tadmm_lstm_desc* d, void* stream);
 
+/* ---- distillation loss: base criterion, KD term and logit gradients (csrc/distill.hip) -------------------------------
+ * losses.py: DistillationLoss around CrossEntropyLoss / LabelSmoothingCrossEntropy / SoftTargetCrossEntropy, and
+ * xcompression/task_distill.py:721-724 soft_cross_entropy, for B rows of C logits in two launches.  s = outputs, k =
+ * outputs_kd (may be the same memory as s), t = the teacher's logits: all of `dtype` (TADMM_CHAIN_F32 / _BF16 / _F16),
+ * unit column stride, row strides s_ld / k_ld / t_ld >= C in elements, any element-aligned base (16-byte, 8-byte or
+ * element accesses are chosen from the bases and strides).
+ *   base_b = -sum_c q_bc log_softmax(s_b)_c   INDEX: q_b = (1-eps) onehot(labels[b]) + eps/C, mean over the kept rows
+ *                                             DENSE: q_b = (1-eps) dense[b] + eps/C (float32 rows, stride dense_ld >= C),
+ *                                                    mean over B
+ *   kd_b     SOFT_KL: sum_c p_t (log p_t - log p_k), p = softmax(. / tau); total scaled by tau^2 / (B*C)
+ *            HARD:    -log_softmax(k_b)[argmax_c t_bc], first maximal index; mean over B
+ *            SOFT_CE: -sum_c softmax(t_b / tau)_c log_softmax(k_b / tau)_c; mean over B*C
+ *   loss   = base when kd_kind is NONE, else (1-alpha) base + alpha kd (base_kind NONE: alpha kd).
+ * INDEX rows: labels[b] == ignore_index drops the row from the base term and its denominator; any other label outside
+ * [0, C) does the same and is counted as bad; labels are compared, never used as an address.  No kept row: NaN.
+ * Outputs: loss_dev[0] (double), loss_f32_dev[0] (nullable: the same value rounded once), counts_dev[0] = kept rows (B
+ * unless INDEX), counts_dev[1] = bad labels; all three are overwritten.  grad_s / grad_k (nullable, float32, contiguous
+ * B x C, 4-byte aligned): d loss / d s and d loss / d k; equal pointers receive the sum of the two (the caller's choice
+ * when s and k are one tensor).  Rows that are not kept get exact zeros in grad_s.
+ * workspace: tadmm_distill_workspace_bytes (host only, reads B alone) bytes, 8-byte aligned: two doubles and one int32
+ * per row, each array rounded up to 256 bytes.  Every logit is shifted by its row maximum before exp; sums are double;
+ * no floating-point atomics; bitwise reproducible; no host synchronisation.
+ * TADMM_ERR_INVALID, with nothing launched: a NULL handle or descriptor, B < 1 or C < 1, an unknown kind or dtype, both
+ * kinds NONE, a pointer the chosen kinds read that is NULL (s for a base kind; k, t for a KD kind; labels; dense;
+ * loss_dev; counts_dev), a pointer not aligned to its element, a row stride below C, eps outside [0, 1], tau <= 0 where
+ * tau is used (SOFT_KL, SOFT_CE).  TADMM_ERR_WORKSPACE: workspace NULL, misaligned or short. */
+enum { TADMM_DISTILL_BASE_NONE = 0, TADMM_DISTILL_BASE_INDEX = 1, TADMM_DISTILL_BASE_DENSE = 2 };
+enum { TADMM_DISTILL_KD_NONE = 0, TADMM_DISTILL_KD_SOFT_KL = 1, TADMM_DISTILL_KD_HARD = 2, TADMM_DISTILL_KD_SOFT_CE = 3 };
+typedef struct {
+  const void* s; const void* k; const void* t;
+  int64_t s_ld, k_ld, t_ld;                   /* elements */
+  const int64_t* labels;                      /* INDEX */
+  const float* dense; int64_t dense_ld;       /* DENSE */
+  void* workspace; size_t workspace_bytes;
+  double* loss_dev;
+  float* loss_f32_dev;                        /* nullable */
+  int64_t* counts_dev;                        /* [kept rows, bad labels] */
+  float* grad_s; float* grad_k;               /* nullable */
+  int64_t ignore_index;
+  double eps, alpha, tau;
+  int32_t B, C;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 */
+  int32_t base_kind, kd_kind;
+  int32_t reserved;
+} tadmm_distill_desc;
+/* sizeof(tadmm_distill_desc) as the library was built */
+int tadmm_distill_desc_bytes(void);
+int tadmm_distill_workspace_bytes(const tadmm_distill_desc* d, size_t* bytes);
+int tadmm_distill_loss(tadmm_handle h, const tadmm_distill_desc* d, void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
