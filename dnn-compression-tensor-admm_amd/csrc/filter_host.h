@@ -595,8 +595,12 @@ static inline int filter_run_pre(tadmm_handle h, FilterGroup& fg, char* ws, Poll
 
 // Part 2 (after the Rayleigh-Ritz solve + eig_norms/sort/extract of the group): Ritz vectors, verification, outputs.
 // Returns the number of problems that must take the fallback solve in *nbad.
+// `behind_verdict` (optional): queued behind the verdict's event and in front of the host's wait for it, so that the
+// stream is not empty while the host wakes up -- the caller's next launch when no problem falls back (the usual case).
+// It must be a launch that may simply be repeated after the fallback solve has replaced some of its inputs.
 static inline int filter_run_post(tadmm_handle h, FilterGroup& fg, char* ws, PollCtx& poll, hipStream_t s, bool debug,
-                                  int* nbad, FilterTiming* tm = nullptr) {
+                                  int* nbad, FilterTiming* tm = nullptr,
+                                  const std::function<void()>& behind_verdict = nullptr) {
   *nbad = 0;
   if (fg.nf == 0) return TADMM_OK;
   auto D = [&](size_t off) { return ws + off; };
@@ -631,6 +635,7 @@ static inline int filter_run_post(tadmm_handle h, FilterGroup& fg, char* ws, Pol
   launch_filt_emit(probs, (const BlockRef*)D(fg.emit.map_off), fg.emit.nblocks, s);
   if (fg.ncomp > 0) launch_comp_emit((const CompDesc*)D(fg.comp_off), (const BlockRef*)D(fg.cemit.map_off), fg.cemit.nblocks, s);
   HIP_OK(h, hipEventRecord(poll.ev[0], s));
+  if (behind_verdict) behind_verdict();
   HIP_OK(h, hipEventSynchronize(poll.ev[0]));
   int bad = 0;
   for (int q = 0; q < fg.nf; ++q) bad += poll.host[1 + q] ? 0 : 1;

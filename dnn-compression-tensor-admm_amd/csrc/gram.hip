@@ -228,34 +228,63 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const GramDesc* __res
 __global__ __launch_bounds__(256) void gram_reduce_kernel(const GramDesc* __restrict__ descs,
                                                           const BlockRef* __restrict__ map,
                                                           const int32_t* __restrict__ skip) {
-  const BlockRef br = map[blockIdx.x];
-  if (skip && skip[br.prob]) return;
-  const GramDesc d = descs[br.prob];
-  const int ntp = d.nt * (d.nt + 1) / 2;
-  const int64_t total = (int64_t)d.Npad * d.ld;
-  const int64_t base = (int64_t)br.local * 1024;
-  for (int t = threadIdx.x; t < 1024; t += 256) {
-    const int64_t idx = base + t;
-    if (idx >= total) break;
-    const int j = (int)(idx / d.ld), i = (int)(idx - (int64_t)j * d.ld);
-    double v = 0.0;
-    if (j < d.N && i < d.N) {
-      int a = j >> 5, b = i >> 5, jr = j & 31, ir = i & 31;
-      if (a > b) { int s = a; a = b; b = s; s = jr; jr = ir; ir = s; }
-      if (a == b && jr > ir) { const int s = jr; jr = ir; ir = s; }   // diagonal tiles: upper part only
-      const int tp = a * d.nt - (a * (a - 1)) / 2 + (b - a);
-      const double* p = d.partial + (int64_t)tp * 1024 + jr * 32 + ir;
-      const int64_t stride = (int64_t)ntp * 1024;
-      int ks = 0;
-      for (; ks + 8 <= d.ksplit; ks += 8) {          // independent loads in flight; the order of the adds is fixed
-        double t[8];
+  const G<const BlockRef>* brp = gp(map + blockIdx.x);
+  const int prob = brp->prob, local = brp->local;
+  const G<const GramDesc>* d = gp(descs + prob);
+  // (the descriptor goes out beside the skip word: both are scalar loads behind the map entry)
+  const int nt = d->nt, N = d->N, Npad = d->Npad, ld = d->ld, ksplit = d->ksplit;
+  const G<const double>* partial = gp((const double*)d->partial);
+  G<double>* Gout = gp(d->G);
+  if (skip && gp(skip)[prob]) return;
+  const int ntp = nt * (nt + 1) / 2;
+  const int64_t total = (int64_t)Npad * ld;
+  const int64_t base = (int64_t)local * 1024;
+  const int64_t stride = (int64_t)ntp * 1024;
+  const bool small = total <= 0x7fffffff;            // uniform: split the index with 32-bit arithmetic
+  // A thread's four outputs are independent: the partial loads of all four go out before the first add.  An output of
+  // the padding (or past the image) reads the first partial instead and its adds are skipped.
+  const G<const double>* p[4];
+  bool live[4];
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = p[(ks + u) * stride];
-        v += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-      }
-      for (; ks < d.ksplit; ++ks) v += p[ks * stride];
-    }
-    d.G[idx] = v;
+  for (int o = 0; o < 4; ++o) {
+    const int64_t idx = base + threadIdx.x + 256 * o;
+    const int j = small ? (int)((uint32_t)idx / (uint32_t)ld) : (int)(idx / ld);
+    const int i = (int)(idx - (int64_t)j * ld);
+    live[o] = idx < total && j < N && i < N;
+    int a = j >> 5, b = i >> 5, jr = j & 31, ir = i & 31;
+    if (a > b) { int s = a; a = b; b = s; s = jr; jr = ir; ir = s; }
+    if (a == b && jr > ir) { const int s = jr; jr = ir; ir = s; }   // diagonal tiles: upper part only
+    const int tp = a * nt - (a * (a - 1)) / 2 + (b - a);
+    p[o] = live[o] ? partial + (int64_t)tp * 1024 + jr * 32 + ir : partial;
+  }
+  int ks = 0;
+  for (; ks + 8 <= ksplit; ks += 8) {                // the order of the adds is fixed
+    double t[4][8];
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[o][u] = p[o][(ks + u) * stride];
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+      v[o] += ((t[o][0] + t[o][1]) + (t[o][2] + t[o][3])) + ((t[o][4] + t[o][5]) + (t[o][6] + t[o][7]));
+  }
+  if (ks < ksplit) {                                 // up to seven more, one by one in order: loads on clamped chunks
+    double t[4][7];
+    const int n = ksplit - ks;
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int u = 0; u < 7; ++u) t[o][u] = p[o][(ks + min(u, n - 1)) * stride];
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int u = 0; u < 7; ++u) v[o] = u < n ? v[o] + t[o][u] : v[o];
+  }
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    const int64_t idx = base + threadIdx.x + 256 * o;
+    if (idx < total) Gout[idx] = live[o] ? v[o] : 0.0;
   }
 }
 

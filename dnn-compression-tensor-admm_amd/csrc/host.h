@@ -324,6 +324,10 @@ struct EigGroup {
   const int* mid_sizes = nullptr;   // per problem: 128 / 192 when it may take the direct route (EigDesc::scratch set), else 0
   std::function<void(hipStream_t)> after_init;   // tick path only: queued right after jacobi_init (which takes the scale
                                                  // of a problem from X = G), e.g. the warm start X <- V G of big problems
+  // tick path only, optional: launches that only read the X images and write outputs of their own (the group's finalize).
+  // Queued behind every sweep whose verdict the host then blocks on -- the sweeps from `expected` on -- so that the
+  // stream is not empty during that wait; run_eig_group reports whether they stand behind the final sweep.
+  std::function<void(hipStream_t)> behind_last;
   // debug only
   const double* off_dev = nullptr; const int* done_dev = nullptr;
 };
@@ -434,11 +438,16 @@ static inline int build_eig_layout(tadmm_handle h, EigLayout& l, std::vector<Eig
 // for small problems that are long finished.
 // Small groups (every problem <= 64 columns) run in ONE launch (jacobi_small_kernel decides convergence itself);
 // *small_pending is set and the caller, after queueing the group's finalize launches, calls check_small_group.
+// *behind_last_stands (optional) is set when g.behind_last was queued behind the sweep that turned out to be the last:
+// the caller then has nothing left to queue for the group.
 static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll, double tol, int max_sweeps, bool debug,
-                                hipStream_t s, int* sweeps_out, bool* small_pending, JacobiTiming* jt = nullptr) {
+                                hipStream_t s, int* sweeps_out, bool* small_pending, JacobiTiming* jt = nullptr,
+                                bool* behind_last_stands = nullptr) {
   const bool super = g.kernel == EigTick::SuperPairs;
   *sweeps_out = 0;
   *small_pending = false;
+  if (behind_last_stands) *behind_last_stands = false;
+  bool stands = false;
   if (g.neig == 0) return TADMM_OK;
   {
     const char* e = getenv("TADMM_JACOBI_SMALL");     // 0: always use the tick kernels (A/B measurements)
@@ -570,9 +579,13 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
     if (g.expected > 0 && gs + 1 >= g.expected) {
       // Jacobi needs about the same number of sweeps from one ADMM iteration to the next: from the sweep that
       // was the last one last time, wait for the verdict (one short stall) instead of queueing a sweep of
-      // launches that would most likely find every problem finished.
+      // launches that would most likely find every problem finished.  What the caller would queue after the group goes
+      // out first (behind the event: the verdict is not delayed), so the GPU has work while the host wakes up; if the
+      // verdict says "not all done" the tournament continues and those launches are simply queued again later.
+      if (g.behind_last && behind_last_stands) { g.behind_last(s); stands = true; }
       rc = consume();
       if (rc != TADMM_OK) CTX_FAIL(h, rc, "poll event failed");
+      if (!all_done) stands = false;
     }
   }
   if (!all_done) {
@@ -587,6 +600,7 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
   }
   if (!all_done) CTX_FAIL(h, TADMM_ERR_NOCONVERGE, "Jacobi did not converge in %d sweeps", max_sweeps);
   *sweeps_out = needed;
+  if (behind_last_stands) *behind_last_stands = stands;
   return TADMM_OK;
 }
 

@@ -121,7 +121,25 @@ struct StepPlan {
   std::vector<int> filt_of;       // filtered problem -> problem of the level
   size_t skip_off = 0;            // [neig] ints: eig group (set for filtered problems that went bad)
   size_t fb_skip_off = 0;         // [nf] ints: fallback group (1 = filtered result accepted)
+  // every projection of the level has beta == 0 and an output that overlaps neither operand: a second launch overwrites
+  // the first, so the launch may be queued before the filter's verdict is known and repeated after a fallback solve
+  bool proj_repeatable = false;
 };
+
+// the element range a strided M x N float matrix touches
+static inline void gemm_span(const float* p, int64_t rows, int64_t cols, int64_t rs, int64_t cs, const float** lo, const float** hi) {
+  *lo = p;
+  *hi = p + (rows - 1) * rs + (cols - 1) * cs + 1;
+}
+static inline bool gemm_repeatable(const GemmDesc& g) {
+  if (g.beta != 0.f || g.M <= 0 || g.N <= 0 || g.K <= 0) return false;
+  if (g.a_rs < 0 || g.a_cs < 0 || g.b_rs < 0 || g.b_cs < 0 || g.c_rs < 0 || g.c_cs < 0) return false;
+  const float *c0, *c1, *a0, *a1, *b0, *b1;
+  gemm_span(g.C, g.M, g.N, g.c_rs, g.c_cs, &c0, &c1);
+  gemm_span(g.A, g.M, g.K, g.a_rs, g.a_cs, &a0, &a1);
+  gemm_span(g.B, g.K, g.N, g.b_rs, g.b_cs, &b0, &b1);
+  return (c1 <= a0 || a1 <= c0) && (c1 <= b0 || b1 <= c0);
+}
 
 struct tadmm_plan_s {
   tadmm_handle h = nullptr;
@@ -457,6 +475,8 @@ static int layout_plan(tadmm_plan_s* P, const float* const* W, float* const* U, 
     sp.fb.prev_off = ar.take((size_t)std::max<size_t>(1, ed_fb.size()) * 8);
     if (const int rc = build_eig_layout(h, sp.fb, ed_fb, true, da, img)) return rc;
     place_phase(sp.proj, da, img, pd.data(), pd.size() * sizeof(GemmDesc), neig, m_proj);
+    sp.proj_repeatable = !pd.empty();
+    for (const GemmDesc& g : pd) sp.proj_repeatable = sp.proj_repeatable && gemm_repeatable(g);
   }
 
   // ---- reconstruction chain, right to left:  R = T_{d-1};  R <- core_s * R ----
@@ -929,14 +949,18 @@ static int single_run(tadmm_plan p, int update_u, int use_u, double* resid_sq_de
   toc(0, 0);
 
   // one eigen group of a level: the tournament (or the single-launch solver) and its finalize launches
-  auto solve_group = [&](EigLayout& L, const EigGroup& eg, bool* small_pending) -> int {
+  // The finalize launches only read the X images and write outputs of their own, so the tournament may queue them
+  // behind the sweep it expects to be the last, in front of its blocking read of that sweep's verdict (EigGroup::behind_last).
+  auto solve_group = [&](EigLayout& L, EigGroup eg, bool* small_pending) -> int {
     int gs = 0;
+    bool finalized = false;
+    eg.behind_last = [&](hipStream_t st) { L.finalize(ws, st, eg.skip); };
     const int rc = run_eig_group(h, eg, p->poll, p->tol, p->max_global_sweeps, p->debug, s, &gs,
-                                 small_pending, &p->jtm);
+                                 small_pending, &p->jtm, &finalized);
     if (rc != TADMM_OK) return rc;
     L.last_sweeps = gs;     // main: the next run's `expected`; fallback: informational (its expected stays 0)
     total_sweeps += gs;
-    L.finalize(ws, s, eg.skip);
+    if (!finalized) L.finalize(ws, s, eg.skip);
     return TADMM_OK;
   };
 
@@ -958,6 +982,10 @@ static int single_run(tadmm_plan p, int update_u, int use_u, double* resid_sq_de
     eg.off_dev = (const double*)D(sp.off_off); eg.done_dev = (const int*)D(sp.done_off);
     eg.expected = sp.main.last_sweeps;
     bool small_pending = false;
+    bool proj_queued = false;
+    auto launch_proj = [&] {
+      launch_gemm((const GemmDesc*)D(sp.proj.desc_off), (const BlockRef*)D(sp.proj.map_off), sp.proj.nblocks, s);
+    };
     {
       const int rc = solve_group(sp.main, eg, &small_pending);
       if (rc != TADMM_OK) return rc;
@@ -969,8 +997,14 @@ static int single_run(tadmm_plan p, int update_u, int use_u, double* resid_sq_de
         small_pending = false;
       }
       int nbad = 0;
-      int rc = filter_run_post(h, sp.fg, ws, p->poll, s, p->debug, &nbad, &p->ftm);
+      // The level's projection goes out behind the verdict's event, before the host waits for it; when a problem falls
+      // back, the launch is repeated below on the fallback's outputs.  Instrumented runs keep the phases apart.
+      std::function<void()> early_proj;
+      if (sp.proj_repeatable && !p->timing)
+        early_proj = [&] { launch_proj(); proj_queued = true; };
+      int rc = filter_run_post(h, sp.fg, ws, p->poll, s, p->debug, &nbad, &p->ftm, early_proj);
       if (rc != TADMM_OK) return rc;
+      if (nbad > 0) proj_queued = false;
       p->filt_problems += sp.fg.nf;
       p->filt_fallbacks += nbad;
       p->filt_stages = std::max(p->filt_stages, sp.fg.last_stages);
@@ -987,7 +1021,7 @@ static int single_run(tadmm_plan p, int update_u, int use_u, double* resid_sq_de
     }
     toc(0, 2);
     tic(0);
-    launch_gemm((const GemmDesc*)D(sp.proj.desc_off), (const BlockRef*)D(sp.proj.map_off), sp.proj.nblocks, s);
+    if (!proj_queued) launch_proj();
     toc(0, 3);
     if (small_pending) {      // the finalize + projection launches above are already queued behind it
       const int rc = check_small_group(h, eg, p->poll);
