@@ -417,7 +417,7 @@ int tadmm_gram_f64(tadmm_handle h, const float* A, int m, int n, double* G, int 
 size_t tadmm_eigh_scratch_bytes(int N) {
   const EigGeom g = eig_geom(N, N, 64, true);
   const size_t Npad = g.Npad, ld = g.ld;
-  return align_up(Npad * ld * 8, 256) + align_up(sizeof(EigDesc), 256) + 4 * align_up(Npad * sizeof(BlockRef), 256) +
+  return align_up(Npad * ld * 8, 256) + align_up(sizeof(EigDesc), 256) + 3 * align_up(Npad * sizeof(BlockRef), 256) +
          align_up(Npad * 8, 256) * 2 + align_up(Npad * 4, 256) + 1024 + align_up((Npad / 16) * 256 * 8, 256);
 }
 
@@ -438,8 +438,8 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   EigDesc* edev = (EigDesc*)(base + o_desc);
   // the group layout of this one problem, with offsets into the scratch instead of a plan's workspace
   EigLayout L;
-  Phase* phases[4] = {&L.tick, &L.norm, &L.ext, &L.self};
-  size_t o_map[4];
+  Phase* phases[3] = {&L.tick, &L.norm, &L.ext};
+  size_t o_map[3];
   for (size_t& o : o_map) o = carve(Npad * sizeof(BlockRef));
   double* lam = (double*)(base + carve((size_t)Npad * 8));
   double* sigma = (double*)(base + carve((size_t)Npad * 8));
@@ -457,9 +457,9 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   e.sblk = sblk;
   EigMaps maps;
   if (const int rc = eig_maps(h, L, ev, false, maps)) return rc;
-  const std::vector<BlockRef>* mv[4] = {&maps.tick, &maps.norm, &maps.ext, &maps.self};
+  const std::vector<BlockRef>* mv[3] = {&maps.tick, &maps.norm, &maps.ext};
   HIP_OK(h, hipMemcpyAsync(edev, &e, sizeof e, hipMemcpyHostToDevice, s));
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < 3; ++i) {
     phases[i]->desc_off = o_desc;
     phases[i]->map_off = o_map[i];
     HIP_OK(h, hipMemcpyAsync(base + o_map[i], mv[i]->data(), mv[i]->size() * sizeof(BlockRef), hipMemcpyHostToDevice, s));
@@ -468,7 +468,6 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   const bool super = L.kernel == EigTick::SuperPairs;
   const int units = L.players[0];
   const BlockRef* m_tick = (const BlockRef*)(base + L.tick.map_off);
-  const BlockRef* m_self = (const BlockRef*)(base + L.self.map_off);
   const double tol = 1e-9;
   int tick = 0, gs = 0;
   bool conv = false;
@@ -497,7 +496,6 @@ static int eigh_leading(tadmm_handle h, const double* G, int N, int r, double* e
   for (; gs < 40 && !conv; ++gs) {
     for (int t = 0; t < units - 1; ++t, ++tick) {
       if (super) {
-        if (t == 0) HIP_OK(h, launch_jacobi_self(edev, m_self, L.self.nblocks, tick, tol, ld, s));
         HIP_OK(h, launch_jacobi_tick3(edev, m_tick, L.tick.nblocks, tick, tol, ld, s));
       } else {
         HIP_OK(h, launch_jacobi_tick(edev, m_tick, L.tick.nblocks, tick, tol, L.tick_lds, s));

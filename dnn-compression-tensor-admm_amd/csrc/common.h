@@ -80,8 +80,8 @@ struct EigDesc {
   int32_t* warm_ok;   // [1] the image is valid (written by a converged solve whose spectrum allowed normalising every column)
   double* scratch;    // optional: 4 * N * N doubles of global scratch -- the problem may take the direct route of tridiag_mid.hip
   int32_t period;     // ticks per sweep of the GROUP's schedule (tick3 groups; 0: this problem's own players - 1): with one
-                      // period for every problem of a group all sweeps start at the same tick, so the self pass is launched
-                      // once per global sweep; a problem with fewer players idles in the ticks beyond its own
+                      // period for every problem of a group all sweeps start at the same tick; a problem with fewer
+                      // players idles in the ticks beyond its own
 };
 void launch_jacobi_init(const EigDesc* descs_dev, int nprob, hipStream_t s, const int32_t* skip = nullptr,
                         double* prev_dev = nullptr);   // prev_dev: [nprob] history of jacobi_conv_kernel, reset here
@@ -103,7 +103,8 @@ void dump_stamps();
 size_t jacobi_tick3_lds_bytes(int ld_max);
 bool jacobi_tick3_fits(int ld_max);
 // tick3: super-pair kernel with carried self-Grams, one workgroup per pair of 16-column super-blocks (nb/4 per problem,
-// nb/2-1 ticks per sweep; one cross-Gram per launch, round-2 solve overlapped with the round-1 update).  Needs launch_jacobi_self on the first tick of every sweep (it refreshes EigDesc::sblk).
+// nb/2-1 ticks per sweep; one cross-Gram per launch, round-2 solve overlapped with the round-1 update).  The first tick
+// of a sweep also rotates the pairs inside every super-block and refreshes EigDesc::sblk from their columns.
 hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
                                int ld_max, hipStream_t s);
 // rows of an eigen-solver image are whole 1 KiB chunks (128 doubles): the tick kernels have no other loader than the
@@ -111,9 +112,6 @@ hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev
 // holds 16 such rows up to ld = 1152; longer rows go through the streamed pair kernel.
 constexpr int kLdResidentMax = 1152;
 static inline int eig_ld(int N) { return (N + 127) / 128 * 128; }
-// once-per-sweep companion of tick3 (tick1 in self mode): within-block pairs + refresh of the carried self-Grams
-hipError_t launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                              int ld_max, hipStream_t s);
 // whole eigen-solve of small problems (Npad <= 64) in one launch, one workgroup per problem; converged flags go to
 // verdict_pinned[1 + p]
 bool jacobi_small_fits(int npad_max);

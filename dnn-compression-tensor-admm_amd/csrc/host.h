@@ -257,7 +257,7 @@ static inline void xcd_by_key(std::vector<BlockRef>& m, KeyFn key) {
 // Which tick kernel a group of problems uses.
 enum class EigTick {
   Pairs,        // one workgroup per pair of 8-column blocks: jacobi_tick_kernel, or the streamed kernel for long rows
-  SuperPairs,   // one workgroup per pair of 16-column super-blocks: jacobi_tick3_kernel + the self pass once per sweep
+  SuperPairs,   // one workgroup per pair of 16-column super-blocks: jacobi_tick3_kernel, self pass in a sweep's first tick
 };
 // Super-pairs whenever 32 columns of the group's longest row fit the LDS (ld_max <= 512).  TADMM_JACOBI_MODE=0 asks for
 // pairs (A/B measurements); any other value means the default.
@@ -313,7 +313,6 @@ struct EigGroup {
   int ld_max = 0;
   size_t tick_lds = 0;              // Pairs: dynamic LDS of the tick launches
   const BlockRef* tick_map = nullptr; int tick_blocks = 0;
-  const BlockRef* self_map = nullptr; int self_blocks = 0;
   double* prev_dev = nullptr;       // [neig] scratch of the convergence kernel
   const int32_t* skip = nullptr;    // optional per-problem predicate (non-zero: the problem is dropped)
   int npad_max = 0;                 // largest padded problem size (<= 64: single-launch solver)
@@ -333,9 +332,9 @@ struct EigGroup {
 };
 
 // Plan-time state of one grouped eigen-solve: where its descriptors and block maps sit in the workspace, and the
-// kernel choice of the group.  tick carries the EigDesc array; self / norm / ext are further maps over it.
+// kernel choice of the group.  tick carries the EigDesc array; norm / ext are further maps over it.
 struct EigLayout {
-  Phase tick, self, norm, ext;
+  Phase tick, norm, ext;
   std::vector<int> players;       // per problem: tournament players
   std::vector<int> row_len;       // per problem: ld of the X image (instrumented runs)
   std::vector<int> mid;           // per problem: 128 / 192 when it may take the direct route of tridiag_mid.hip, else 0
@@ -359,7 +358,6 @@ struct EigLayout {
     g.gsteps = gsteps; g.kernel = kernel; g.aligned = aligned;
     g.ld_max = ld_max; g.npad_max = npad_max; g.tick_lds = tick_lds;
     g.tick_map = (const BlockRef*)(ws + tick.map_off); g.tick_blocks = tick.nblocks;
-    g.self_map = (const BlockRef*)(ws + self.map_off); g.self_blocks = self.nblocks;
     g.prev_dev = (double*)(ws + prev_off);
     g.skip = skip;
     return g;
@@ -376,11 +374,11 @@ struct EigLayout {
   void finalize(char* ws, hipStream_t s, const int32_t* skip) const { sort(ws, s, skip); extract(ws, s, skip); }
 };
 
-// Kernel choice, players and the four block maps of a group (counts go into the layout's phases, offsets do not).
+// Kernel choice, players and the three block maps of a group (counts go into the layout's phases, offsets do not).
 // `align` (tick3 groups, unless TADMM_JACOBI_ALIGN=0): stamp one sweep period on every problem.
 // Every eigen-solver descriptor of the library passes through here, so this is where the premise of the tick kernels'
 // loader is checked: rows of whole 1 KiB pieces (eig_ld).
-struct EigMaps { std::vector<BlockRef> tick, self, norm, ext; };
+struct EigMaps { std::vector<BlockRef> tick, norm, ext; };
 static inline int eig_maps(tadmm_handle h, EigLayout& l, std::vector<EigDesc>& descs, bool align, EigMaps& m) {
   for (const EigDesc& e : descs)
     if (e.ld <= 0 || e.ld % 128)
@@ -402,28 +400,25 @@ static inline int eig_maps(tadmm_handle h, EigLayout& l, std::vector<EigDesc>& d
     l.mid.push_back((e.scratch && eig_mid_direct_size(e.N) && e.N == e.Npad) ? e.N : 0);
     l.gsteps = std::max(l.gsteps, units - 1);
     for (int b = 0; b < units / 2; ++b) m.tick.push_back(BlockRef{pq, b});
-    if (super) for (int b = 0; b < units; ++b) m.self.push_back(BlockRef{pq, b});
     for (int b = 0; b < (e.Npad + 3) / 4; ++b) m.norm.push_back(BlockRef{pq, b});
     for (int b = 0; b < (e.r + 3) / 4; ++b) m.ext.push_back(BlockRef{pq, b});
   }
   xcd_group(m.tick);
-  xcd_group(m.self);
   l.aligned = super && align && align_sweeps_on();
   if (l.aligned) for (EigDesc& e : descs) e.period = l.gsteps;
-  l.tick.nprob = l.self.nprob = l.norm.nprob = l.ext.nprob = l.neig;
-  l.tick.nblocks = (int)m.tick.size(); l.self.nblocks = (int)m.self.size();
+  l.tick.nprob = l.norm.nprob = l.ext.nprob = l.neig;
+  l.tick.nblocks = (int)m.tick.size();
   l.norm.nblocks = (int)m.norm.size(); l.ext.nblocks = (int)m.ext.size();
   return TADMM_OK;
 }
 
-// eig_maps + placement: descriptors and tick map, then the self, norm and ext maps, in that order from `da`
+// eig_maps + placement: descriptors and tick map, then the norm and ext maps, in that order from `da`
 static inline int build_eig_layout(tadmm_handle h, EigLayout& l, std::vector<EigDesc>& descs, bool align, Arena& da,
                                    HostImage* img) {
   EigMaps m;
   const int rc = eig_maps(h, l, descs, align, m);
   if (rc != TADMM_OK) return rc;
   place_phase(l.tick, da, img, descs.data(), descs.size() * sizeof(EigDesc), l.neig, m.tick);
-  place_map_like(l.self, l.tick, da, img, m.self);
   place_map_like(l.norm, l.tick, da, img, m.norm);
   place_map_like(l.ext, l.tick, da, img, m.ext);
   return TADMM_OK;
@@ -434,8 +429,7 @@ static inline int build_eig_layout(tadmm_handle h, EigLayout& l, std::vector<Eig
 // so finished problems cost nothing in later launches).  The host only needs "all finished?" and reads that
 // verdict one sweep late: the verdict of sweep g (written by the kernel straight into pinned host memory -- no
 // copy in the stream) is consumed after sweep g+1 has been queued, so the GPU never idles on a poll; the price
-// is one sweep of empty launches at the end.  The per-problem flags let the host stop launching the self pass
-// for small problems that are long finished.
+// is one sweep of empty launches at the end.
 // Small groups (every problem <= 64 columns) run in ONE launch (jacobi_small_kernel decides convergence itself);
 // *small_pending is set and the caller, after queueing the group's finalize launches, calls check_small_group.
 // *behind_last_stands (optional) is set when g.behind_last was queued behind the sweep that turned out to be the last:
@@ -518,10 +512,6 @@ static inline int run_eig_group(tadmm_handle h, const EigGroup& g, PollCtx& poll
   for (; gs < max_sweeps && !all_done; ++gs) {
     for (int t = 0; t < g.gsteps; ++t, ++tick) {
       if (super) {
-        bool any_first = false;     // does any unfinished problem start a sweep of its own at this tick?
-        for (int q = 0; q < g.neig && !any_first; ++q)
-          any_first = !known_done[q] && g.players[q] > 1 && (tick % (g.aligned ? g.gsteps : g.players[q] - 1)) == 0;
-        if (any_first) HIP_OK(h, launch_jacobi_self(g.ed, g.self_map, g.self_blocks, tick, tol, g.ld_max, s));
         const bool timed = jt && jt->on;
         if (timed) (void)hipEventRecord(jt->a, s);
         HIP_OK(h, launch_jacobi_tick3(g.ed, g.tick_map, g.tick_blocks, tick, tol, g.ld_max, s));

@@ -18,7 +18,8 @@
 //   tick3 (default, ld <= 512): a workgroup owns a *super-pair* of two 16-column super-blocks (32 columns in LDS),
 //          carries the two self-Grams from launch to launch, computes ONE cross-Gram tile, and runs 2 rounds of
 //          2 concurrent 16x16 sub-problems (see the header of jacobi_tick3_kernel); the within-super-block
-//          pairs are rotated once per sweep by tick1 in "self mode", which also refreshes the carried Grams;
+//          pairs are rotated on the first tick of a sweep, in front of that launch's cross Gram (the "self pass",
+//          which also refreshes the carried Grams from the columns);
 //   tick1 (fallback, ld > 512): a workgroup owns one pair (16 columns), LDS resident up to ld = 1152
 //          (jacobi_tick_kernel), streamed through the LDS in chunks beyond (jacobi_tick_stream_kernel);
 //   small (Npad <= 64): the whole eigen-solve in one launch, one workgroup per problem (jacobi_small_kernel).
@@ -79,6 +80,14 @@ __device__ __forceinline__ void rr_pair(int nb, int step, int q, int& a, int& b)
 // written by some lanes is visible to the other lanes of the same wave at the next instruction; the
 // fence only stops the compiler from caching LDS values in registers / reordering across it.
 __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+// Workgroup barrier that orders LDS traffic only (as in chol.hip): __syncthreads() also waits for the wave's outstanding
+// global stores, which is what the tail of tick3 wants to keep in flight.
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 // Scratch of one pair visit (all in LDS)
 struct PairScratch {
@@ -351,10 +360,30 @@ struct TickPos {
     }
     return false;
   }
+  // The same rule on words the caller has loaded itself (`state`), so that they travel with its column loads instead of
+  // forming two dependent trips in front of them: the flag, the slot of the previous sweep (only looked at on step 0;
+  // off[1] on the very first tick, never used) and the scale off[2], which jacobi_init writes and no tick ever does.
+  struct State { int done; double prev, hmax; };
+  __device__ __forceinline__ State state(const EigDesc& d) const {
+    return State{*gp(d.done), gp(d.off)[(sweep - 1) & 1], gp(d.off)[2]};
+  }
+  __device__ __forceinline__ bool retired(const EigDesc& d, const State& s, double tol, bool leader) const {
+    if (s.done) return true;
+    if (step == 0 && sweep > 0 && s.prev < tol) {
+      if (leader) *gp(d.done) = 1;
+      return true;
+    }
+    return false;
+  }
+  // A convergence measure of this sweep goes into its slot (values are >= 0: their bit patterns order like the numbers).
+  __device__ __forceinline__ void record(const EigDesc& d, double mx) const {
+    __hip_atomic_fetch_max(gp(reinterpret_cast<unsigned long long*>(&d.off[sweep & 1])),
+                           (unsigned long long)__double_as_longlong(mx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   // Last step of a sweep: clear the slot of the NEXT sweep.  Called behind a barrier, when every thread of the
   // workgroup has taken its `retired` decision.
   __device__ __forceinline__ void clear_next(const EigDesc& d, bool leader) const {
-    if (step == steps - 1 && leader) d.off[(sweep + 1) & 1] = 0.0;
+    if (step == steps - 1 && leader) gp(d.off)[(sweep + 1) & 1] = 0.0;
   }
 };
 
@@ -395,6 +424,8 @@ __device__ __forceinline__ void dma_load_slab(double* Xs, int ldp, const SlabCol
 //   Slab:        back into the slab, in place (a tile is touched by one wave only);
 //   Global:      to the global column image g (16 lanes write 128 contiguous bytes of one column);
 //   GlobalAgent: the same as relaxed agent-scope stores (tick3: straight from the accumulators to HBM).
+// Both global forms store through gp(): a flat store would also count on lgkmcnt and stand in the way of every LDS wait
+// behind it.
 enum class QDst { Slab, Global, GlobalAgent };
 template <bool kQt, QDst kDst>
 __device__ __forceinline__ void apply_q_tiles(double* Xs, int ldp, int ncol, const double (*Q)[kHP], int u, int v, int wi,
@@ -410,6 +441,7 @@ __device__ __forceinline__ void apply_q_tiles(double* Xs, int ldp, int ncol, con
     rowk[t] = row * ldp;
     growk[t] = (kDst == QDst::Slab) ? 0 : g.at(row);
   }
+  G<double>* xt = gp(g.XT);
   const int ntile = ncol >> 4;
   for (int it = wi; it < ntile; it += nw) {
     const int col = it * 16 + r;
@@ -419,34 +451,31 @@ __device__ __forceinline__ void apply_q_tiles(double* Xs, int ldp, int ncol, con
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (kDst == QDst::Slab) Xs[rowk[e] + col] = acc[e];
-      else if (kDst == QDst::Global) g.XT[growk[e] + col] = acc[e];
-      else __hip_atomic_store(g.XT + growk[e] + col, acc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else if (kDst == QDst::Global) xt[growk[e] + col] = acc[e];
+      else __hip_atomic_store(xt + growk[e] + col, acc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
 
 // Dynamic LDS layout of tick1 (doubles): X[16][ldp] | PairScratch
 __global__ __launch_bounds__(256) void jacobi_tick_kernel(const EigDesc* __restrict__ descs,
-                                                          const BlockRef* __restrict__ map, int tick, double tol,
-                                                          int self_mode) {
-  // self_mode: companion of jacobi_tick3_kernel.  The tournament runs over nb/2 super-blocks of 16
-  // columns; this kernel acts only on the first tick of a sweep, one workgroup per super-block, and
-  // rotates all 120 index pairs inside it (blocks 2*local and 2*local+1, `within` rotations included).
+                                                          const BlockRef* __restrict__ map, int tick, double tol) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const BlockRef br = map[blockIdx.x];
   const EigDesc d = descs[br.prob];
-  const TickPos pos(tick, self_mode ? (d.nb >> 1) : d.nb, self_mode ? d.period : 0);
+  const TickPos pos(tick, d.nb, 0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool leader = br.local == 0 && tid == 0;
-  if (pos.retired(d, tol, leader)) return;
-  if (self_mode && pos.step != 0) return;
+  // one trip for the words of the convergence rule and the scale of the solve.  A retired workgroup leaves before the
+  // columns are asked for: up to 144 KiB of them, which the sweeps of a group's slower problems would load for nothing
+  const TickPos::State st = pos.state(d);
+  if (pos.retired(d, st, tol, leader)) return;
   const int ld = d.ld, ldp = ld + 2;
   double* Xs = smem;
   const PairScratch S = carve_scratch(Xs + kPair * ldp);
 
   int ba, bb;
-  if (self_mode) { ba = 2 * br.local; bb = ba + 1; }
-  else rr_pair(d.nb, pos.step, br.local, ba, bb);
+  rr_pair(d.nb, pos.step, br.local, ba, bb);
   const int r = lane & 15, q = lane >> 4;
   const SlabCols cols{d.XT, ld, ba, bb, kJB, 0};
 
@@ -454,8 +483,7 @@ __global__ __launch_bounds__(256) void jacobi_tick_kernel(const EigDesc* __restr
   dma_load_slab(Xs, ldp, cols, ld, wave, 4, lane);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-  // (in self mode the tick3 launch of the same tick clears the next sweep's slot)
-  if (!self_mode) pos.clear_next(d, leader);
+  pos.clear_next(d, leader);
 
   // ---- 1. H = Xp^T Xp, a quarter of the rows per wave ----
   const int per = ld >> 2;                         // ld is a multiple of 128 -> per % 8 == 0
@@ -467,10 +495,8 @@ __global__ __launch_bounds__(256) void jacobi_tick_kernel(const EigDesc* __restr
   __syncthreads();
   // ---- 2. the 16x16 rotation ----
   if (wave == 0) {
-    double* hcur = (self_mode && d.sblk) ? d.sblk + (int64_t)br.local * (kPair * kPair) : nullptr;
-    const double mx = pair_inner_solve_fast(S, lane, d.off[2], tol, pos.step == 0, hcur);
-    if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned long long*>(&d.off[pos.sweep & 1]), (unsigned long long)__double_as_longlong(mx));
+    const double mx = pair_inner_solve_fast(S, lane, st.hmax, tol, pos.step == 0);
+    if (lane == 0) pos.record(d, mx);
   }
   __syncthreads();
   if (!*S.rotated) return;
@@ -482,7 +508,7 @@ __global__ __launch_bounds__(256) void jacobi_tick_kernel(const EigDesc* __restr
 // ------------------------------------------------------------------------------------------------
 // tick1, streamed: the pair kernel for problems whose 16 columns do not fit the LDS (ld > 1152: the
 // 4096-wide classifier layers of the VGG tables).  Same tournament, same inner solve, same descriptors
-// and block map as jacobi_tick_kernel (self_mode = 0); the columns pass through the LDS in chunks of
+// and block map as jacobi_tick_kernel; the columns pass through the LDS in chunks of
 // kStreamChunk rows twice -- once for H = Xp^T Xp (the four waves keep their partial tiles in
 // registers across chunks), once for Xp <- Xp Q (second read mostly from L2 / Infinity Cache).
 // A chunk is 128 KiB per workgroup, every piece of a wave in flight at once: the pass is bound by what one CU pulls
@@ -554,16 +580,20 @@ __global__ __launch_bounds__(256) void jacobi_tick_stream_kernel(const EigDesc* 
 // tick3: super-pair kernel with carried self-Grams.
 //
 // Every 16-column super-block b carries its 16x16 self-Gram S_b = X_b^T X_b in global memory (EigDesc::sblk,
-// refreshed exactly once per sweep by the self kernel).  A launch on the super-pair (A, B) then needs only the
+// refreshed exactly once per sweep: on the first tick of a sweep every super-block sits in exactly one workgroup, and
+// each half of that workgroup first forms the Gram of its own 16 columns over all rows, rotates the 120 index pairs
+// inside them -- the only place where the pairs inside an 8-column block meet -- updates its slab rows and keeps the
+// Gram of the rotated columns as S_b: the "self pass").  A launch on the super-pair (A, B) then needs only the
 // CROSS Gram C = X_A^T X_B -- one 16x16 MFMA tile accumulated over all rows (128 MFMAs instead of the 512 of
 // four sub-pair Grams) -- to assemble the full 32x32 Gram  H32 = [S_A C; C^T S_B]  in LDS.  Both rounds of
 // sub-pair solves work on 16x16 sub-blocks of H32; between the rounds H32 is transformed by the round-1
 // rotations (H32 <- Q1^T H32 Q1, small LDS arithmetic), so the round-2 solves do NOT need the updated columns:
 // they run on waves 0 and 4 WHILE the other six waves apply Q1 to the 32 columns on the matrix cores.
-// Critical path per launch: load -> cross Gram -> solve 1 -> solve 2 (|| apply 1) -> apply 2 -> store.
+// Critical path per launch: load (columns, convergence words and carried Grams in one trip) -> [self pass] ->
+// cross Gram -> solve 1 -> solve 2 (|| apply 1) -> apply 2 -> store (|| last transform of H32, carried Grams).
 //
-// Dynamic LDS (doubles): X[32][ldp] | R[2048] (cross-Gram partials, then H32[32][34]) |
-//                        per half: H[16][18] Q1[16][18] Q2[16][18] | flags
+// Dynamic LDS (doubles): X[32][ldp] | R[2048] (self-Gram partials of the two halves, cross-Gram partials, then
+//                        H32[32][34]) | per half: H[16][18] Q1[16][18] Q2[16][18] | flags
 // ------------------------------------------------------------------------------------------------
 constexpr int kH32 = kSuper + 2;    // leading dimension of the 32x32 LDS image
 
@@ -596,7 +626,8 @@ __device__ __forceinline__ double pair_measure_h32(const double (*H32)[kH32], in
 // In the permuted coordinates [idx_a | idx_b] Q is block diagonal, so each of the two products is four
 // independent 16x16x16 tile products: waves 0-3 take one tile each (4 MFMAs), operands straight from LDS.
 // Qa / Qb are passed TRANSPOSED (Qt[a][b] = Q[b][a]).
-template <int ua, int va, int ub, int vb>
+// kLdsBarriers: the two barriers order LDS traffic only (global stores of the caller stay in flight across them).
+template <int ua, int va, int ub, int vb, bool kLdsBarriers = false>
 __device__ __forceinline__ void transform_h32(double (*H32)[kH32], const double (*Qa)[kHP], const double (*Qb)[kHP],
                                               int tid) {
   const int lane = tid & 63, wave = tid >> 6;
@@ -616,12 +647,12 @@ __device__ __forceinline__ void transform_h32(double (*H32)[kH32], const double 
 #pragma unroll
     for (int t = 0; t < 4; ++t) out = __builtin_amdgcn_mfma_f64_16x16x4f64(QI[r][4 * t + kq], acc[t], out, 0, 0, 0);
   }
-  __syncthreads();                   // every tile has been read before any is overwritten
+  if (kLdsBarriers) lds_barrier(); else __syncthreads();     // every tile has been read before any is overwritten
   if (wave < 4) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) H32[idx(I, kq + 4 * e)][idx(J, r)] = out[e];
   }
-  __syncthreads();
+  if (kLdsBarriers) lds_barrier(); else __syncthreads();
 }
 
 __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __restrict__ descs,
@@ -631,6 +662,7 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
   const EigDesc d = descs[br.prob];
   const TickPos pos(tick, d.nb >> 1, d.period);
   if (pos.step >= pos.steps) return;             // idle tick of the group's schedule (this problem has fewer players)
+  const bool first = pos.step == 0;              // first tick of a sweep: the self pass runs in here
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = wave >> 2, wv = wave & 3, th = tid & 255;
   const bool leader = br.local == 0 && tid == 0;
@@ -648,26 +680,51 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
   double (*Q2)[kHP] = Q1 + kPair;
   double (*Q1o)[kHP] = reinterpret_cast<double (*)[kHP]>(R + 2048 + (1 - half) * (3 * kPair * kHP)) + kPair;
   double (*Q2o)[kHP] = Q1o + kPair;
-  int* flags = reinterpret_cast<int*>(R + 2048 + 2 * (3 * kPair * kHP));   // [0..1] rotated round 1, [2..3] round 2
+  int* flags = reinterpret_cast<int*>(R + 2048 + 2 * (3 * kPair * kHP));   // rotated: [0..1] round 1, [2..3] round 2,
+                                                                           // [4..5] self pass
 
   int sa, sb;
   rr_pair(d.nb >> 1, pos.step, br.local, sa, sb);
   const int r = lane & 15, q = lane >> 4;
   const SlabCols cols{d.XT, ld, sa, sb, kPair, 0};
+  G<double>* sblk = gp(d.sblk) + (int64_t)(tid < 256 ? sa : sb) * (kPair * kPair) + th;
 
-  // ---- load the 32 columns: issued before the convergence flags are even read, their load latency hides behind the
-  // columns' ----
+  // ---- one trip to memory: the 32 columns, the words the convergence rule looks at, the scale of the solves and this
+  // thread's element of the two carried self-Grams (which the first tick of a sweep computes itself) ----
   dma_load_slab(Xs, ldp, cols, ld, wave, 8, lane);
-  if (pos.retired(d, tol, leader)) {
-    __builtin_amdgcn_s_waitcnt(0);                    // no DMA may still target this workgroup's LDS at exit
-    return;
-  }
-  // the two carried self-Grams go to registers
-  const double sreg = d.sblk[(int64_t)(tid < 256 ? sa : sb) * (kPair * kPair) + th];
-  __builtin_amdgcn_s_waitcnt(0);
+  const TickPos::State st = pos.state(d);
+  double sreg = first ? 0.0 : *sblk;
+  __builtin_amdgcn_s_waitcnt(0);                      // also for a retired workgroup: no DMA may target its LDS at exit
+  if (pos.retired(d, st, tol, leader)) return;
   __syncthreads();
   STAMP(0, t0);
   pos.clear_next(d, leader);
+  const double hmax = st.hmax;
+
+  // ---- first tick of a sweep: every super-block is in exactly one workgroup, so half 0 rotates the 120 index pairs
+  // inside super-block sa and half 1 those inside sb (`within` rotations included), from the Gram of its 16 columns over
+  // all rows; the Gram of the rotated columns is the carried self-Gram of this sweep ----
+  if (first) {
+    PairScratch S;
+    S.red = R + half * 1024; S.H = Hs; S.Q = Q1; S.rotated = flags + 4 + half;
+    double* hcur = &Q2[0][0];                                      // 256 of its 288 doubles
+    const int per = ld >> 2;                                       // ld is a multiple of 128 -> per % 8 == 0
+    GramAcc h;
+    h.add(Xs + (half * kPair + r) * ldp, wv * per, (wv + 1) * per, q);
+    h.store_partial(S.red + wv * 256, lane);
+    __syncthreads();
+    pair_gram_reduce(S, th);
+    __syncthreads();
+    if (wv == half) {
+      const double mx = pair_inner_solve_fast(S, lane, hmax, tol, true, hcur);
+      if (lane == 0) pos.record(d, mx);
+    }
+    __syncthreads();
+    sreg = hcur[th];
+    if (flags[4 + half]) apply_q_tiles<false, QDst::Slab>(Xs, ldp, ld, Q1, 2 * half, 2 * half + 1, wv, 4, lane);
+    __syncthreads();
+    STAMP(6, t0);
+  }
 
   // ---- cross Gram C = X_A^T X_B : every wave reduces ld/8 rows ----
   {
@@ -703,7 +760,6 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
   __syncthreads();
   STAMP(1, t0);
 
-  const double hmax = d.off[2];
   double mxall = 0.0;
   const int mwave = (half + 2) & 3;                                 // the measuring wave of this half
   // ---- round 1: (0,2) | (1,3) ----
@@ -748,25 +804,28 @@ __global__ __launch_bounds__(512) void jacobi_tick3_kernel(const EigDesc* __rest
   }
   __syncthreads();
   STAMP(4, t0);
-  // ---- final self-Grams, then the round-2 column update straight from the MFMA accumulators to HBM ----
-  if (wv == mwave && lane == 0)
-    atomicMax(reinterpret_cast<unsigned long long*>(&d.off[pos.sweep & 1]), (unsigned long long)__double_as_longlong(mxall));
-  const int any_rot = flags[0] | flags[1] | flags[2] | flags[3];
-  if (!any_rot) return;
-  {
-    double (*Qa)[kHP] = half ? Q2o : Q2;       // (0,3)
-    double (*Qb)[kHP] = half ? Q2 : Q2o;       // (1,2)
-    transform_h32<0, 3, 1, 2>(H32, Qa, Qb, tid);
+  // ---- the round-2 column update straight from the MFMA accumulators to HBM, then the final self-Grams ----
+  if (wv == mwave && lane == 0) pos.record(d, mxall);
+  const int any_rot = flags[0] | flags[1] | flags[2] | flags[3] | (first ? flags[4] | flags[5] : 0);
+  if (!any_rot) {
+    if (first) *sblk = sreg;     // the columns stay as they are; their fresh self-Grams start the sweep
+    return;
   }
-  STAMP(5, t0);
-  d.sblk[(int64_t)(tid < 256 ? sa : sb) * (kPair * kPair) + th] =
-      (tid < 256) ? H32[th >> 4][th & 15] : H32[kPair + (th >> 4)][kPair + (th & 15)];
   {
     // the two halves' round-2 sub-pairs (0,3) and (1,2) cover all 32 columns; a sub-pair that was not rotated
-    // in round 2 has Q2 = I and the product is an exact copy of what round 1 left in LDS
+    // in round 2 has Q2 = I and the product is an exact copy of what the self pass and round 1 left in LDS.
+    // Issued first: the update reads the slab and Q2 only, and its stores are the longest latency left in the launch
     const int u = half ? 1 : 0, v = half ? 2 : 3;
     apply_q_tiles<true, QDst::GlobalAgent>(Xs, ldp, ld, Q2, u, v, wv, 4, lane, cols);
   }
+  STAMP(5, t0);
+  {
+    // behind LDS-only barriers, so that no wave waits for its column stores before the last of them
+    double (*Qa)[kHP] = half ? Q2o : Q2;       // (0,3)
+    double (*Qb)[kHP] = half ? Q2 : Q2o;       // (1,2)
+    transform_h32<0, 3, 1, 2, true>(H32, Qa, Qb, tid);
+  }
+  *sblk = (tid < 256) ? H32[th >> 4][th & 15] : H32[kPair + (th >> 4)][kPair + (th & 15)];
   STAMP(20, t0);
 }
 
@@ -950,11 +1009,12 @@ void dump_stamps() {
   unsigned long long h[32];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps), sizeof h) != hipSuccess) return;
   const double n = h[31] ? (double)h[31] : 1.0;
-  // slots 10..12: cumulative inside pair_inner_solve_fast (after the measure, the cross pairs, the end); 0..5, 20: tick3
+  // slots 10..12: cumulative inside pair_inner_solve_fast (after the measure, the cross pairs, the end); 0..6, 20: tick3
+  // (6: end of the self pass, summed over the first ticks of the sweeps only)
   fprintf(stderr, "[stampsS] per launch (2 solves): preamble=%.0f loop=%.0f epilogue=%.0f\n", h[10] / n, (h[11] - h[10]) / n,
           (h[12] - h[11]) / n);
-  fprintf(stderr, "[stamps3] launches=%llu cumulative: load=%.0f gram=%.0f solve1=%.0f xform=%.0f solve2||apply1=%.0f apply2+xform=%.0f end=%.0f\n",
-          h[31], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[5] / n, h[20] / n);
+  fprintf(stderr, "[stamps3] launches=%llu cumulative: load=%.0f self(sum/launches)=%.0f gram=%.0f solve1=%.0f xform=%.0f solve2||apply1=%.0f apply2=%.0f end=%.0f\n",
+          h[31], h[0] / n, h[6] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[5] / n, h[20] / n);
 }
 #else
 void dump_stamps() {}
@@ -1106,7 +1166,7 @@ size_t jacobi_tick_stream_lds_bytes() { return ((size_t)kPair * (kStreamChunk + 
 bool jacobi_size_supported(int n) { return n >= 1 && n <= kJacobiMaxN; }
 size_t jacobi_tick_lds_bytes(int ld_max) { return ((size_t)kPair * (ld_max + 2) + kPairScratchDoubles) * 8; }
 size_t jacobi_tick3_lds_bytes(int ld_max) {
-  return ((size_t)kSuper * (ld_max + 2) + 2048 + 2 * (3 * kPair * kHP)) * 8 + 16;
+  return ((size_t)kSuper * (ld_max + 2) + 2048 + 2 * (3 * kPair * kHP)) * 8 + 32;
 }
 bool jacobi_tick3_fits(int ld_max) { return jacobi_tick3_lds_bytes(ld_max) <= 160 * 1024; }
 hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
@@ -1124,18 +1184,6 @@ hipError_t launch_jacobi_tick3(const EigDesc* descs_dev, const BlockRef* map_dev
   return hipSuccess;
 }
 
-static DynLdsOptIn allow_tick_lds;      // jacobi_tick_kernel has two launchers: the self pass and the plain pair tick
-
-hipError_t launch_jacobi_self(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
-                              int ld_max, hipStream_t s) {
-  if (nblocks <= 0) return hipSuccess;
-  const hipError_t e = allow_tick_lds(jacobi_tick_kernel, 160 * 1024);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), jacobi_tick_lds_bytes(ld_max), s, descs_dev, map_dev,
-                     tick, tol, 1);
-  return hipSuccess;
-}
-
 hipError_t launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev, int nblocks, int tick, double tol,
                               size_t lds_bytes, hipStream_t s) {
   if (nblocks <= 0) return hipSuccess;
@@ -1146,8 +1194,9 @@ hipError_t launch_jacobi_tick(const EigDesc* descs_dev, const BlockRef* map_dev,
     hipLaunchKernelGGL(jacobi_tick_stream_kernel, dim3(nblocks), dim3(256), jacobi_tick_stream_lds_bytes(), s, descs_dev,
                        map_dev, tick, tol);
   } else {
+    static DynLdsOptIn allow_tick_lds;
     if ((e = allow_tick_lds(jacobi_tick_kernel, 160 * 1024)) != hipSuccess) return e;
-    hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), lds_bytes, s, descs_dev, map_dev, tick, tol, 0);
+    hipLaunchKernelGGL(jacobi_tick_kernel, dim3(nblocks), dim3(256), lds_bytes, s, descs_dev, map_dev, tick, tol);
   }
   e = hipPeekAtLastError();
   if (e != hipSuccess)
