@@ -1,0 +1,9 @@
+"""Drop-in alias of the reference module `xcompression/transformer/optimization.py`: re-exports the MI355X-native
+implementation."""
+import os as _os
+import sys as _sys
+
+_sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
+from tadmm.optimization import (SCHEDULES, BertAdam, ConstantLR, WarmupConstantSchedule,  # noqa: E402,F401
+                                WarmupCosineSchedule, WarmupCosineWithHardRestartsSchedule,
+                                WarmupCosineWithWarmupRestartsSchedule, WarmupLinearSchedule, _LRSchedule)

@@ -96,6 +96,13 @@ class StiefelDesc(C.Structure):
     ]
 
 
+BERTADAM_CHUNK = 4096    # kBaChunk of csrc/bertadam.hip (checked against the library at load)
+
+
+class BertAdamDesc(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
 class DgemmTileProb(C.Structure):
     """tadmm_dgemm_tile_prob: one problem of the filter's tile product / daxpby as the filter describes it (tests)."""
     _fields_ = [
@@ -228,6 +235,15 @@ ABI = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tadmm_stiefel_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tadmm_stiefel_plan_destroy": (C.c_int, [C.c_void_p]),
+    "tadmm_bertadam_desc_bytes": (C.c_int, []),
+    "tadmm_bertadam_chunk": (C.c_int, []),
+    "tadmm_bertadam_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(BertAdamDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_bertadam_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BertAdamDesc), C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.POINTER(C.c_void_p)]),
+    "tadmm_bertadam_step": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_void_p]),
+    "tadmm_bertadam_norms": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "tadmm_bertadam_plan_destroy": (C.c_int, [C.c_void_p]),
     "tadmm_gemm_pack_bytes": (C.c_size_t, [C.c_int, C.POINTER(GemmDesc)]),
     "tadmm_gemm_pack": (C.c_int, [C.c_int, C.POINTER(GemmDesc), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "tadmm_gemm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -355,6 +371,11 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_orth_desc layout mismatch")
         if lib.tadmm_stiefel_desc_bytes() != C.sizeof(StiefelDesc):
             raise TadmmLibraryError(f"{path}: tadmm_stiefel_desc layout mismatch")
+        if lib.tadmm_bertadam_desc_bytes() != C.sizeof(BertAdamDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_bertadam_desc layout mismatch")
+        if lib.tadmm_bertadam_chunk() != BERTADAM_CHUNK:
+            raise TadmmLibraryError(f"{path}: tadmm_bertadam_chunk() = {lib.tadmm_bertadam_chunk()}, binding "
+                                    f"{BERTADAM_CHUNK}")
         if lib.tadmm_wgrad_desc_bytes() != C.sizeof(WgradDesc):
             raise TadmmLibraryError(f"{path}: tadmm_wgrad_desc layout mismatch")
         if lib.tadmm_ttm_desc_bytes() != C.sizeof(TtmDesc):

@@ -1446,6 +1446,109 @@ def stiefel_project_(*xs: torch.Tensor) -> StiefelPlan:
     return plan
 
 
+# ------------------------------------------------------------------ BertAdam (csrc/bertadam.hip)
+BERTADAM_CHUNK = _cabi.BERTADAM_CHUNK      # elements one workgroup takes at a time; a chunk never spans two tensors
+
+
+def bert_adam_native(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor) -> bool:
+    """True when (p, g, m, v) can go into a `BertAdamPlan`: float32, dense-contiguous, on one HIP device, of one shape.
+    Everything else takes `bert_adam_composed`.  Pure host logic."""
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and not t.is_sparse
+               and t.is_contiguous() and t.numel() > 0 and t.shape == p.shape and t.device == p.device
+               for t in (p, g, m, v))
+
+
+class BertAdamPlan:
+    """One set of tensors stepped together by the reference's BertAdam rule (`tadmm_bertadam_plan`): `tensors` is a list
+    of (p, g, m, v), float32 dense-contiguous device tensors of one shape each (`bert_adam_native`; 4-byte alignment is
+    enough, 16-byte aligned tensors take 16-byte accesses).  `step` is two launches for the whole list (one without
+    clipping), copies nothing and never synchronises; g is left as it was.  The table is uploaded once, here."""
+
+    def __init__(self, tensors: Sequence):
+        if not tensors:
+            raise TadmmError(-1, "BertAdamPlan: no tensors")
+        dev = tensors[0][0].device
+        if dev.type != "cuda":
+            raise TadmmError(-1, f"BertAdamPlan tensors must live on a HIP device (got {dev}); use bert_adam_composed")
+        n = len(tensors)
+        arr = (_cabi.BertAdamDesc * n)()
+        for i, (p, g, m, v) in enumerate(tensors):
+            if not bert_adam_native(p, g, m, v) or p.device != dev:
+                raise TadmmError(-1, f"BertAdamPlan tensor {i}: p, g, m and v must be float32 dense-contiguous tensors of "
+                                     f"one shape on {dev}; everything else takes bert_adam_composed")
+            arr[i].p, arr[i].g, arr[i].m, arr[i].v, arr[i].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), \
+                p.numel()
+        self.device = dev
+        self.tensors = [tuple(t) for t in tensors]
+        self._written = [t for p, _, m, v in self.tensors for t in (p, m, v)]
+        self.h = _handle(dev)
+        lib = self.h.lib
+        size = C.c_size_t()
+        self.h.check(lib.tadmm_bertadam_workspace_bytes(n, arr, C.byref(size)))
+        self.workspace = _scratch(size.value, dev)
+        plan = C.c_void_p()
+        self.h.check(lib.tadmm_bertadam_plan_create(self.h.ptr, n, arr, self.workspace.data_ptr(), int(size.value),
+                                                    _stream(dev), C.byref(plan)))
+        self._plan = plan
+        self._fin = weakref.finalize(self, lib.tadmm_bertadam_plan_destroy, plan)
+        ptr = C.c_void_p()
+        self.h.check(lib.tadmm_bertadam_norms(plan, C.byref(ptr)))
+        off = ptr.value - self.workspace.data_ptr()
+        self._norms = self.workspace[off:off + 8 * n].view(torch.float64)
+
+    def step(self, lr: float, b1: float = 0.9, b2: float = 0.999, e: float = 1e-6, weight_decay: float = 0.01,
+             max_grad_norm: float = 1.0):
+        """c = min(1, max_grad_norm / (||g|| + 1e-6)) per tensor (1 with max_grad_norm <= 0); gc = g c;
+        m <- b1 m + (1-b1) gc;  v <- b2 v + (1-b2) gc^2;  p <- p - lr (m / (sqrt(v) + e) + weight_decay p).
+        b1 or b2 outside [0, 1), e < 0 and lr < 0 are refused by the library before anything is launched."""
+        self.h.check(self.h.lib.tadmm_bertadam_step(self._plan, float(lr), float(b1), float(b2), float(e),
+                                                    float(weight_decay), float(max_grad_norm), _stream(self.device)))
+        self._touched()
+
+    def _touched(self):
+        # the launches write through raw pointers: tell autograd and the layers' inference caches (`param_key`)
+        torch.autograd.graph.increment_version(self._written)
+
+    def grad_norms(self) -> torch.Tensor:
+        """Every tensor's gradient norm as the last step with max_grad_norm > 0 computed it (zeros before the first): a
+        float64 device tensor, a view of the plan's workspace that the next such step overwrites.  No synchronisation."""
+        return self._norms
+
+
+def bert_adam_composed(ps: Sequence[torch.Tensor], gs: Sequence[torch.Tensor], ms: Sequence[torch.Tensor],
+                       vs: Sequence[torch.Tensor], lr: float, b1: float = 0.9, b2: float = 0.999, e: float = 1e-6,
+                       weight_decay: float = 0.01, max_grad_norm: float = 1.0):
+    """The arithmetic of `BertAdamPlan.step` on `torch._foreach_*` calls, in the tensors' own dtype, in place on ps, ms
+    and vs (gs untouched): the route of everything the kernel does not take (other dtypes, non-contiguous parameters,
+    CPU tensors) and its CPU-testable twin.  Returns the list of gradient norms (0-dim tensors), or None without
+    clipping.  Sparse gradients raise, as in the reference."""
+    ps, gs, ms, vs = list(ps), list(gs), list(ms), list(vs)
+    if any(g.is_sparse for g in gs):
+        raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+    if not ps:
+        return None
+    norms = None
+    with torch.no_grad():
+        if max_grad_norm > 0:
+            norms = torch._foreach_norm(gs)
+            coef = torch._foreach_add(norms, 1e-6)
+            torch._foreach_reciprocal_(coef)
+            torch._foreach_mul_(coef, float(max_grad_norm))
+            torch._foreach_clamp_max_(coef, 1.0)
+            gs = torch._foreach_mul(gs, coef)
+        torch._foreach_mul_(ms, b1)
+        torch._foreach_add_(ms, gs, alpha=1.0 - b1)
+        torch._foreach_mul_(vs, b2)
+        torch._foreach_addcmul_(vs, gs, gs, value=1.0 - b2)
+        upd = torch._foreach_sqrt(vs)
+        torch._foreach_add_(upd, e)
+        upd = torch._foreach_div(ms, upd)
+        if weight_decay > 0:
+            torch._foreach_add_(upd, ps, alpha=weight_decay)
+        torch._foreach_add_(ps, upd, alpha=-lr)
+    return norms
+
+
 # ------------------------------------------------------------------ gathered TT-matrix chain (csrc/ttm_gather.hip)
 TTM_MAX_D = _cabi.TTM_MAX_D
 TTM_LDS_BYTES = 160 * 1024

@@ -272,6 +272,50 @@ int tadmm_stiefel_adam_step(tadmm_stiefel_plan p, double lr, double beta1, doubl
 int tadmm_stiefel_project(tadmm_stiefel_plan p, int32_t* status_dev, void* stream);
 int tadmm_stiefel_plan_destroy(tadmm_stiefel_plan p);
 
+/* ---- BertAdam (xcompression/transformer/optimization.py:183-302) -------------------------------------------------
+ * The optimiser of the reference's BERT training scripts, for ALL n tensors of a param group in two launches
+ * (csrc/bertadam.hip).  Every tensor is float32, dense-contiguous, n elements, its four pointers 4-byte aligned; tensors
+ * whose four pointers are 16-byte aligned take 16-byte accesses, the others single elements (chosen per tensor).
+ * Work is cut into chunks of tadmm_bertadam_chunk() elements, a chunk never spanning two tensors.  With
+ * max_grad_norm > 0 a first launch stores each chunk's sum of g^2 (double) into the workspace; the update launch adds a
+ * tensor's partial sums in a fixed order that depends on the tensor alone (every chunk of it sees the same bits) and forms
+ *   norm = sqrt(sum g^2),   c = (float) min(1, max_grad_norm / (norm + 1e-6))          (c = 1 with max_grad_norm <= 0)
+ * then per element, in float32, each operation rounded on its own:
+ *   gc = g c;   m <- b1 m + (1 - b1) gc;   v <- b2 v + (1 - b2) gc gc
+ *   u = m / (sqrtf(v) + e);   u += weight_decay p  (only with weight_decay > 0);   p <- p - lr u
+ * There is no bias correction; lr is the caller's scheduled rate.  g is read only (the reference scales .grad in place,
+ * this does not).  Non-finite gradients follow IEEE as in the reference: an inf element gives norm = inf, c = 0 and a NaN
+ * at that element only; there is no skipping and no status word.  No atomics, no inter-workgroup waiting: results are
+ * bitwise reproducible.
+ * tadmm_bertadam_workspace_bytes / _plan_create return TADMM_ERR_INVALID, with nothing launched, for n <= 0, a null or
+ * misaligned (not 4-byte) pointer and a tensor with n <= 0; _plan_create returns TADMM_ERR_WORKSPACE for a workspace
+ * that is null or too small and TADMM_ERR_INVALID for one that is not 16-byte aligned.  The plan uploads its table and
+ * chunk map once, ordered on `stream` (the call waits for the copy), and clears the norms; the pointers of the
+ * descriptors and the workspace must stay valid for the life of the plan.
+ * tadmm_bertadam_step copies nothing and synchronises nothing; it returns TADMM_ERR_INVALID, with nothing launched, for a
+ * NULL plan, b1 or b2 outside [0, 1), e < 0 and lr < 0 (NaN included).
+ * tadmm_bertadam_norms hands out the device array of n doubles holding every tensor's gradient norm as the last step
+ * with max_grad_norm > 0 computed it (zeros before the first); it lives in the workspace. */
+typedef struct {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+} tadmm_bertadam_desc;
+typedef struct tadmm_bertadam_plan_s* tadmm_bertadam_plan;
+/* sizeof(tadmm_bertadam_desc) as the library was built */
+int tadmm_bertadam_desc_bytes(void);
+/* elements per chunk (one workgroup's unit of work; a multiple of 4) */
+int tadmm_bertadam_chunk(void);
+int tadmm_bertadam_workspace_bytes(int n, const tadmm_bertadam_desc* descs, size_t* bytes);
+int tadmm_bertadam_plan_create(tadmm_handle h, int n, const tadmm_bertadam_desc* descs, void* workspace,
+                               size_t workspace_bytes, void* stream, tadmm_bertadam_plan* out);
+int tadmm_bertadam_step(tadmm_bertadam_plan p, double lr, double b1, double b2, double e, double weight_decay,
+                        double max_grad_norm, void* stream);
+int tadmm_bertadam_norms(tadmm_bertadam_plan p, double** norms_dev);
+int tadmm_bertadam_plan_destroy(tadmm_bertadam_plan p);
+
 /* ---- building blocks (also used by the factorised layers) -------------- */
 /* C[i,j] = alpha * sum_k A(i,k) B(k,j) (+ beta*C) with arbitrary element strides; one of the two
  * strides of each operand must be 1.  Replaces the torch.mm / F.linear chains of
