@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, xcompression/transformer/optimization.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -29,6 +29,7 @@ def __getattr__(name):
         "TTLSTM": ("rnn_layers", "TTLSTM"),
         "DistillationLoss": ("losses", "DistillationLoss"),
         "BertAdam": ("optimization", "BertAdam"),
+        "BertSelfAttention": ("bert_layers", "BertSelfAttention"),
         "stiefel_step": ("ops", "stiefel_step"), "stiefel_project_": ("ops", "stiefel_project_"),
     }
     if name == "optimization":      # the module itself, as the reference's scripts import it

@@ -160,6 +160,21 @@ class DistillDesc(C.Structure):
     ]
 
 
+class AttnDesc(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p),
+        ("q_ld", C.c_int64), ("k_ld", C.c_int64), ("v_ld", C.c_int64),
+        ("q_bs", C.c_int64), ("k_bs", C.c_int64), ("v_bs", C.c_int64),
+        ("mask", C.c_void_p), ("keep", C.c_void_p),
+        ("ctx", C.c_void_p), ("scores", C.c_void_p), ("stats", C.c_void_p),
+        ("g_ctx", C.c_void_p), ("g_sc", C.c_void_p),
+        ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("p", C.c_double),
+        ("B", C.c_int64), ("H", C.c_int32), ("S", C.c_int32), ("d", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -285,6 +300,11 @@ ABI = {
     "tadmm_distill_desc_bytes": (C.c_int, []),
     "tadmm_distill_workspace_bytes": (C.c_int, [C.POINTER(DistillDesc), C.POINTER(C.c_size_t)]),
     "tadmm_distill_loss": (C.c_int, [C.c_void_p, C.POINTER(DistillDesc), C.c_void_p]),
+    "tadmm_attn_desc_bytes": (C.c_int, []),
+    "tadmm_attn_fits": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_attn_workspace_bytes": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_attn_fwd": (C.c_int, [C.c_void_p, C.POINTER(AttnDesc), C.c_void_p]),
+    "tadmm_attn_bwd": (C.c_int, [C.c_void_p, C.POINTER(AttnDesc), C.c_void_p]),
     "tadmm_core_conv_desc_bytes": (C.c_int, []),
     "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
     "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
@@ -384,6 +404,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_lstm_desc layout mismatch")
         if lib.tadmm_distill_desc_bytes() != C.sizeof(DistillDesc):
             raise TadmmLibraryError(f"{path}: tadmm_distill_desc layout mismatch")
+        if lib.tadmm_attn_desc_bytes() != C.sizeof(AttnDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_attn_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         if lib.tadmm_dgemm_tile_prob_bytes() != C.sizeof(DgemmTileProb):

@@ -957,3 +957,132 @@ def soft_cross_entropy(predicts: torch.Tensor, targets: torch.Tensor, temperatur
     p = predicts if predicts.dim() == 2 else predicts.reshape(-1, C)
     t = targets if targets.dim() == 2 else targets.reshape(-1, C)
     return distillation_loss(None, p, t.detach(), None, base="none", kd="soft_ce", alpha=1.0, tau=temperature, route=route)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# BERT self-attention (csrc/attn.hip): the body of compressed_modeling*.py: *BertSelfAttention.forward after the three
+# projections -- raw masked scores (a differentiable output: TinyBERT regresses them), softmax, dropout, context.
+# ---------------------------------------------------------------------------------------------------------------
+class _AttnFn(torch.autograd.Function):
+    """Two differentiable outputs; the backward recomputes P from q, k, the mask and the saved row statistics."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, keep, num_heads, p, need_scores):
+        need = any(ctx.needs_input_grad[:3])
+        ctx.set_materialize_grads(False)
+        context, scores, stats = ops.attn_fwd(q, k, v, mask, num_heads, p=p, keep=keep, need_scores=need_scores,
+                                              need_stats=need)
+        if need:
+            ctx.save_for_backward(q, k, v, stats)
+        ctx.mask, ctx.keep, ctx.cfg = mask, keep, (num_heads, p)
+        if scores is None:
+            return context
+        return context, scores
+
+    @staticmethod
+    def backward(ctx, g_ctx, g_sc=None):
+        q, k, v, stats = ctx.saved_tensors
+        num_heads, p = ctx.cfg
+        if g_ctx is None and g_sc is None:
+            return (None,) * 8
+        dq, dk, dv = ops.attn_bwd(q, k, v, ctx.mask, num_heads, stats, g_ctx, g_sc, p=p, keep=ctx.keep)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None)
+
+
+def _attn_args(q, k, v, mask, num_heads, dropout_p, who):
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{who}: {n} must be a (B, S, H*d) tensor")
+        if t.shape != q.shape or t.dtype != q.dtype or t.device != q.device:
+            raise ValueError(f"{who}: q, k and v must agree in shape, type and device")
+    if num_heads < 1 or q.shape[2] % num_heads:
+        raise ValueError(f"{who}: the hidden size ({q.shape[2]}) is not a multiple of the number of heads ({num_heads})")
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise ValueError(f"{who}: dropout_p must be in [0, 1) (got {dropout_p})")
+
+
+def attention_keep_mask(B: int, H: int, S: int, p: float, device, generator=None) -> torch.Tensor:
+    """The byte tensor (B, H, S, S) of kept probabilities of a dropout at rate p, drawn with torch's generator (so that
+    a seed reproduces a run and both routes of `self_attention` can be handed the same mask)."""
+    return (torch.rand((B, H, S, S), device=device, generator=generator) >= p).to(torch.uint8)
+
+
+def self_attention_composed(q, k, v, mask, num_heads: int, *, dropout_p: float = 0.0, training: bool = False,
+                            need_scores: bool = True, keep=None):
+    """`self_attention` as the reference composes it (compressed_modeling_tt.py:379-403) from torch operations, under
+    autograd, on any device: the route for shapes the launch refuses, masks that are not (B, 1, 1, S), masks that
+    require grad, CPU tensors and float16 training, and the yardstick of tests/test_gpu_attn.py and
+    scripts/bench_attention.py.  Dropout multiplies by `keep` / (1 - p) (drawn here when not given)."""
+    _attn_args(q, k, v, mask, num_heads, dropout_p, "self_attention_composed")
+    B, S, Hd = q.shape
+    d = Hd // num_heads
+    ql, kl, vl = (t.view(B, S, num_heads, d).permute(0, 2, 1, 3) for t in (q, k, v))
+    scores = torch.matmul(ql, kl.transpose(-1, -2))
+    scores = scores / (d ** 0.5)
+    if mask is not None:
+        scores = scores + mask
+    probs = torch.softmax(scores, dim=-1)
+    if training and dropout_p > 0.0:
+        if keep is None:
+            keep = attention_keep_mask(B, num_heads, S, dropout_p, q.device)
+        probs = probs * (keep != 0).to(probs.dtype) / (1.0 - dropout_p)
+    context = torch.matmul(probs, vl).permute(0, 2, 1, 3).contiguous().view(B, S, Hd)
+    return context, (scores if need_scores else None)
+
+
+def attention_launch_refusal(is_cuda: bool, dtype, B: int, H: int, S: int, d: int, grad: bool, mask_shape=None,
+                             mask_foreign: bool = False):
+    """None when csrc/attn.hip takes a call with these properties, else the reason it does not (a string): CPU tensors,
+    a type other than float32 / bfloat16 / float16, float16 with gradients, S or d out of range, a mask that is not
+    (B, 1, 1, S), or one that requires grad or lives elsewhere (`mask_foreign`).  A pure function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    if dtype not in ops.ATTN_DTYPES:
+        return f"{dtype} operands"
+    if dtype == torch.float16 and grad:
+        return "float16 with gradients"
+    if B < 1 or S < 1 or d < 1 or not ops.attn_fits(S, d, H, dtype):
+        return f"S = {S}, d = {d}"
+    if mask_shape is not None and tuple(mask_shape) != (B, 1, 1, S):
+        return f"a mask of shape {tuple(mask_shape)}"
+    if mask_foreign:
+        return "a mask that requires grad or lives on another device"
+    return None
+
+
+def self_attention(q, k, v, mask, num_heads: int, *, dropout_p: float = 0.0, training: bool = False,
+                   need_scores: bool = True, keep=None, route: str = None):
+    """(context, scores or None) of a BERT self-attention for projected q, k, v of shape (B, S, H*d):
+
+        scores[b,h,i,j] = (Q[b,i,h,:] . K[b,j,h,:]) / sqrt(d) + mask[b,0,0,j]
+        context[b,i,h*d:(h+1)*d] = sum_j dropout(softmax_j(scores))[b,h,i,j] V[b,j,h,:]
+
+    Both outputs are differentiable in q, k and v.  `mask`: additive, (B, 1, 1, S) or None.  Dropout acts only when
+    `training` and `dropout_p` > 0: `keep` (B, H, S, S) bytes, nonzero = kept, is drawn with torch's generator when not
+    given.  `route`: None (the launch where it takes the call and the measured rule `ops.attn_pays` says it is ahead),
+    "launch" (csrc/attn.hip: one launch forward, two backward) or "composed" (torch operations).  The launch takes HIP
+    tensors of float32 or bfloat16 (float16 without gradients), S <= 512, d <= 64, a (B, 1, 1, S) mask that requires no
+    gradient; everything else goes to the composed route under `route=None` and raises under `route="launch"`."""
+    who = "self_attention"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    _attn_args(q, k, v, mask, num_heads, dropout_p, who)
+    B, S, Hd = q.shape
+    d = Hd // num_heads
+    p = float(dropout_p) if training else 0.0
+    grad = torch.is_grad_enabled() and _needs_grad(q, k, v)
+    why = attention_launch_refusal(q.is_cuda, q.dtype, B, num_heads, S, d, grad,
+                                   None if mask is None else tuple(mask.shape),
+                                   mask is not None and (mask.requires_grad or mask.device != q.device))
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    launch = why is None and (route == "launch" or (route is None and ops.attn_pays(B, num_heads, S, d, q.dtype, grad)))
+    if not launch:
+        return self_attention_composed(q, k, v, mask, num_heads, dropout_p=dropout_p, training=training,
+                                       need_scores=need_scores, keep=keep)
+    if p > 0.0 and keep is None:
+        keep = attention_keep_mask(B, num_heads, S, p, q.device)
+    out = _AttnFn.apply(q, k, v, None if mask is None else mask.detach(), keep if p > 0.0 else None, int(num_heads), p,
+                        bool(need_scores))
+    return out if need_scores else (out, None)

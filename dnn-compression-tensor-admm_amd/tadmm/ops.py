@@ -1993,3 +1993,140 @@ def distill_loss_pays(B: int, C: int, dtype, grad: bool = False) -> bool:
     fastest in all 48 classes (2.1x - 4.2x; both routes are bound by the host at these sizes), so the rule is a
     constant.  Batches beyond 1024 rows and class counts beyond 1000 were not measured."""
     return True
+
+
+# ------------------------------------------------------------------ BERT self-attention (csrc/attn.hip)
+ATTN_DTYPES = DISTILL_DTYPES
+
+
+def attn_fits(S: int, d: int, H: int = 1, dtype=torch.float32) -> bool:
+    """True when `tadmm_attn_fwd` / `_bwd` take sequences of S tokens with heads of width d (`tadmm_attn_fits`:
+    1 <= S <= 512, 1 <= d <= 64).  Raises TadmmError for S < 1, d < 1 or H < 1.  Host only."""
+    dsc = _cabi.AttnDesc()
+    dsc.S, dsc.d, dsc.H, dsc.dtype = int(S), int(d), int(H), ATTN_DTYPES[dtype]
+    rc = _cabi.load().tadmm_attn_fits(C.byref(dsc), None)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_attn_fits: S = {S}, d = {d}, H = {H}")
+    return rc == 1
+
+
+def attn_workspace_bytes(B: int, H: int, S: int) -> int:
+    """Bytes of the backward's workspace (`tadmm_attn_workspace_bytes`: one double per query row and head)."""
+    dsc = _cabi.AttnDesc()
+    dsc.B, dsc.H, dsc.S = int(B), int(H), int(S)
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_attn_workspace_bytes(C.byref(dsc), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_attn_workspace_bytes: B = {B}, H = {H}, S = {S}")
+    return int(size.value)
+
+
+def _attn_heads(t, who, what, shape, dt):
+    """A (B, S, H*d) operand read in place by heads: unit element stride and a row stride >= H*d as it stands (a slice
+    of a packed qkv tensor), anything else as a contiguous copy.  Returns (tensor, row stride, batch stride)."""
+    t = _operand(t, who, what, (dt,), shape, layout=None)
+    B, S, Hd = t.shape
+    if (Hd > 1 and t.stride(2) != 1) or (S > 1 and t.stride(1) < Hd) or (B > 1 and t.stride(0) < 0):
+        t = t.contiguous()
+    ld = max(int(t.stride(1)), Hd) if S > 1 else Hd
+    return t, ld, (int(t.stride(0)) if B > 1 else 0)
+
+
+def _attn_desc(q, k, v, mask, num_heads, p, keep, who):
+    q = _operand(q, who, "q", tuple(ATTN_DTYPES), layout=None)
+    if q.dim() != 3 or num_heads < 1 or q.shape[2] % num_heads or q.shape[1] < 1 or q.shape[2] < 1:
+        raise TadmmError(-1, f"{who}: q must be (B, S >= 1, H*d) with H = {num_heads} (got {tuple(q.shape)})")
+    B, S, Hd = q.shape
+    H, hd = int(num_heads), Hd // int(num_heads)
+    dev, dt = q.device, q.dtype
+    dsc = _cabi.AttnDesc()
+    hold = []
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        t, ld, bs = _attn_heads(t, who, name, (B, S, Hd), dt)
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: {name} on {t.device}, q on {dev}")
+        hold.append(t)
+        setattr(dsc, name, t.data_ptr())
+        setattr(dsc, name + "_ld", ld)
+        setattr(dsc, name + "_bs", bs)
+    if mask is not None:
+        mask = _operand(mask, who, "mask", None, (B, 1, 1, S), layout=None)
+        if mask.device != dev:
+            raise TadmmError(-1, f"{who}: mask on {mask.device}, q on {dev}")
+        mask = mask.reshape(B, S).to(torch.float32).contiguous()
+        hold.append(mask)
+        dsc.mask = mask.data_ptr()
+    p = float(p)
+    if p > 0.0:
+        if keep is None:
+            raise TadmmError(-1, f"{who}: dropout p = {p} needs the keep tensor")
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        keep = _operand(keep, who, "keep", (torch.uint8,), (B, H, S, S), layout="copy")
+        if keep.device != dev:
+            raise TadmmError(-1, f"{who}: keep on {keep.device}, q on {dev}")
+        hold.append(keep)
+        dsc.keep = keep.data_ptr()
+    dsc.p = p
+    dsc.B, dsc.H, dsc.S, dsc.d, dsc.dtype = B, H, S, hd, ATTN_DTYPES[dt]
+    return dsc, hold, (B, H, S, hd, dev, dt)
+
+
+def attn_fwd(q, k, v, mask, num_heads: int, *, p: float = 0.0, keep=None, need_scores: bool = True,
+             need_stats: bool = False):
+    """(context, scores, stats) of `tadmm_attn_fwd`: q, k, v (B, S, H*d) float32, bfloat16 or float16 of one type, read in
+    place by heads (unit element stride, any row stride >= H*d: slices of a packed qkv tensor are not copied); `mask`
+    additive (B, 1, 1, S) or None; `keep` (B, H, S, S) uint8 / bool, read when p > 0.  context (B, S, H*d) and scores
+    (B, H, S, S; None unless `need_scores`) in the input type, stats float32 (B, H, S, 2) = (row maximum, row sum of
+    exp(score - maximum)) (None unless `need_stats`; the backward reads it).  One launch; nothing synchronises."""
+    who = "attn_fwd"
+    dsc, hold, (B, H, S, hd, dev, dt) = _attn_desc(q, k, v, mask, num_heads, p, keep, who)
+    ctx = torch.empty((B, S, H * hd), dtype=dt, device=dev)
+    scores = torch.empty((B, H, S, S), dtype=dt, device=dev) if need_scores else None
+    stats = torch.empty((B, H, S, 2), dtype=torch.float32, device=dev) if need_stats else None
+    dsc.ctx = ctx.data_ptr()
+    dsc.scores = None if scores is None else scores.data_ptr()
+    dsc.stats = None if stats is None else stats.data_ptr()
+    h = _handle(dev)
+    h.check(h.lib.tadmm_attn_fwd(h.ptr, C.byref(dsc), _stream(dev)))
+    return ctx, scores, stats
+
+
+def attn_bwd(q, k, v, mask, num_heads: int, stats, g_ctx, g_sc, *, p: float = 0.0, keep=None):
+    """(dq, dk, dv) of `tadmm_attn_bwd` for the upstream gradients `g_ctx` (of the context) and `g_sc` (of the scores),
+    either None: float32 or bfloat16 (float16 is refused), each (B, S, H*d) contiguous in the input type.  P is
+    recomputed from q, k, the mask and `stats` (float32 (B, H, S, 2), from `attn_fwd(need_stats=True)`).  Two launches, no
+    atomics, bitwise reproducible; nothing synchronises."""
+    who = "attn_bwd"
+    dsc, hold, (B, H, S, hd, dev, dt) = _attn_desc(q, k, v, mask, num_heads, p, keep, who)
+    stats = _operand(stats, who, "stats", (torch.float32,), (B, H, S, 2), layout="copy")
+    dsc.stats = stats.data_ptr()
+    if g_ctx is not None:
+        g_ctx = _operand(g_ctx, who, "g_ctx", (dt,), (B, S, H * hd), layout="copy")
+        dsc.g_ctx = g_ctx.data_ptr()
+        nbytes = attn_workspace_bytes(B, H, S)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    if g_sc is not None:
+        g_sc = _operand(g_sc, who, "g_sc", (dt,), (B, H, S, S), layout="copy")
+        dsc.g_sc = g_sc.data_ptr()
+    out = torch.empty((3, B, S, H * hd), dtype=dt, device=dev)
+    dsc.dq, dsc.dk, dsc.dv = out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr()
+    h = _handle(dev)
+    h.check(h.lib.tadmm_attn_bwd(h.ptr, C.byref(dsc), _stream(dev)))
+    return out[0], out[1], out[2]
+
+
+def attn_pays(B: int, H: int, S: int, d: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.self_attention` sends a call the launch can take to it and not to the composed torch route.
+    A pure function of its arguments.  Measured (scripts/bench_attention.py) at H = 12, d = 64,
+    B in {1, 8, 32}, S in {64, 128, 384, 512}, float32 and bfloat16, forward with and without the scores output and a
+    training step with gradients into both outputs, against `self_attention_composed` in the same run.  At S = 64 and
+    128 the launch's slowest window is below the composed route's fastest in all 36 classes (forward 1.4x - 3.8x, training
+    step 1.5x - 4.2x; the composed route is bound by the host's nine launches there).  At S = 384 and 512 the composed
+    route is ahead in 32 of 36 classes (the launch at 0.47x - 0.88x of it), two are level and two go to the launch
+    (B = 1, S = 384: bfloat16 training 1.23x): the launch computes the score product twice and stages its tiles with
+    element loads, which the batched BLAS products of the composed route do not.  So the rule is the sequence length alone: the launch up to 128
+    tokens, the composed route beyond.  Not measured: lengths between 129 and 383 (sent to the composed route), head
+    widths other than 64, head counts other than 12, float16, dropout on."""
+    return S <= 128

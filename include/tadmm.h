@@ -679,6 +679,58 @@ int tadmm_distill_desc_bytes(void);
 int tadmm_distill_workspace_bytes(const tadmm_distill_desc* d, size_t* bytes);
 int tadmm_distill_loss(tadmm_handle h, const tadmm_distill_desc* d, void* stream);
 
+/* ---- BERT self-attention: scores, softmax, dropout mask and context in one launch (csrc/attn.hip) -------------------
+ * The body of xcompression/transformer/compressed_modeling*.py: *BertSelfAttention.forward after the projections.
+ * q, k, v: (B, S, H*d) of `dtype`, read in place by heads: unit element stride, row strides q_ld / k_ld / v_ld >= H*d and
+ * batch strides q_bs / k_bs / v_bs in elements (a slice of a packed (B, S, 3*H*d) tensor has ld = 3*H*d, bs = S*3*H*d),
+ * any element-aligned base.
+ *   scores[b,h,i,j] = (Q[b,i,h,:] . K[b,j,h,:]) / sqrt(d) + mask[b,j]      mask: float32 (B, S), nullable (zeros);
+ *                                                                           -inf allowed in rows that keep a finite entry
+ *   P = softmax_j(scores);  Pd = P * (keep != 0) / (1 - p)                  keep: bytes (B, H, S, S), read when p > 0
+ *   ctx[b,i,h*d:(h+1)*d] = sum_j Pd[b,h,i,j] V[b,j,h,:]                     ctx: (B, S, H*d) contiguous, of `dtype`
+ * tadmm_attn_fwd writes ctx, scores ((B, H, S, S) contiguous, of `dtype`; nullable: not written) and stats (float32
+ * (B, H, S, 2): m = the row maximum and l = sum_j exp(score - m), so that lse = m + log l; nullable).  One launch.
+ * tadmm_attn_bwd reads q, k, v, mask, keep, stats and the upstream gradients g_ctx (of ctx) and g_sc (of scores), both
+ * contiguous, of `dtype`, each nullable (zeros), and writes dq, dk, dv ((B, S, H*d) contiguous, of `dtype`):
+ *   dPd = (g_ctx V^T) keep / (1-p),  D_i = sum_j P_ij dPd_ij,  dS = g_sc + P (dPd - D)
+ *   dQ = dS K / sqrt(d),  dK = dS^T Q / sqrt(d),  dV = Pd^T g_ctx
+ * with P recomputed from q, k, mask and stats as exp(s - m) / l, the forward's own expression (a single rounded lse
+ * would cost float32 parity).  Two launches (query-row blocks: D and dQ; key blocks: dK and dV); the
+ * workspace (tadmm_attn_workspace_bytes: one double per (b, h, i), rounded up to 256 bytes; 8-byte aligned) carries D
+ * from the first to the second and is needed when g_ctx is given.  No atomics; bitwise reproducible; no host
+ * synchronisation.  float32 products are exact (v_mfma_f32_16x16x4_f32); the 16-bit types use
+ * v_mfma_f32_16x16x32_{bf16,f16} with float32 accumulation; the softmax is float32.
+ * tadmm_attn_fits is host only and reads H, S, d and dtype: 1 when the launches take the shape (1 <= S <= 512,
+ * 1 <= d <= 64), 0 when not, TADMM_ERR_INVALID for a NULL descriptor or S < 1, d < 1, H < 1.  *lds_bytes (nullable): the
+ * static LDS of the larger launch.  The launches return TADMM_ERR_UNSUPPORTED where _fits returns 0 and
+ * TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or descriptor; an unknown dtype; TADMM_CHAIN_F16 in _bwd;
+ * q, k, v NULL or not element aligned; a row stride below H*d; any other pointer not aligned to its element; p outside
+ * [0, 1); p > 0 without keep; ctx NULL (_fwd); stats, dq, dk or dv NULL (_bwd).  TADMM_ERR_WORKSPACE: g_ctx given and the
+ * workspace NULL, misaligned or short.  B == 0 succeeds and launches nothing. */
+typedef struct {
+  const void* q; const void* k; const void* v;
+  int64_t q_ld, k_ld, v_ld;                   /* row strides, elements */
+  int64_t q_bs, k_bs, v_bs;                   /* batch strides, elements */
+  const float* mask;                          /* (B, S); nullable */
+  const uint8_t* keep;                        /* (B, H, S, S); required when p > 0 */
+  void* ctx;                                  /* forward */
+  void* scores;                               /* forward; nullable */
+  float* stats;                               /* forward writes it (nullable), backward reads it */
+  const void* g_ctx; const void* g_sc;        /* backward; each nullable */
+  void* dq; void* dk; void* dv;               /* backward */
+  void* workspace; size_t workspace_bytes;    /* backward with g_ctx */
+  double p;                                   /* dropout probability, [0, 1) */
+  int64_t B;
+  int32_t H, S, d;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (forward only) */
+} tadmm_attn_desc;
+/* sizeof(tadmm_attn_desc) as the library was built */
+int tadmm_attn_desc_bytes(void);
+int tadmm_attn_fits(const tadmm_attn_desc* d, size_t* lds_bytes);
+int tadmm_attn_workspace_bytes(const tadmm_attn_desc* d, size_t* bytes);
+int tadmm_attn_fwd(tadmm_handle h, const tadmm_attn_desc* d, void* stream);
+int tadmm_attn_bwd(tadmm_handle h, const tadmm_attn_desc* d, void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
