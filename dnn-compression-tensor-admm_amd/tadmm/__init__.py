@@ -30,6 +30,11 @@ def __getattr__(name):
         "DistillationLoss": ("losses", "DistillationLoss"),
         "BertAdam": ("optimization", "BertAdam"),
         "BertSelfAttention": ("bert_layers", "BertSelfAttention"),
+        "BertLayerNorm": ("bert_layers", "BertLayerNorm"), "BertSelfOutput": ("bert_layers", "BertSelfOutput"),
+        "BertIntermediate": ("bert_layers", "BertIntermediate"), "BertOutput": ("bert_layers", "BertOutput"),
+        "BertAttention": ("bert_layers", "BertAttention"), "BertLayer": ("bert_layers", "BertLayer"),
+        "BertEncoder": ("bert_layers", "BertEncoder"), "BertEmbeddings": ("bert_layers", "BertEmbeddings"),
+        "BertPooler": ("bert_layers", "BertPooler"),
         "stiefel_step": ("ops", "stiefel_step"), "stiefel_project_": ("ops", "stiefel_project_"),
     }
     if name == "optimization":      # the module itself, as the reference's scripts import it

@@ -175,6 +175,20 @@ class AttnDesc(C.Structure):
     ]
 
 
+class BertNormDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("res", C.c_void_p),
+        ("x_ld", C.c_int64), ("res_ld", C.c_int64),
+        ("keep", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+        ("y", C.c_void_p), ("stats", C.c_void_p), ("g", C.c_void_p),
+        ("dx", C.c_void_p), ("dres", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("p", C.c_double), ("eps", C.c_double),
+        ("rows", C.c_int64), ("hidden", C.c_int32), ("dtype", C.c_int32), ("param_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -305,6 +319,11 @@ ABI = {
     "tadmm_attn_workspace_bytes": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(C.c_size_t)]),
     "tadmm_attn_fwd": (C.c_int, [C.c_void_p, C.POINTER(AttnDesc), C.c_void_p]),
     "tadmm_attn_bwd": (C.c_int, [C.c_void_p, C.POINTER(AttnDesc), C.c_void_p]),
+    "tadmm_bertnorm_desc_bytes": (C.c_int, []),
+    "tadmm_bertnorm_fits": (C.c_int, [C.POINTER(BertNormDesc), C.POINTER(C.c_int)]),
+    "tadmm_bertnorm_workspace_bytes": (C.c_int, [C.POINTER(BertNormDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_bertnorm_fwd": (C.c_int, [C.c_void_p, C.POINTER(BertNormDesc), C.c_void_p]),
+    "tadmm_bertnorm_bwd": (C.c_int, [C.c_void_p, C.POINTER(BertNormDesc), C.c_void_p]),
     "tadmm_core_conv_desc_bytes": (C.c_int, []),
     "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
     "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
@@ -406,6 +425,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_distill_desc layout mismatch")
         if lib.tadmm_attn_desc_bytes() != C.sizeof(AttnDesc):
             raise TadmmLibraryError(f"{path}: tadmm_attn_desc layout mismatch")
+        if lib.tadmm_bertnorm_desc_bytes() != C.sizeof(BertNormDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_bertnorm_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         if lib.tadmm_dgemm_tile_prob_bytes() != C.sizeof(DgemmTileProb):

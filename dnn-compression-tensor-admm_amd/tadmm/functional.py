@@ -1086,3 +1086,133 @@ def self_attention(q, k, v, mask, num_heads: int, *, dropout_p: float = 0.0, tra
     out = _AttnFn.apply(q, k, v, None if mask is None else mask.detach(), keep if p > 0.0 else None, int(num_heads), p,
                         bool(need_scores))
     return out if need_scores else (out, None)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# BERT sub-layer tail (csrc/bertnorm.hip): LayerNorm(dropout(x) + res) of compressed_modeling*.py: *SelfOutput,
+# BertOutput, BertEmbeddings and BertPredictionHeadTransform, with the reference's BertLayerNorm (eps inside the root).
+# ---------------------------------------------------------------------------------------------------------------
+class _BertNormFn(torch.autograd.Function):
+    """x, res: (rows, hidden).  The backward recomputes s and xhat from x, res, keep and the saved (mean, rstd)."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, keep, eps, p):
+        need = any(ctx.needs_input_grad[:4])
+        y, stats = ops.bertnorm_fwd(x, res, weight, bias, eps=eps, p=p, keep=keep, need_stats=need)
+        if need:
+            ctx.save_for_backward(x, res, weight, stats)
+        ctx.keep, ctx.cfg = keep, (eps, p)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, res, weight, stats = ctx.saved_tensors
+        eps, p = ctx.cfg
+        need = ctx.needs_input_grad
+        dx, dres, dgamma, dbeta = ops.bertnorm_bwd(x, res, weight, stats, g, eps=eps, p=p, keep=ctx.keep,
+                                                   need=(need[0], need[1] and res is not None, need[2], need[3]))
+        if dgamma is not None:
+            dgamma = dgamma.to(weight.dtype)
+        if dbeta is not None:
+            dbeta = dbeta.to(weight.dtype)
+        return dx, dres, dgamma, dbeta, None, None, None
+
+
+def _layer_norm_args(x, res, weight, bias, dropout_p, keep, who):
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] < 1:
+        raise ValueError(f"{who}: x must be a tensor (..., hidden >= 1)")
+    if res is not None and (not isinstance(res, torch.Tensor) or res.shape != x.shape):
+        raise ValueError(f"{who}: res must have the shape of x")
+    for n, t in (("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (x.shape[-1],):
+            raise ValueError(f"{who}: {n} must be a ({x.shape[-1]},) tensor")
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise ValueError(f"{who}: dropout_p must be in [0, 1) (got {dropout_p})")
+    if keep is not None and (not isinstance(keep, torch.Tensor) or keep.shape != x.shape):
+        raise ValueError(f"{who}: keep must have the shape of x")
+
+
+def residual_keep_mask(shape, p: float, device, generator=None) -> torch.Tensor:
+    """The byte tensor of `shape` of kept elements of a dropout at rate p, drawn with torch's generator (so that a seed
+    reproduces a run and both routes of `residual_layer_norm` can be handed the same mask)."""
+    return (torch.rand(tuple(shape), device=device, generator=generator) >= p).to(torch.uint8)
+
+
+def residual_layer_norm_composed(x, res, weight, bias, *, eps: float = 1e-12, dropout_p: float = 0.0,
+                                 training: bool = False, keep=None):
+    """`residual_layer_norm` from torch operations, under autograd, on any device: `F.dropout` (or `keep` / (1 - p) where
+    a mask is given), the add, `F.layer_norm` -- the arithmetic of the reference's ten-call BertLayerNorm
+    (compressed_modeling_tt.py:145-158) behind its dropout and add, in the fewest launches torch has.  The route for what
+    the launch refuses (CPU tensors, float64, float16 training, rows wider than `ops.bertnorm_hmax()`), and the yardstick
+    of tests/test_gpu_bertnorm.py and scripts/bench_bertlayer.py.  Parameters of another type than x are converted."""
+    _layer_norm_args(x, res, weight, bias, dropout_p, keep, "residual_layer_norm_composed")
+    h = x
+    if training and dropout_p > 0.0:
+        if keep is None:
+            h = F.dropout(x, dropout_p, True)
+        else:
+            h = x * (keep != 0).to(x.dtype) / (1.0 - dropout_p)
+    if res is not None:
+        h = h + res
+    return F.layer_norm(h, (h.shape[-1],), weight.to(h.dtype), bias.to(h.dtype), eps)
+
+
+def layer_norm_launch_refusal(is_cuda: bool, dtype, rows: int, hidden: int, grad: bool, param_dtype=None,
+                              foreign: bool = False):
+    """None when csrc/bertnorm.hip takes a call with these properties, else the reason it does not (a string): CPU
+    tensors, a type other than float32 / bfloat16 / float16, float16 with gradients, no rows, a row wider than the
+    launch holds, parameters that are neither float32 nor of the type of x, or a residual, parameter or keep tensor of
+    another type or on another device (`foreign`).  A pure function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    if dtype not in ops.BERTNORM_DTYPES:
+        return f"{dtype} operands"
+    if dtype == torch.float16 and grad:
+        return "float16 with gradients"
+    if rows < 1 or hidden < 1 or not ops.bertnorm_fits(hidden, dtype):
+        return f"rows = {rows}, hidden = {hidden}"
+    if param_dtype is not None and param_dtype not in (torch.float32, dtype):
+        return f"{param_dtype} parameters beside {dtype} operands"
+    if foreign:
+        return "a residual, parameter or keep tensor of another type or on another device"
+    return None
+
+
+def residual_layer_norm(x, res, weight, bias, *, eps: float = 1e-12, dropout_p: float = 0.0, training: bool = False,
+                        keep=None, route: str = None):
+    """LayerNorm(dropout(x) + res) over the last dimension, the tail of every BERT sub-layer:
+
+        s = x * keep / (1 - p) + res,   y = weight * (s - mean(s)) / sqrt(var(s) + eps) + bias
+
+    with the biased variance and eps inside the root (the reference's BertLayerNorm).  `res`: a tensor of the shape and
+    type of x, or None (a plain LayerNorm).  Dropout acts only when `training` and `dropout_p` > 0: `keep` (the shape of
+    x, bytes, nonzero = kept) is drawn with torch's generator when not given.  Differentiable in x, res, weight and
+    bias; the gradients of x and res are always two tensors.  `route`: None (the launch where it takes the call and the
+    measured rule `ops.bertnorm_pays` says it is ahead), "launch" (csrc/bertnorm.hip: one launch forward, two backward)
+    or "composed" (torch operations).  The launch takes HIP tensors of float32 or bfloat16 (float16 without gradients)
+    with at most `ops.bertnorm_hmax()` columns and parameters in float32 or the type of x; leading dimensions are
+    flattened to rows, without a copy where the strides allow it (unit element stride, one row stride).  Everything
+    else goes to the composed route under `route=None` and raises under `route="launch"`."""
+    who = "residual_layer_norm"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    _layer_norm_args(x, res, weight, bias, dropout_p, keep, who)
+    hidden = x.shape[-1]
+    rows = x.numel() // hidden
+    p = float(dropout_p) if training else 0.0
+    grad = _needs_grad(x, res, weight, bias)
+    foreign = (res is not None and (res.dtype != x.dtype or res.device != x.device)) \
+        or weight.device != x.device or bias.device != x.device or weight.dtype != bias.dtype \
+        or (keep is not None and p > 0.0 and keep.device != x.device)
+    why = layer_norm_launch_refusal(x.is_cuda, x.dtype, rows, hidden, grad, weight.dtype, foreign)
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    launch = why is None and (route == "launch" or (route is None and ops.bertnorm_pays(rows, hidden, x.dtype, grad)))
+    if not launch:
+        return residual_layer_norm_composed(x, res, weight, bias, eps=eps, dropout_p=dropout_p, training=training,
+                                            keep=keep)
+    if p > 0.0 and keep is None:
+        keep = residual_keep_mask(x.shape, p, x.device)
+    y = _BertNormFn.apply(x.reshape(rows, hidden), None if res is None else res.reshape(rows, hidden), weight, bias,
+                          keep.reshape(rows, hidden) if p > 0.0 else None, float(eps), p)
+    return y.view(x.shape)

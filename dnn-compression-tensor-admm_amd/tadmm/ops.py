@@ -2130,3 +2130,154 @@ def attn_pays(B: int, H: int, S: int, d: int, dtype, grad: bool = False) -> bool
     tokens, the composed route beyond.  Not measured: lengths between 129 and 383 (sent to the composed route), head
     widths other than 64, head counts other than 12, float16, dropout on."""
     return S <= 128
+
+
+# ------------------------------------------------------------------ BERT sub-layer tail (csrc/bertnorm.hip)
+BERTNORM_DTYPES = DISTILL_DTYPES
+
+
+def bertnorm_hmax() -> int:
+    """The widest row `tadmm_bertnorm_fwd` / `_bwd` take (what `tadmm_bertnorm_fits` reports).  Host only."""
+    hmax = C.c_int()
+    _cabi.load().tadmm_bertnorm_fits(None, C.byref(hmax))
+    return int(hmax.value)
+
+
+def bertnorm_fits(hidden: int, dtype=torch.float32) -> bool:
+    """True when the launches take rows of `hidden` columns (`tadmm_bertnorm_fits`: 1 <= hidden <= `bertnorm_hmax()`).
+    Raises TadmmError for hidden < 1.  Host only."""
+    dsc = _cabi.BertNormDesc()
+    dsc.hidden, dsc.dtype = int(hidden), BERTNORM_DTYPES[dtype]
+    rc = _cabi.load().tadmm_bertnorm_fits(C.byref(dsc), None)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_bertnorm_fits: hidden = {hidden}")
+    return rc == 1
+
+
+def bertnorm_workspace_bytes(rows: int, hidden: int) -> int:
+    """Bytes of the backward's workspace (`tadmm_bertnorm_workspace_bytes`: one float32 (2, hidden rounded up to 4)
+    partial per workgroup of the row launch, min(ceil(rows / 4), 512) of them, rounded up to 256 bytes).  Host only."""
+    dsc = _cabi.BertNormDesc()
+    dsc.rows, dsc.hidden = int(rows), int(hidden)
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_bertnorm_workspace_bytes(C.byref(dsc), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_bertnorm_workspace_bytes: rows = {rows}, hidden = {hidden}")
+    return int(size.value)
+
+
+def _bertnorm_rows(t, who, what, shape, dt):
+    """A (rows, hidden) operand read in place: unit column stride and a row stride >= hidden as it stands (a column
+    slice of a wider tensor, a view that starts anywhere), anything else as a contiguous copy.  Returns (tensor, row
+    stride)."""
+    t = _operand(t, who, what, (dt,), shape, layout=None)
+    rows, hidden = t.shape
+    if (hidden > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < hidden):
+        t = t.contiguous()
+    return t, (max(int(t.stride(0)), hidden) if rows > 1 else hidden)
+
+
+def _bertnorm_desc(x, res, gamma, beta, p, keep, eps, who):
+    x = _operand(x, who, "x", tuple(BERTNORM_DTYPES), layout=None)
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise TadmmError(-1, f"{who}: x must be (rows, hidden >= 1) (got {tuple(x.shape)})")
+    rows, hidden = x.shape
+    dev, dt = x.device, x.dtype
+    dsc = _cabi.BertNormDesc()
+    hold = []
+    x, dsc.x_ld = _bertnorm_rows(x, who, "x", (rows, hidden), dt)
+    dsc.x = x.data_ptr()
+    hold.append(x)
+    if res is not None:
+        res, dsc.res_ld = _bertnorm_rows(res, who, "res", (rows, hidden), dt)
+        dsc.res = res.data_ptr()
+        hold.append(res)
+    pdt = gamma.dtype if isinstance(gamma, torch.Tensor) else None
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is None and name == "beta":
+            continue
+        t = _operand(t, who, name, (torch.float32, dt), (hidden,), layout="copy")
+        if t.dtype != pdt:
+            raise TadmmError(-1, f"{who}: gamma and beta must be of one type (got {pdt} and {t.dtype})")
+        hold.append(t)
+        setattr(dsc, name, t.data_ptr())
+    p = float(p)
+    if p > 0.0:
+        if keep is None:
+            raise TadmmError(-1, f"{who}: dropout p = {p} needs the keep tensor")
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        keep = _operand(keep, who, "keep", (torch.uint8,), (rows, hidden), layout="copy")
+        hold.append(keep)
+        dsc.keep = keep.data_ptr()
+    for t in hold:
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: an operand on {t.device}, x on {dev}")
+    dsc.p, dsc.eps = p, float(eps)
+    dsc.rows, dsc.hidden, dsc.dtype, dsc.param_dtype = rows, hidden, BERTNORM_DTYPES[dt], BERTNORM_DTYPES[pdt]
+    return dsc, hold, (rows, hidden, dev, dt)
+
+
+def bertnorm_fwd(x, res, gamma, beta, *, eps: float = 1e-12, p: float = 0.0, keep=None, need_stats: bool = False):
+    """(y, stats) of `tadmm_bertnorm_fwd`: y = LayerNorm(x keep / (1 - p) + res) over the last dimension of x (rows,
+    hidden), float32, bfloat16 or float16; `res` of the same type and shape or None; both read in place (unit element
+    stride, any row stride >= hidden, any element alignment).  `gamma`, `beta`: (hidden,), both float32 or both of the
+    type of x.  `keep` (rows, hidden) uint8 / bool, read when p > 0.  y (rows, hidden) contiguous in the type of x;
+    stats float32 (rows, 2) = (mean, 1 / sqrt(var + eps)) (None unless `need_stats`; the backward reads it).  One launch;
+    nothing synchronises."""
+    who = "bertnorm_fwd"
+    dsc, hold, (rows, hidden, dev, dt) = _bertnorm_desc(x, res, gamma, beta, p, keep, eps, who)
+    y = torch.empty((rows, hidden), dtype=dt, device=dev)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=dev) if need_stats else None
+    dsc.y = y.data_ptr()
+    dsc.stats = None if stats is None else stats.data_ptr()
+    h = _handle(dev)
+    h.check(h.lib.tadmm_bertnorm_fwd(h.ptr, C.byref(dsc), _stream(dev)))
+    return y, stats
+
+
+def bertnorm_bwd(x, res, gamma, stats, g, *, eps: float = 1e-12, p: float = 0.0, keep=None,
+                 need=(True, True, True, True)):
+    """(dx, dres, dgamma, dbeta) of `tadmm_bertnorm_bwd` for the upstream gradient `g` (rows, hidden) of y: float32 or
+    bfloat16 (float16 is refused).  s and xhat are recomputed from x, res, keep and `stats` (from
+    `bertnorm_fwd(need_stats=True)`).  dx and dres are two tensors in the type of x, dgamma and dbeta float32 (hidden,);
+    `need` says which of the four are wanted (None for the others; dres is None without `res`).  Two launches (one when
+    neither dgamma nor dbeta is wanted), no atomics, bitwise reproducible; nothing synchronises."""
+    who = "bertnorm_bwd"
+    dsc, hold, (rows, hidden, dev, dt) = _bertnorm_desc(x, res, gamma, None, p, keep, eps, who)
+    stats = _operand(stats, who, "stats", (torch.float32,), (rows, 2), layout="copy")
+    g = _operand(g, who, "g", (dt,), (rows, hidden), layout="copy")
+    dsc.stats, dsc.g = stats.data_ptr(), g.data_ptr()
+    want_dx, want_dres, want_dg, want_db = (bool(n) for n in need)
+    dx = torch.empty((rows, hidden), dtype=dt, device=dev) if want_dx else None
+    dres = torch.empty((rows, hidden), dtype=dt, device=dev) if want_dres and res is not None else None
+    dgamma = torch.empty(hidden, dtype=torch.float32, device=dev) if want_dg else None
+    dbeta = torch.empty(hidden, dtype=torch.float32, device=dev) if want_db else None
+    for name, t in (("dx", dx), ("dres", dres), ("dgamma", dgamma), ("dbeta", dbeta)):
+        setattr(dsc, name, None if t is None else t.data_ptr())
+    if want_dg or want_db:
+        nbytes = bertnorm_workspace_bytes(rows, hidden)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    h = _handle(dev)
+    h.check(h.lib.tadmm_bertnorm_bwd(h.ptr, C.byref(dsc), _stream(dev)))
+    return dx, dres, dgamma, dbeta
+
+
+def bertnorm_pays(rows: int, hidden: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.residual_layer_norm` sends a call the launch can take to it and not to the composed torch
+    route.  A pure function of its arguments.  Measured (scripts/bench_bertlayer.py) at rows = B S
+    for B in {1, 8, 32}, S in {64, 128, 512}, hidden in {312, 768, 1024}, float32 and bfloat16, a forward under no_grad
+    and a training step with dropout 0.1, against `residual_layer_norm_composed` in the same run.  Up to 4096 rows both
+    routes are bound by the host and the composed route is ahead beyond the spread in 88 of 96 classes, level in 8
+    (forward 0.018 against 0.024 ms, training step 0.085 against 0.13 - 0.17 ms): F.layer_norm behind one add is two
+    native calls, the launch pays its Python descriptor and, in training, three torch calls for the keep mask.  At 16384
+    rows the kernel's one pass shows: float32 forward 1.3x - 1.9x at all three widths, float32 training 1.2x at 768 and
+    1024 (behind at 312), bfloat16 forward 1.5x at 768 and 1024 (level at 312), bfloat16 training behind everywhere.  So
+    the rule goes by the element count rows * hidden, from the smallest class measured ahead: float32 forward from
+    16384 x 312, float32 training and 16-bit forward from 16384 x 768, 16-bit training never.  Not measured: row counts
+    between 4096 and 16384 and beyond 16384, widths other than the three, float16 (treated as bfloat16)."""
+    n = int(rows) * int(hidden)
+    if grad:
+        return dtype == torch.float32 and n >= 16384 * 768
+    return n >= (16384 * 312 if dtype == torch.float32 else 16384 * 768)

@@ -731,6 +731,60 @@ int tadmm_attn_workspace_bytes(const tadmm_attn_desc* d, size_t* bytes);
 int tadmm_attn_fwd(tadmm_handle h, const tadmm_attn_desc* d, void* stream);
 int tadmm_attn_bwd(tadmm_handle h, const tadmm_attn_desc* d, void* stream);
 
+/* ---- BERT sub-layer tail: dropout, residual add and LayerNorm in one launch (csrc/bertnorm.hip) ---------------------
+ * xcompression/transformer/compressed_modeling*.py: LayerNorm(dropout(x) + res) of *SelfOutput, BertOutput, BertEmbeddings
+ * and BertPredictionHeadTransform, with the reference's BertLayerNorm (epsilon inside the root).  x, res: (rows, hidden)
+ * of `dtype`, read in place: unit element stride, row strides x_ld / res_ld >= hidden in elements, any element-aligned
+ * base (16-byte accesses when every base is 16-byte aligned, the row strides are whole 16-byte units and hidden is a
+ * multiple of 16 bytes of elements; element accesses otherwise).  res is nullable (zeros).
+ *   s_ij   = x_ij * (keep_ij != 0) / (1 - p) + res_ij        keep: bytes (rows, hidden) contiguous, read when p > 0
+ *   mean_i = sum_j s_ij / hidden,  var_i = sum_j (s_ij - mean_i)^2 / hidden,  rstd_i = 1 / sqrt(var_i + eps)
+ *   y_ij   = gamma_j (s_ij - mean_i) rstd_i + beta_j         gamma, beta: (hidden) of `param_dtype`: float32 or `dtype`
+ * Elementwise arithmetic is float32; the two row sums (of s, and of (s - mean)^2 over the row held in registers) are added
+ * in double, so mean and rstd are exact values rounded once to float32.
+ * tadmm_bertnorm_fwd writes y ((rows, hidden) contiguous, of `dtype`) and stats (float32 (rows, 2) = (mean, rstd);
+ * nullable).  One launch.
+ * tadmm_bertnorm_bwd reads x, res, keep, gamma, stats and g (the gradient of y: contiguous, of `dtype`), recomputes s and
+ * xhat = (s - mean) rstd with the forward's expressions and writes, each nullable and contiguous of `dtype`,
+ *   dres_ij = rstd_i (a_ij - mean_j a_i. - xhat_ij mean_j(a_i. xhat_i.)),  a = g gamma;    dx = dres keep / (1 - p)
+ * (dx and dres must be two buffers) and, each nullable, float32 (hidden): dgamma_j = sum_i g_ij xhat_ij, dbeta_j =
+ * sum_i g_ij.  Two launches: row blocks (per-workgroup partial sums to the workspace), then a fixed-order sum of the
+ * partials in double; the second and the workspace (tadmm_bertnorm_workspace_bytes, reads rows and hidden; 16-byte
+ * aligned) are needed only when dgamma or dbeta is given.  No atomics; grids depend on (rows, hidden, dtype) alone:
+ * bitwise reproducible; no host synchronisation.
+ * tadmm_bertnorm_fits is host only and reads hidden: 1 for 1 <= hidden <= HMAX (2048; *hmax, nullable, receives it), 0
+ * above, TADMM_ERR_INVALID for a NULL descriptor or hidden < 1.  The launches return TADMM_ERR_UNSUPPORTED where _fits
+ * returns 0 and TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or descriptor; rows < 0 or hidden < 1; an
+ * unknown dtype; TADMM_CHAIN_F16 in _bwd; a param_dtype that is neither float32 nor dtype; x NULL; a pointer not aligned
+ * to its element; a row stride below hidden; p outside [0, 1); p > 0 without keep; eps negative or not finite; gamma NULL
+ * (beta too in _fwd); y NULL (_fwd); stats or g NULL (_bwd); dx == dres.  TADMM_ERR_WORKSPACE: dgamma or dbeta given and
+ * the workspace NULL, misaligned or short.  rows == 0 succeeds and launches nothing. */
+typedef struct {
+  const void* x; const void* res;             /* res nullable */
+  int64_t x_ld, res_ld;                       /* row strides, elements */
+  const uint8_t* keep;                        /* (rows, hidden); required when p > 0 */
+  const void* gamma; const void* beta;        /* (hidden) of param_dtype */
+  void* y;                                    /* forward */
+  float* stats;                               /* forward writes it (nullable), backward reads it */
+  const void* g;                              /* backward */
+  void* dx; void* dres;                       /* backward; each nullable */
+  float* dgamma; float* dbeta;                /* backward; each nullable */
+  void* workspace; size_t workspace_bytes;    /* backward with dgamma or dbeta */
+  double p;                                   /* dropout probability, [0, 1) */
+  double eps;
+  int64_t rows;
+  int32_t hidden;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (forward only) */
+  int32_t param_dtype;                        /* TADMM_CHAIN_F32 | dtype */
+  int32_t reserved;
+} tadmm_bertnorm_desc;
+/* sizeof(tadmm_bertnorm_desc) as the library was built */
+int tadmm_bertnorm_desc_bytes(void);
+int tadmm_bertnorm_fits(const tadmm_bertnorm_desc* d, int* hmax);
+int tadmm_bertnorm_workspace_bytes(const tadmm_bertnorm_desc* d, size_t* bytes);
+int tadmm_bertnorm_fwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* stream);
+int tadmm_bertnorm_bwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
