@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -27,7 +27,7 @@ def __getattr__(name):
         "TTEmbedding": ("emb_layers", "TTEmbedding"), "TTMEmbedding": ("emb_layers", "TTMEmbedding"),
         "SVDEmbedding": ("emb_layers", "SVDEmbedding"),
         "TTLSTM": ("rnn_layers", "TTLSTM"),
-        "DistillationLoss": ("losses", "DistillationLoss"),
+        "DistillationLoss": ("losses", "DistillationLoss"), "TinyBertLayerLoss": ("losses", "TinyBertLayerLoss"),
         "BertAdam": ("optimization", "BertAdam"),
         "BertSelfAttention": ("bert_layers", "BertSelfAttention"),
         "BertLayerNorm": ("bert_layers", "BertLayerNorm"), "BertSelfOutput": ("bert_layers", "BertSelfOutput"),

@@ -160,6 +160,27 @@ class DistillDesc(C.Structure):
     ]
 
 
+LAYER_MSE_MAX_PAIRS = 32
+LAYER_MSE_ATT, LAYER_MSE_REP = 0, 1
+
+
+class LayerMsePair(C.Structure):
+    _fields_ = [
+        ("s", C.c_void_p), ("t", C.c_void_p), ("grad", C.c_void_p),
+        ("n", C.c_int64), ("scale", C.c_double), ("thr", C.c_float),
+        ("clamp", C.c_int32), ("group", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class LayerMseDesc(C.Structure):
+    _fields_ = [
+        ("pairs", LayerMsePair * LAYER_MSE_MAX_PAIRS),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("terms_dev", C.c_void_p), ("loss_dev", C.c_void_p), ("loss_f32_dev", C.c_void_p),
+        ("npairs", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p),
@@ -314,6 +335,11 @@ ABI = {
     "tadmm_distill_desc_bytes": (C.c_int, []),
     "tadmm_distill_workspace_bytes": (C.c_int, [C.POINTER(DistillDesc), C.POINTER(C.c_size_t)]),
     "tadmm_distill_loss": (C.c_int, [C.c_void_p, C.POINTER(DistillDesc), C.c_void_p]),
+    "tadmm_layer_mse_desc_bytes": (C.c_int, []),
+    "tadmm_layer_mse_max_pairs": (C.c_int, []),
+    "tadmm_layer_mse_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tadmm_layer_mse_workspace_bytes": (C.c_int, [C.POINTER(LayerMseDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_layer_mse": (C.c_int, [C.c_void_p, C.POINTER(LayerMseDesc), C.c_void_p]),
     "tadmm_attn_desc_bytes": (C.c_int, []),
     "tadmm_attn_fits": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(C.c_size_t)]),
     "tadmm_attn_workspace_bytes": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(C.c_size_t)]),
@@ -423,6 +449,11 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_lstm_desc layout mismatch")
         if lib.tadmm_distill_desc_bytes() != C.sizeof(DistillDesc):
             raise TadmmLibraryError(f"{path}: tadmm_distill_desc layout mismatch")
+        if lib.tadmm_layer_mse_desc_bytes() != C.sizeof(LayerMseDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_layer_mse_desc layout mismatch")
+        if lib.tadmm_layer_mse_max_pairs() != LAYER_MSE_MAX_PAIRS:
+            raise TadmmLibraryError(f"{path}: tadmm_layer_mse_max_pairs() = {lib.tadmm_layer_mse_max_pairs()}, binding "
+                                    f"{LAYER_MSE_MAX_PAIRS}")
         if lib.tadmm_attn_desc_bytes() != C.sizeof(AttnDesc):
             raise TadmmLibraryError(f"{path}: tadmm_attn_desc layout mismatch")
         if lib.tadmm_bertnorm_desc_bytes() != C.sizeof(BertNormDesc):

@@ -960,6 +960,197 @@ def soft_cross_entropy(predicts: torch.Tensor, targets: torch.Tensor, temperatur
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# TinyBERT layer losses (csrc/layermse.hip): the intermediate-layer step of task_distill.py:810-828 -- the MSE of the
+# attention scores with the masked entries zeroed, the MSE of the hidden states, and the students' gradients, for all
+# pairs of a step in two launches.
+# ---------------------------------------------------------------------------------------------------------------
+LAYER_MSE_REDUCTIONS = ("batch_sum", "mean")
+
+
+def _layer_mse_list(x, who, what):
+    if x is None:
+        return []
+    if isinstance(x, torch.Tensor):
+        return [x]
+    x = list(x)
+    for i, t in enumerate(x):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {what}[{i}] must be a tensor (got {type(t).__name__})")
+    return x
+
+
+def _layer_mse_args(student_atts, teacher_atts, student_reps, teacher_reps, reduction, att_weights, rep_weights, who):
+    """The four arguments as lists, and the scale c of every pair: w B / numel ("batch_sum") or w / numel ("mean")."""
+    if reduction not in LAYER_MSE_REDUCTIONS:
+        raise ValueError(f"{who}: reduction is one of {LAYER_MSE_REDUCTIONS} (got {reduction!r})")
+    sides = []
+    for name, ss, ts, ws in (("atts", student_atts, teacher_atts, att_weights), ("reps", student_reps, teacher_reps, rep_weights)):
+        ss, ts = _layer_mse_list(ss, who, "student_" + name), _layer_mse_list(ts, who, "teacher_" + name)
+        if len(ss) != len(ts):
+            raise ValueError(f"{who}: {len(ss)} student_{name} and {len(ts)} teacher_{name}")
+        if ws is None:
+            ws = [1.0] * len(ss)
+        elif isinstance(ws, (int, float)):
+            ws = [float(ws)] * len(ss)
+        else:
+            ws = [float(w) for w in ws]
+            if len(ws) != len(ss):
+                raise ValueError(f"{who}: {len(ws)} weights for {len(ss)} student_{name}")
+        scales = []
+        for i, (s, t, w) in enumerate(zip(ss, ts, ws)):
+            if s.shape != t.shape:
+                raise ValueError(f"{who}: student_{name}[{i}] is {tuple(s.shape)}, teacher_{name}[{i}] is {tuple(t.shape)}")
+            if s.dim() < 1 or s.numel() < 1:
+                raise ValueError(f"{who}: student_{name}[{i}] must have a batch dimension and at least one element "
+                                 f"(got {tuple(s.shape)})")
+            scales.append(w * (s.shape[0] if reduction == "batch_sum" else 1) / s.numel())
+        sides.append((ss, ts, scales))
+    return sides
+
+
+def intermediate_distillation_loss_composed(student_atts, teacher_atts, student_reps, teacher_reps, *,
+                                            threshold=-1e2, reduction: str = "batch_sum", att_weights=None,
+                                            rep_weights=None):
+    """`intermediate_distillation_loss` as the reference composes it (task_distill.py:810-828) from `torch.where` and
+    `F.mse_loss` under autograd, on any device and any floating type: 16-bit tensors are widened to float32 first, float64
+    stays float64 (and so does the result).  The route for what the launch refuses and where `ops.layer_mse_pays` says
+    it is not ahead, and the yardstick of tests/test_gpu_layer_mse.py and scripts/bench_layer_mse.py."""
+    who = "intermediate_distillation_loss_composed"
+    sides = _layer_mse_args(student_atts, teacher_atts, student_reps, teacher_reps, reduction, att_weights, rep_weights, who)
+    anyt = next((s for ss, _, _ in sides for s in ss), None)
+    out = []
+    for k, (ss, ts, scales) in enumerate(sides):
+        total = None
+        for s, t, c in zip(ss, ts, scales):
+            t = t.detach()
+            if s.dtype in (torch.bfloat16, torch.float16):
+                s, t = s.float(), t.float()
+            elif t.dtype != s.dtype:
+                t = t.to(s.dtype)
+            if k == 0 and threshold is not None:
+                s = torch.where(s <= threshold, torch.zeros_like(s), s)
+                t = torch.where(t <= threshold, torch.zeros_like(t), t)
+            term = F.mse_loss(s, t) * (c * s.numel())
+            total = term if total is None else total + term
+        if total is None:
+            total = torch.zeros((), dtype=torch.float32, device=None if anyt is None else anyt.device)
+        out.append(total)
+    return out[0], out[1]
+
+
+def layer_mse_launch_refusal(is_cuda: bool, dtypes, npairs: int, teacher_foreign: bool = False):
+    """None when csrc/layermse.hip takes a call with these properties, else the reason it does not (a string): CPU
+    tensors, an element type other than float32 / bfloat16 / float16, more than one type in the call (`dtypes`: the
+    types of all students and teachers), more than `ops.LAYER_MSE_MAX_PAIRS` pairs, or a tensor that lives on another
+    device than the first student (`teacher_foreign`).  A pure function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    dtypes = list(dict.fromkeys(dtypes))
+    for dt in dtypes:
+        if dt not in ops.LAYER_MSE_DTYPES:
+            return f"{dt} operands"
+    if len(dtypes) > 1:
+        return "mixed element types in one call (" + ", ".join(str(dt) for dt in dtypes) + ")"
+    if npairs > ops.LAYER_MSE_MAX_PAIRS:
+        return f"{npairs} pairs (one call takes {ops.LAYER_MSE_MAX_PAIRS})"
+    if teacher_foreign:
+        return "a teacher on another device than its student"
+    return None
+
+
+class _LayerMseFn(torch.autograd.Function):
+    """apply(cfg, *students, *teachers): the forward computes both losses and the float32 gradients of the students that
+    need one into one flat buffer, attention pairs first; the backward multiplies each group's slice by its incoming
+    gradient and only then rounds to the students' type (a float16 gradient 2 d B / numel is below float16's normal
+    range before GradScaler's 2^16 is applied)."""
+
+    @staticmethod
+    def forward(ctx, cfg, *tensors):
+        natt, nrep, scales, threshold = cfg
+        n = natt + nrep
+        students, teachers = tensors[:n], tensors[n:]
+        ctx.set_materialize_grads(False)
+        needs = ctx.needs_input_grad[1:1 + n]
+        spans, cursor, cut = [None] * n, 0, None         # flat[:cut]: the attention pairs, flat[cut:]: the hidden pairs
+        for i, s in enumerate(students):
+            if i == natt:
+                cut = cursor
+            if needs[i]:
+                start = (cursor + 3) // 4 * 4            # 16-byte aligned: wide gradient stores
+                cursor = start + s.numel()
+                spans[i] = (start, cursor)
+        cut = cursor if cut is None else cut
+        flat = torch.empty(cursor, dtype=torch.float32, device=students[0].device) if cursor else None
+        grads = [None if sp is None else flat[sp[0]:sp[1]] for sp in spans]
+        loss, _ = ops.layer_mse(students, teachers, scales, [0] * natt + [1] * nrep,
+                                [threshold is not None] * natt + [False] * nrep, threshold, grads=grads)
+        ctx.flat, ctx.spans, ctx.cut, ctx.natt = flat, spans, cut, natt
+        ctx.meta = [(s.dtype, s.shape) for s in students]
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_att, g_rep):
+        flat, n, cut = ctx.flat, len(ctx.spans), ctx.cut
+        out = [None] * (1 + 2 * n)
+        if flat is None or (g_att is None and g_rep is None):
+            return tuple(out)
+        res = torch.empty(flat.shape, dtype=ctx.meta[0][0], device=flat.device)
+        for g, lo, hi in ((g_att, 0, cut), (g_rep, cut, flat.numel())):
+            if g is not None and hi > lo:             # scale in float32, round once on the store
+                torch.mul(flat[lo:hi], g if g.dtype == torch.float32 else g.float(), out=res[lo:hi])
+        for i, sp in enumerate(ctx.spans):
+            if sp is not None and (g_att if i < ctx.natt else g_rep) is not None:
+                out[1 + i] = res[sp[0]:sp[1]].view(ctx.meta[i][1])
+        return tuple(out)
+
+
+def intermediate_distillation_loss(student_atts, teacher_atts, student_reps, teacher_reps, *, threshold=-1e2,
+                                   reduction: str = "batch_sum", att_weights=None, rep_weights=None, route: str = None):
+    """(att_loss, rep_loss) of TinyBERT's intermediate-layer distillation step (task_distill.py:810-828), both float32
+    0-dim and differentiable in the student tensors; the teachers are detached:
+
+        att_loss = sum_i w_i R((s_i where s_i > threshold else 0) - (t_i where t_i > threshold else 0))
+        rep_loss = sum_i w_i R(s_i - t_i)
+        R(d) = "batch_sum": sum_b mean(d[b]^2)   (the reference's loop over the batch axis of the last layer)
+               "mean":      mean(d^2)            (MSELoss over the whole tensor: upstream TinyBERT's per-layer loop)
+
+    Each of the four arguments is a tensor or a sequence of tensors, paired by position; either side may be empty (its
+    loss is then a float32 zero without a graph).  `threshold=None` switches the clamp off.  `att_weights`, `rep_weights`:
+    None, one number or one per pair (task_distill1.py's beta_scale).  `route`: None (the launch where it takes the call
+    and the measured rule `ops.layer_mse_pays` says it is ahead), "launch" (csrc/layermse.hip: values and gradients in
+    two launches, the backward at most two more) or "composed" (torch operations).  The launch takes HIP tensors of one
+    type (float32, bfloat16 or float16) on one device, at most `ops.LAYER_MSE_MAX_PAIRS` pairs; anything else goes to
+    the composed route under `route=None` and raises under `route="launch"`.  Students that are not contiguous are
+    copied.  Nothing synchronises."""
+    who = "intermediate_distillation_loss"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    sides = _layer_mse_args(student_atts, teacher_atts, student_reps, teacher_reps, reduction, att_weights, rep_weights, who)
+    (sa, ta, ca), (sr, tr, cr) = sides
+    students, teachers = sa + sr, ta + tr
+    n = len(students)
+    kw = dict(threshold=threshold, reduction=reduction, att_weights=att_weights, rep_weights=rep_weights)
+    if n == 0:
+        return intermediate_distillation_loss_composed(sa, ta, sr, tr, **kw)
+    every = students + teachers
+    dev = students[0].device
+    why = layer_mse_launch_refusal(all(t.is_cuda for t in every), [t.dtype for t in every], n,
+                                   any(t.device != dev for t in every))
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    launch = why is None and route != "composed"
+    if launch and route is None:
+        launch = ops.layer_mse_pays(sum(s.numel() for s in students), n, students[0].dtype, _needs_grad(*students))
+    if not launch:
+        att, rep = intermediate_distillation_loss_composed(sa, ta, sr, tr, **kw)
+        return att.float(), rep.float()
+    students = [s if s.is_contiguous() else s.contiguous() for s in students]       # the gradient returns through the copy
+    cfg = (len(sa), len(sr), tuple(ca + cr), None if threshold is None else float(threshold))
+    att, rep = _LayerMseFn.apply(cfg, *students, *[t.detach() for t in teachers])
+    return (att if sa else att.detach()), (rep if sr else rep.detach())
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # BERT self-attention (csrc/attn.hip): the body of compressed_modeling*.py: *BertSelfAttention.forward after the three
 # projections -- raw masked scores (a differentiable output: TinyBERT regresses them), softmax, dropout, context.
 # ---------------------------------------------------------------------------------------------------------------

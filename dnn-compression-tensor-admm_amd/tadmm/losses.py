@@ -29,6 +29,9 @@ Deliberate differences:
     counted on the device (`bad_labels()` reads the counter of the latest call) instead of faulting the device;
   * logits and targets must be HIP tensors, the logits of one type (float32, bfloat16 or float16) on one device;
     anything else raises `TadmmError` naming the tensor.  There is no CPU path.
+
+`TinyBertLayerLoss` (below) is the intermediate-layer step of xcompression/task_distill.py:810-828: the attention and
+hidden-state MSE terms of every pair and the students' gradients from one call of csrc/layermse.hip.
 """
 from __future__ import annotations
 
@@ -141,3 +144,34 @@ class DistillationLoss(torch.nn.Module):
                                     tau=self.tau, smoothing=smoothing, ignore_index=ignore_index, counts=box)
         self._counts = box[0] if box else None
         return loss
+
+
+class TinyBertLayerLoss(torch.nn.Module):
+    """The intermediate-layer distillation step of xcompression/task_distill.py:810-828 (and task_distill2.py,
+    general_distill.py:438-451) as a criterion:
+
+        criterion = TinyBertLayerLoss()
+        att_loss, rep_loss = criterion(student_atts[-1], teacher_atts[-1], student_reps[-1], teacher_reps[-1])
+
+    att_loss regresses the students' raw attention scores on the teachers' with every entry <= `threshold` (the additive
+    -10000 of masked keys) set to zero on both sides, rep_loss the hidden states; each argument is a tensor or a
+    sequence of tensors paired by position.  reduction "batch_sum" is the reference's loop over the batch axis of the
+    last layer (sum over samples of the sample's mean), "mean" is MSELoss over each whole tensor, summed over the pairs
+    (upstream TinyBERT's loop over layers; `att_weights` / `rep_weights` of the call carry task_distill1.py's per-layer
+    scale).  Both losses, and the gradients of every student tensor, come from one call of csrc/layermse.hip (two
+    launches; `functional.intermediate_distillation_loss`); `route` ("launch", "composed" or None for the measured rule
+    `ops.layer_mse_pays`) is an attribute like that of the BERT modules.  Which teacher layer is paired with which
+    student layer stays the caller's business, as in the reference.  Both results are float32 0-dim tensors."""
+
+    def __init__(self, threshold=-1e2, reduction: str = "batch_sum"):
+        super().__init__()
+        if reduction not in HF.LAYER_MSE_REDUCTIONS:
+            raise ValueError(f"TinyBertLayerLoss: reduction is one of {HF.LAYER_MSE_REDUCTIONS} (got {reduction!r})")
+        self.threshold = threshold
+        self.reduction = reduction
+        self.route = None
+
+    def forward(self, student_atts, teacher_atts, student_reps, teacher_reps, att_weights=None, rep_weights=None):
+        return HF.intermediate_distillation_loss(student_atts, teacher_atts, student_reps, teacher_reps,
+                                                 threshold=self.threshold, reduction=self.reduction,
+                                                 att_weights=att_weights, rep_weights=rep_weights, route=self.route)

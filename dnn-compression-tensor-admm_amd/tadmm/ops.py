@@ -1995,6 +1995,122 @@ def distill_loss_pays(B: int, C: int, dtype, grad: bool = False) -> bool:
     return True
 
 
+# ------------------------------------------------------------------ TinyBERT layer losses (csrc/layermse.hip)
+LAYER_MSE_MAX_PAIRS = _cabi.LAYER_MSE_MAX_PAIRS
+LAYER_MSE_DTYPES = DISTILL_DTYPES
+LAYER_MSE_GROUPS = {"att": _cabi.LAYER_MSE_ATT, "rep": _cabi.LAYER_MSE_REP}
+
+
+def layer_mse_geometry():
+    """(chunk_elems, max_blocks) of `tadmm_layer_mse`: the elements of one chunk of a pair and the cap of the streaming
+    launch's grid (`tadmm_layer_mse_geometry`).  Host only."""
+    chunk, blocks = C.c_int(), C.c_int()
+    rc = _cabi.load().tadmm_layer_mse_geometry(C.byref(chunk), C.byref(blocks))
+    if rc < 0:
+        raise TadmmError(rc, "tadmm_layer_mse_geometry")
+    return int(chunk.value), int(blocks.value)
+
+
+def layer_mse_workspace_bytes(numels: Sequence[int]) -> int:
+    """Bytes of the partial-sum workspace of `tadmm_layer_mse` for pairs of `numels` elements
+    (`tadmm_layer_mse_workspace_bytes`: one double per pair and workgroup).  Host only."""
+    numels = [int(n) for n in numels]
+    d = _cabi.LayerMseDesc()
+    d.npairs = len(numels)
+    for i, n in enumerate(numels[:LAYER_MSE_MAX_PAIRS]):
+        d.pairs[i].n = n
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_layer_mse_workspace_bytes(C.byref(d), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_layer_mse_workspace_bytes: numels = {numels}")
+    return int(size.value)
+
+
+def _per_pair(v, n, what):
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"layer_mse: {len(v)} {what} for {n} pairs")
+        return list(v)
+    return [v] * n
+
+
+def layer_mse(students, teachers, scales, groups, clamp, thr, *, grads=None):
+    """(loss, terms) of `tadmm_layer_mse` for the pairs (students[i], teachers[i]): equal shapes, float32, bfloat16 or
+    float16 of one type on one HIP device (a non-contiguous tensor is copied).  With s' and t' the values of a pair whose
+    entries <= `thr` are replaced by zero where `clamp` is set, term_i = scales[i] * sum((s' - t')^2); loss: float32 (2,) =
+    the sums of the terms of group "att" (0) and of group "rep" (1); terms: float64 (npairs,).  `groups`, `clamp` and `thr`
+    are one value for all pairs or a sequence.  `grads`: per pair None or a contiguous float32 tensor of the pair's
+    element count that receives d term_i / d students[i] = 2 scales[i] (s' - t'), zero where s was clamped.  Two launches
+    whatever the number of pairs (at most `LAYER_MSE_MAX_PAIRS`); nothing synchronises."""
+    who = "layer_mse"
+    students, teachers = list(students), list(teachers)
+    n = len(students)
+    if len(teachers) != n:
+        raise ValueError(f"{who}: {n} students and {len(teachers)} teachers")
+    if not 1 <= n <= LAYER_MSE_MAX_PAIRS:
+        raise TadmmError(-1, f"{who}: {n} pairs; one call takes 1 to {LAYER_MSE_MAX_PAIRS}")
+    scales, groups = _per_pair(scales, n, "scales"), _per_pair(groups, n, "groups")
+    clamp, thr = _per_pair(clamp, n, "clamp flags"), _per_pair(thr, n, "thresholds")
+    grads = _per_pair(grads, n, "gradient buffers")
+    first = _operand(students[0], who, "students[0]", tuple(LAYER_MSE_DTYPES), layout=None)
+    dev, dt = first.device, first.dtype
+    d = _cabi.LayerMseDesc()
+    hold = []
+    for i in range(n):
+        s = _operand(students[i], who, f"students[{i}]", (dt,), layout="copy")
+        t = _operand(teachers[i], who, f"teachers[{i}]", (dt,), tuple(s.shape), layout="copy")
+        if s.device != dev or t.device != dev:
+            raise TadmmError(-1, f"{who}: pair {i} on {s.device} / {t.device}, students[0] on {dev}")
+        if s.numel() < 1:
+            raise TadmmError(-1, f"{who}: pair {i} is empty")
+        if groups[i] not in (0, 1) and groups[i] not in LAYER_MSE_GROUPS:
+            raise ValueError(f"{who}: group {groups[i]!r} of pair {i} is none of 0, 1, 'att', 'rep'")
+        hold += [s, t]
+        q = d.pairs[i]
+        q.s, q.t, q.n = s.data_ptr(), t.data_ptr(), s.numel()
+        q.scale = float(scales[i])
+        q.clamp = 1 if clamp[i] and thr[i] is not None else 0
+        q.thr = float(thr[i]) if q.clamp else 0.0
+        q.group = LAYER_MSE_GROUPS.get(groups[i], groups[i])
+        if grads[i] is not None:
+            g = _output(grads[i], tuple(grads[i].shape), torch.float32, dev, f"{who}: grads[{i}]")
+            if g.numel() != s.numel():
+                raise TadmmError(-1, f"{who}: grads[{i}] has {g.numel()} elements, the pair {s.numel()}")
+            q.grad = g.data_ptr()
+    d.npairs, d.dtype = n, LAYER_MSE_DTYPES[dt]
+    wide = torch.empty(n + 3, dtype=torch.float64, device=dev)      # [terms | loss as double (2) | loss as float32 (2)]
+    loss = wide[n + 2:].view(torch.float32)
+    size = C.c_size_t()
+    h = _handle(dev)
+    rc = h.lib.tadmm_layer_mse_workspace_bytes(C.byref(d), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"{who}: the pairs hold more chunks than one call takes")
+    ws = _scratch(size.value, dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), size.value
+    d.terms_dev, d.loss_dev, d.loss_f32_dev = wide.data_ptr(), wide.data_ptr() + 8 * n, loss.data_ptr()
+    h.check(h.lib.tadmm_layer_mse(h.ptr, C.byref(d), _stream(dev)))
+    return loss, wide[:n]
+
+
+def layer_mse_pays(numel: int, npairs: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.intermediate_distillation_loss` sends a call the launch can take to it and not to the
+    composed torch route.  A pure function of the total element count of the students, the number of pairs, the element
+    type and whether gradients will be asked for.  Measured (scripts/bench_layer_mse.py) against
+    `intermediate_distillation_loss_composed` in the same run, three runs, float32 and bfloat16, value only and value +
+    backward, at four classes: the reference's step (1 + 1 pairs, 9.4 M elements), a small step (1 + 1 pairs, 0.55 M),
+    and per-layer loops of 4 + 5 pairs (31.6 M) and 12 + 13 pairs (29.1 M).  In every run the launch's slowest window is
+    below the composed route's fastest for the value (2.0x - 11.3x), for the bfloat16 training step (1.5x - 8.4x) and
+    for the float32 training step of the 9- and 25-pair classes (3.3x - 5.5x).  The float32 training step of the two
+    2-pair classes is ahead by the medians in all three runs (1.3x - 2.2x) but level by the windows in two of them
+    (the launch's slowest window 0.17 - 0.20 ms against the composed route's fastest 0.16 - 0.17 ms: both are bound by the
+    host there), so it goes to the composed route until it has 9 pairs or 29.1 M elements, the smallest classes
+    measured ahead.  Not measured: float16 (treated as bfloat16), between 2 and 9 pairs, more than 32 M elements, calls
+    in which only some students require a gradient."""
+    if grad and dtype == torch.float32:
+        return npairs >= 9 or numel >= 29_097_984
+    return True
+
+
 # ------------------------------------------------------------------ BERT self-attention (csrc/attn.hip)
 ATTN_DTYPES = DISTILL_DTYPES
 

@@ -785,6 +785,53 @@ int tadmm_bertnorm_workspace_bytes(const tadmm_bertnorm_desc* d, size_t* bytes);
 int tadmm_bertnorm_fwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* stream);
 int tadmm_bertnorm_bwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* stream);
 
+/* ---- TinyBERT layer losses: masked attention MSE and hidden-state MSE with gradients (csrc/layermse.hip) -------------
+ * xcompression/task_distill.py:810-828 (also task_distill1.py, task_distill2.py, general_distill.py:438-451) for all
+ * pairs of a step in two launches.  A call carries npairs <= TADMM_LAYER_MSE_MAX_PAIRS pairs; pair i is s (student)
+ * and t (teacher), n elements each, flat and dense, of `dtype` (TADMM_CHAIN_F32 / _BF16 / _F16; one type per call),
+ * any element-aligned base (16-byte loads where both bases of the pair are 16-byte aligned, element loads otherwise).
+ * With every value widened to float32 on load:
+ *   s' = (clamp && s <= thr) ? 0 : s,  t' = (clamp && t <= thr) ? 0 : t,  d = s' - t'
+ *   terms_dev[i] = scale * sum_e d^2                 (the caller folds weight / denominator into `scale`)
+ *   grad[e]      = (clamp && s <= thr) ? 0 : 2 scale d      (float32, n elements, 4-byte aligned; nullable: not written)
+ *   loss_dev[g]  = sum of terms_dev[i] over the pairs of group g, in pair order (0 when the group has none)
+ * -inf is clamped; a NaN compares false and propagates.  d, d^2 and the sums are double; grad is rounded once.
+ * Outputs: terms_dev[npairs] and loss_dev[2] (double), loss_f32_dev[2] (nullable: loss_dev rounded once); overwritten.
+ * workspace: tadmm_layer_mse_workspace_bytes (host only; reads npairs and every n) bytes, 8-byte aligned: one double per
+ * pair and workgroup of the streaming launch, min(chunks, max_blocks) of them, rounded up to 256 bytes, where a pair of n
+ * elements has ceil(n / chunk_elems) chunks and tadmm_layer_mse_geometry reports chunk_elems and max_blocks.
+ * No floating-point atomics; bitwise reproducible; no host synchronisation; all element offsets are 64-bit.
+ * TADMM_ERR_INVALID, with nothing launched: a NULL handle or descriptor, npairs outside [1, max], n < 1, an unknown
+ * dtype or group, s or t NULL, a pointer not aligned to its element, terms_dev or loss_dev NULL.  TADMM_ERR_UNSUPPORTED:
+ * more than 2^31 - 1 chunks.  TADMM_ERR_WORKSPACE: workspace NULL, misaligned or short. */
+#define TADMM_LAYER_MSE_MAX_PAIRS 32
+enum { TADMM_LAYER_MSE_ATT = 0, TADMM_LAYER_MSE_REP = 1 };
+typedef struct {
+  const void* s; const void* t;
+  float* grad;                                /* nullable */
+  int64_t n;
+  double scale;
+  float thr;
+  int32_t clamp;                              /* 0: thr is not read */
+  int32_t group;                              /* TADMM_LAYER_MSE_ATT | TADMM_LAYER_MSE_REP */
+  int32_t reserved;
+} tadmm_layer_mse_pair;
+typedef struct {
+  tadmm_layer_mse_pair pairs[TADMM_LAYER_MSE_MAX_PAIRS];
+  void* workspace; size_t workspace_bytes;
+  double* terms_dev;                          /* [npairs] */
+  double* loss_dev;                           /* [attention, hidden] */
+  float* loss_f32_dev;                        /* nullable */
+  int32_t npairs;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 */
+} tadmm_layer_mse_desc;
+/* sizeof(tadmm_layer_mse_desc) as the library was built */
+int tadmm_layer_mse_desc_bytes(void);
+int tadmm_layer_mse_max_pairs(void);
+int tadmm_layer_mse_geometry(int* chunk_elems, int* max_blocks);
+int tadmm_layer_mse_workspace_bytes(const tadmm_layer_mse_desc* d, size_t* bytes);
+int tadmm_layer_mse(tadmm_handle h, const tadmm_layer_mse_desc* d, void* stream);
+
 /* G = A A^T (m<=n) or A^T A (m>n) of a row-major float32 m x n matrix, exact fp32 products
  * accumulated in fp64 on v_mfma_f64_16x16x4_f64.  G is written as double[Npad][ldg] (zero padded; see tadmm_gram_ld), N=min(m,n).
  * partial_dev: scratch of tadmm_gram_scratch_bytes(m,n). */
