@@ -30,32 +30,9 @@
 // Grids and the row-to-workgroup map depend on (rows, hidden, dtype) alone; no atomics: bitwise reproducible.
 // Accesses: VEC elements = 16 bytes when every base is 16-byte aligned, the row strides are whole 16-byte units and
 // hidden is a multiple of VEC; one element otherwise.
-#include "host.h"
+#include "rownorm_common.h"
 
 namespace tadmm {
-
-struct bn_bf16 { uint16_t x; };
-struct bn_f16 { _Float16 x; };
-
-__device__ __forceinline__ float bn_widen(float v) { return v; }
-__device__ __forceinline__ float bn_widen(bn_bf16 v) { return __uint_as_float((uint32_t)v.x << 16); }
-__device__ __forceinline__ float bn_widen(bn_f16 v) { return (float)v.x; }
-
-template <typename T> __device__ __forceinline__ T bn_narrow(float v);
-template <> __device__ __forceinline__ float bn_narrow<float>(float v) { return v; }
-template <> __device__ __forceinline__ bn_bf16 bn_narrow<bn_bf16>(float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return bn_bf16{(uint16_t)((u >> 16) | 0x40)};     // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                                       // nearest even
-  return bn_bf16{(uint16_t)(u >> 16)};
-}
-template <> __device__ __forceinline__ bn_f16 bn_narrow<bn_f16>(float v) { return bn_f16{(_Float16)v}; }
-
-template <typename T, int N> struct alignas(sizeof(T) * N) BnPack { T v[N]; };
-
-constexpr int kBnMaxNV = 32;                 // values of a row a lane holds at most
-constexpr int kBnHmax = 64 * kBnMaxNV;       // widest row
-constexpr int kBnFwdGrid = 1024, kBnBwdGrid = 512;
 
 struct BnArgs {
   const void* x; const void* res;
@@ -70,59 +47,6 @@ struct BnArgs {
   int64_t rows;
   int32_t hidden, hp, param_f32;
 };
-
-template <typename F>
-__device__ __forceinline__ F bn_wave_sum(F v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// xhat, the one expression of forward and backward: the difference of two float32 values is exact in double, so xhat
-// carries the rounding of rstd and its own, nothing else (a float32 difference and product would add two more, which
-// the sum over rows of g xhat amplifies where the terms cancel)
-__device__ __forceinline__ float bn_xhat(float s, float mean, float rstd) {
-  return (float)(((double)s - (double)mean) * (double)rstd);
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void bn_load(const T* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 1) {
-    v[0] = bn_widen(p[0]);
-  } else {
-    const BnPack<T, VEC> t = *reinterpret_cast<const BnPack<T, VEC>*>(p);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) v[j] = bn_widen(t.v[j]);
-  }
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void bn_store(T* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 1) {
-    p[0] = bn_narrow<T>(v[0]);
-  } else {
-    BnPack<T, VEC> t;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) t.v[j] = bn_narrow<T>(v[j]);
-    *reinterpret_cast<BnPack<T, VEC>*>(p) = t;
-  }
-}
-
-// gamma or beta of the columns a lane owns: float32 or T, element loads (once per wave)
-template <typename T, int VEC, int CH>
-__device__ __forceinline__ void bn_load_param(const void* __restrict__ p, bool f32, int hidden, int lane,
-                                              float (&v)[CH][VEC]) {
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = (i * 64 + lane) * VEC;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float t = 0.f;
-      if (c < hidden) t = f32 ? ((const float*)p)[c + j] : bn_widen(((const T*)p)[c + j]);
-      v[i][j] = t;
-    }
-  }
-}
 
 // s = x keep / (1 - p) + res of row r for the columns a lane owns (zeros beyond the row); bit (i * VEC + j) of `kept`
 // is set where the element was kept (all ones without dropout).  The one expression of s, forward and backward.
@@ -323,17 +247,16 @@ __global__ __launch_bounds__(256) void bertnorm_param_kernel(const float* __rest
   if (dbeta) dbeta[c] = (float)tb;
 }
 
+void bn_param_launch(const float* part, int nwg, int hidden, int hp, float* dgamma, float* dbeta, hipStream_t s) {
+  hipLaunchKernelGGL(bertnorm_param_kernel, dim3((unsigned)((hidden + 15) / 16)), dim3(256), 0, s, part, nwg, hidden, hp,
+                     dgamma, dbeta);
+}
+
 }  // namespace tadmm
 
 using namespace tadmm;
 
 namespace {
-
-int bn_grid(int64_t rows, int cap) { return (int)std::min<int64_t>((rows + 3) / 4, cap); }
-int bn_hp(int hidden) { return (hidden + 3) & ~3; }
-size_t bn_ws_bytes(int64_t rows, int hidden) {
-  return align_up((size_t)bn_grid(rows, kBnBwdGrid) * 2 * bn_hp(hidden) * sizeof(float), 256);
-}
 
 template <typename T, bool BWD>
 void bn_launch(const BnArgs& a, bool wide, hipStream_t s) {
@@ -468,8 +391,7 @@ int tadmm_bertnorm_bwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* strea
   if (d->dtype == TADMM_CHAIN_F32) bn_launch<float, true>(a, wide, s);
   else bn_launch<bn_bf16, true>(a, wide, s);
   if (params)
-    hipLaunchKernelGGL(bertnorm_param_kernel, dim3((unsigned)((d->hidden + 15) / 16)), dim3(256), 0, s,
-                       (const float*)a.part, bn_grid(d->rows, kBnBwdGrid), d->hidden, a.hp, d->dgamma, d->dbeta);
+    bn_param_launch(a.part, bn_grid(d->rows, kBnBwdGrid), d->hidden, a.hp, d->dgamma, d->dbeta, s);
   HIP_OK(h, hipGetLastError());
   return TADMM_OK;
 }

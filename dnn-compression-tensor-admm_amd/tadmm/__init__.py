@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, vit_tt.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -37,7 +37,13 @@ def __getattr__(name):
         "BertPooler": ("bert_layers", "BertPooler"),
         "stiefel_step": ("ops", "stiefel_step"), "stiefel_project_": ("ops", "stiefel_project_"),
     }
-    if name == "optimization":      # the module itself, as the reference's scripts import it
+    # vit_tt.py: the modules and the twelve factories
+    for attr in ("DropPath", "PatchEmbed", "TTAttention", "TTMlp", "TTBlock", "TTVisionTransformer"):
+        table[attr] = ("vit_layers", attr)
+    for kind in ("ttm", "ttr", "tkm", "tkr"):
+        for arch in ("vit_small", "deit_tiny", "deit_small"):
+            table[f"{kind}_{arch}_patch16_224"] = ("vit_layers", f"{kind}_{arch}_patch16_224")
+    if name == "optimization":    # the module itself, as the reference's scripts import it
         return importlib.import_module(".optimization", __name__)
     if name in table:
         mod, attr = table[name]

@@ -210,6 +210,20 @@ class BertNormDesc(C.Structure):
     ]
 
 
+class PreNormDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("b", C.c_void_p),
+        ("x_ld", C.c_int64), ("b_ld", C.c_int64),
+        ("keep", C.c_void_p), ("path_keep", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+        ("s", C.c_void_p), ("y", C.c_void_p), ("stats", C.c_void_p), ("g_y", C.c_void_p), ("g_s", C.c_void_p),
+        ("dx", C.c_void_p), ("db", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("p", C.c_double), ("p_path", C.c_double), ("eps", C.c_double),
+        ("rows", C.c_int64), ("rows_per_sample", C.c_int64),
+        ("hidden", C.c_int32), ("dtype", C.c_int32), ("param_dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -350,6 +364,11 @@ ABI = {
     "tadmm_bertnorm_workspace_bytes": (C.c_int, [C.POINTER(BertNormDesc), C.POINTER(C.c_size_t)]),
     "tadmm_bertnorm_fwd": (C.c_int, [C.c_void_p, C.POINTER(BertNormDesc), C.c_void_p]),
     "tadmm_bertnorm_bwd": (C.c_int, [C.c_void_p, C.POINTER(BertNormDesc), C.c_void_p]),
+    "tadmm_prenorm_desc_bytes": (C.c_int, []),
+    "tadmm_prenorm_fits": (C.c_int, [C.POINTER(PreNormDesc), C.POINTER(C.c_int)]),
+    "tadmm_prenorm_workspace_bytes": (C.c_int, [C.POINTER(PreNormDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_prenorm_fwd": (C.c_int, [C.c_void_p, C.POINTER(PreNormDesc), C.c_void_p]),
+    "tadmm_prenorm_bwd": (C.c_int, [C.c_void_p, C.POINTER(PreNormDesc), C.c_void_p]),
     "tadmm_core_conv_desc_bytes": (C.c_int, []),
     "tadmm_core_conv_fwd": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
     "tadmm_core_conv_dgrad": (C.c_int, [C.c_void_p, C.POINTER(CoreConvDesc), C.c_void_p]),
@@ -458,6 +477,8 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_attn_desc layout mismatch")
         if lib.tadmm_bertnorm_desc_bytes() != C.sizeof(BertNormDesc):
             raise TadmmLibraryError(f"{path}: tadmm_bertnorm_desc layout mismatch")
+        if lib.tadmm_prenorm_desc_bytes() != C.sizeof(PreNormDesc):
+            raise TadmmLibraryError(f"{path}: tadmm_prenorm_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):
             raise TadmmLibraryError(f"{path}: tadmm_core_conv_desc layout mismatch")
         if lib.tadmm_dgemm_tile_prob_bytes() != C.sizeof(DgemmTileProb):

@@ -1407,3 +1407,156 @@ def residual_layer_norm(x, res, weight, bias, *, eps: float = 1e-12, dropout_p: 
     y = _BertNormFn.apply(x.reshape(rows, hidden), None if res is None else res.reshape(rows, hidden), weight, bias,
                           keep.reshape(rows, hidden) if p > 0.0 else None, float(eps), p)
     return y.view(x.shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Pre-norm block tail (csrc/prenorm.hip): x + drop_path(dropout(branch)) and the LayerNorm of that sum, the step between
+# the branches of vit_tt.py: TTBlock (timm's Block.forward) -- two outputs, the stream and what the next branch reads.
+# ---------------------------------------------------------------------------------------------------------------
+class _PreNormFn(torch.autograd.Function):
+    """x, b: (rows, hidden).  Returns (s, y); the backward recomputes xhat from the saved output s and (mean, rstd)."""
+
+    @staticmethod
+    def forward(ctx, x, b, weight, bias, keep, path_keep, eps, p, p_path, nper):
+        need = any(ctx.needs_input_grad[:4])
+        ctx.set_materialize_grads(False)
+        s, y, stats = ops.prenorm_fwd(x, b, weight, bias, eps=eps, p=p, keep=keep, p_path=p_path, path_keep=path_keep,
+                                      rows_per_sample=nper, need_stats=need)
+        if need:
+            ctx.save_for_backward(s, weight, stats)
+        ctx.keep, ctx.path_keep, ctx.cfg = keep, path_keep, (eps, p, p_path, nper)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, g_s, g_y):
+        if g_s is None and g_y is None:
+            return (None,) * 10
+        s, weight, stats = ctx.saved_tensors
+        eps, p, p_path, nper = ctx.cfg
+        need = ctx.needs_input_grad
+        dx, db, dgamma, dbeta = ops.prenorm_bwd(s, weight, stats, g_y, g_s, eps=eps, p=p, keep=ctx.keep, p_path=p_path,
+                                                path_keep=ctx.path_keep, rows_per_sample=nper, need=need[:4])
+        if dgamma is not None:
+            dgamma = dgamma.to(weight.dtype)
+        if dbeta is not None:
+            dbeta = dbeta.to(weight.dtype)
+        return (dx, db, dgamma, dbeta) + (None,) * 6
+
+
+def _add_layer_norm_args(x, branch, weight, bias, dropout_p, drop_path_p, keep, path_keep, who):
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or x.shape[-1] < 1:
+        raise ValueError(f"{who}: x must be a (B, N, C) or (rows, C) tensor with C >= 1")
+    if not isinstance(branch, torch.Tensor) or branch.shape != x.shape:
+        raise ValueError(f"{who}: branch must have the shape of x")
+    for n, t in (("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (x.shape[-1],):
+            raise ValueError(f"{who}: {n} must be a ({x.shape[-1]},) tensor")
+    for n, r in (("dropout_p", dropout_p), ("drop_path_p", drop_path_p)):
+        if not 0.0 <= float(r) < 1.0:
+            raise ValueError(f"{who}: {n} must be in [0, 1) (got {r})")
+    if keep is not None and (not isinstance(keep, torch.Tensor) or keep.shape != x.shape):
+        raise ValueError(f"{who}: keep must have the shape of x")
+    if path_keep is not None and (not isinstance(path_keep, torch.Tensor) or tuple(path_keep.shape) != (x.shape[0],)):
+        raise ValueError(f"{who}: path_keep must be a ({x.shape[0]},) tensor")
+
+
+def drop_path_keep_mask(B: int, p: float, device, generator=None) -> torch.Tensor:
+    """The byte tensor (B,) of the samples a DropPath at rate p keeps, drawn with torch's generator (so that a seed
+    reproduces a run and both routes of `add_layer_norm` can be handed the same mask).  timm keeps a sample where
+    floor(1 - p + rand) is 1, which is rand >= p."""
+    return (torch.rand((B,), device=device, generator=generator) >= p).to(torch.uint8)
+
+
+def add_layer_norm_composed(x, branch, weight, bias, *, eps: float = 1e-6, dropout_p: float = 0.0,
+                            drop_path_p: float = 0.0, training: bool = False, keep=None, path_keep=None):
+    """`add_layer_norm` from torch operations, under autograd, on any device: `F.dropout` of the branch (or `keep` /
+    (1 - p) where a mask is given), timm's DropPath arithmetic `x.div(keep_prob) * floor(keep_prob + rand((B, 1, 1)))`
+    (or `path_keep` in place of the drawn factor), the add, `F.layer_norm`.  The route for what the launch refuses and
+    the yardstick of tests/test_gpu_prenorm.py and scripts/bench_vit_block.py.  Parameters of another type than x are
+    converted.  Returns (stream, normed)."""
+    _add_layer_norm_args(x, branch, weight, bias, dropout_p, drop_path_p, keep, path_keep, "add_layer_norm_composed")
+    h = branch
+    if training and dropout_p > 0.0:
+        if keep is None:
+            h = F.dropout(h, dropout_p, True)
+        else:
+            h = h * (keep != 0).to(h.dtype) / (1.0 - dropout_p)
+    if training and drop_path_p > 0.0:
+        keep_prob = 1.0 - drop_path_p
+        shape = (x.shape[0],) + (1,) * (x.dim() - 1)
+        if path_keep is None:
+            factor = (keep_prob + torch.rand(shape, dtype=h.dtype, device=h.device)).floor_()
+        else:
+            factor = (path_keep != 0).to(h.dtype).view(shape)
+        h = h.div(keep_prob) * factor
+    s = x + h
+    return s, F.layer_norm(s, (s.shape[-1],), weight.to(s.dtype), bias.to(s.dtype), eps)
+
+
+def add_layer_norm_launch_refusal(is_cuda: bool, dtype, rows: int, hidden: int, grad: bool, param_dtype=None,
+                                  foreign: bool = False):
+    """None when csrc/prenorm.hip takes a call with these properties, else the reason it does not (a string): CPU
+    tensors, a type other than float32 / bfloat16 / float16, float16 with gradients, no rows, a row wider than the
+    launch holds, parameters that are neither float32 nor of the type of x, or a branch, parameter or keep tensor of
+    another type or on another device (`foreign`).  A pure function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    if dtype not in ops.PRENORM_DTYPES:
+        return f"{dtype} operands"
+    if dtype == torch.float16 and grad:
+        return "float16 with gradients"
+    if rows < 1 or hidden < 1 or not ops.prenorm_fits(hidden, dtype):
+        return f"rows = {rows}, hidden = {hidden}"
+    if param_dtype is not None and param_dtype not in (torch.float32, dtype):
+        return f"{param_dtype} parameters beside {dtype} operands"
+    if foreign:
+        return "a branch, parameter or keep tensor of another type or on another device"
+    return None
+
+
+def add_layer_norm(x, branch, weight, bias, *, eps: float = 1e-6, dropout_p: float = 0.0, drop_path_p: float = 0.0,
+                   training: bool = False, keep=None, path_keep=None, route: str = None):
+    """(stream, normed): the step between the branches of a pre-norm transformer block,
+
+        stream = x + branch * keep / (1 - p) * path_keep[sample] / (1 - p_path)
+        normed = weight * (stream - mean(stream)) / sqrt(var(stream) + eps) + bias
+
+    with the biased variance and eps inside the root (nn.LayerNorm).  x: (B, N, C), a sample being x[b], or (rows, C)
+    with every row its own sample.  Dropout and DropPath act only when `training` and their rate is > 0: `keep` (the
+    shape of x) and `path_keep` ((B,)), bytes with nonzero = kept, are drawn with torch's generator when not given.
+    Both outputs are differentiable in x, branch, weight and bias; the gradients of x and branch are always two
+    tensors.  `route`: None (the launch where it takes the call and the measured rule `ops.prenorm_pays` says it is
+    ahead), "launch" (csrc/prenorm.hip: one launch forward, two backward; the statistics are those of the stream as
+    stored in the type of x) or "composed" (torch operations).  The launch takes HIP tensors of float32 or bfloat16
+    (float16 without gradients) with at most `ops.bertnorm_hmax()` columns and parameters in float32 or the type of x,
+    read in place where the strides allow it.  Everything else goes to the composed route under `route=None` and raises
+    under `route="launch"`."""
+    who = "add_layer_norm"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    _add_layer_norm_args(x, branch, weight, bias, dropout_p, drop_path_p, keep, path_keep, who)
+    hidden = x.shape[-1]
+    rows = x.numel() // hidden
+    nper = x.shape[1] if x.dim() == 3 else 1
+    p = float(dropout_p) if training else 0.0
+    p_path = float(drop_path_p) if training else 0.0
+    grad = _needs_grad(x, branch, weight, bias)
+    foreign = branch.dtype != x.dtype or branch.device != x.device or weight.device != x.device \
+        or bias.device != x.device or weight.dtype != bias.dtype \
+        or (keep is not None and p > 0.0 and keep.device != x.device) \
+        or (path_keep is not None and p_path > 0.0 and path_keep.device != x.device)
+    why = add_layer_norm_launch_refusal(x.is_cuda, x.dtype, rows, hidden, grad, weight.dtype, foreign)
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    launch = why is None and (route == "launch" or (route is None and ops.prenorm_pays(rows, hidden, x.dtype, grad)))
+    if not launch:
+        return add_layer_norm_composed(x, branch, weight, bias, eps=eps, dropout_p=dropout_p, drop_path_p=drop_path_p,
+                                       training=training, keep=keep, path_keep=path_keep)
+    if p > 0.0 and keep is None:
+        keep = residual_keep_mask(x.shape, p, x.device)
+    if p_path > 0.0 and path_keep is None:
+        path_keep = drop_path_keep_mask(x.shape[0], p_path, x.device)
+    s, y = _PreNormFn.apply(x.reshape(rows, hidden), branch.reshape(rows, hidden), weight, bias,
+                            keep.reshape(rows, hidden) if p > 0.0 else None, path_keep if p_path > 0.0 else None,
+                            float(eps), p, p_path, int(nper))
+    return s.view(x.shape), y.view(x.shape)

@@ -2397,3 +2397,153 @@ def bertnorm_pays(rows: int, hidden: int, dtype, grad: bool = False) -> bool:
     if grad:
         return dtype == torch.float32 and n >= 16384 * 768
     return n >= (16384 * 312 if dtype == torch.float32 else 16384 * 768)
+
+
+# ------------------------------------------------------------------ pre-norm block tail (csrc/prenorm.hip)
+PRENORM_DTYPES = BERTNORM_DTYPES
+
+
+def prenorm_fits(hidden: int, dtype=torch.float32) -> bool:
+    """True when the launches take rows of `hidden` columns (`tadmm_prenorm_fits`: 1 <= hidden <= `bertnorm_hmax()`).
+    Raises TadmmError for hidden < 1.  Host only."""
+    dsc = _cabi.PreNormDesc()
+    dsc.hidden, dsc.dtype = int(hidden), PRENORM_DTYPES[dtype]
+    rc = _cabi.load().tadmm_prenorm_fits(C.byref(dsc), None)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_prenorm_fits: hidden = {hidden}")
+    return rc == 1
+
+
+def prenorm_workspace_bytes(rows: int, hidden: int) -> int:
+    """Bytes of the backward's workspace (`tadmm_prenorm_workspace_bytes`: that of `bertnorm_workspace_bytes`, one
+    float32 (2, hidden rounded up to 4) partial per workgroup of the row launch).  Host only."""
+    dsc = _cabi.PreNormDesc()
+    dsc.rows, dsc.hidden = int(rows), int(hidden)
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_prenorm_workspace_bytes(C.byref(dsc), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_prenorm_workspace_bytes: rows = {rows}, hidden = {hidden}")
+    return int(size.value)
+
+
+def _prenorm_desc(like, gamma, beta, p, keep, p_path, path_keep, rows_per_sample, eps, who):
+    """The descriptor fields forward and backward share, for a (rows, hidden) tensor `like` that fixes shape, type and
+    device.  Returns (descriptor, tensors to keep alive, (rows, hidden, device, dtype))."""
+    like = _operand(like, who, "x", tuple(PRENORM_DTYPES), layout=None)
+    if like.dim() != 2 or like.shape[1] < 1:
+        raise TadmmError(-1, f"{who}: x must be (rows, hidden >= 1) (got {tuple(like.shape)})")
+    rows, hidden = like.shape
+    dev, dt = like.device, like.dtype
+    nper = int(rows_per_sample)
+    if nper < 1 or rows % nper:
+        raise TadmmError(-1, f"{who}: {rows} rows are not whole samples of {nper} rows")
+    dsc = _cabi.PreNormDesc()
+    hold = []
+    pdt = gamma.dtype if isinstance(gamma, torch.Tensor) else None
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is None and name == "beta":
+            continue
+        t = _operand(t, who, name, (torch.float32, dt), (hidden,), layout="copy")
+        if t.dtype != pdt:
+            raise TadmmError(-1, f"{who}: gamma and beta must be of one type (got {pdt} and {t.dtype})")
+        hold.append(t)
+        setattr(dsc, name, t.data_ptr())
+    p, p_path = float(p), float(p_path)
+    for rate, name, t, shape in ((p, "keep", keep, (rows, hidden)), (p_path, "path_keep", path_keep, (rows // nper,))):
+        if rate > 0.0:
+            if t is None:
+                raise TadmmError(-1, f"{who}: a rate of {rate} needs the {name} tensor")
+            if t.dtype == torch.bool:
+                t = t.view(torch.uint8)
+            t = _operand(t, who, name, (torch.uint8,), shape, layout="copy")
+            hold.append(t)
+            setattr(dsc, name, t.data_ptr())
+    for t in hold:
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: an operand on {t.device}, x on {dev}")
+    dsc.p, dsc.p_path, dsc.eps = p, p_path, float(eps)
+    dsc.rows, dsc.rows_per_sample, dsc.hidden = rows, nper, hidden
+    dsc.dtype, dsc.param_dtype = PRENORM_DTYPES[dt], PRENORM_DTYPES[pdt]
+    return dsc, hold, (rows, hidden, dev, dt)
+
+
+def prenorm_fwd(x, b, gamma, beta, *, eps: float = 1e-6, p: float = 0.0, keep=None, p_path: float = 0.0,
+                path_keep=None, rows_per_sample: int = 1, need_stats: bool = False):
+    """(s, y, stats) of `tadmm_prenorm_fwd`: s = x + b keep / (1 - p) path_keep[sample] / (1 - p_path), y = LayerNorm(s)
+    over the last dimension, with the statistics of s as stored.  x, b: (rows, hidden) float32, bfloat16 or float16, read
+    in place (unit element stride, any row stride >= hidden, any element alignment); rows = B * `rows_per_sample`.
+    `gamma`, `beta`: (hidden,), both float32 or both of the type of x.  `keep` (rows, hidden) and `path_keep` (B,) uint8 /
+    bool, read when their rate is > 0.  s and y (rows, hidden) contiguous in the type of x; stats float32 (rows, 2) =
+    (mean, 1 / sqrt(var + eps)) (None unless `need_stats`; the backward reads it).  One launch; nothing synchronises."""
+    who = "prenorm_fwd"
+    dsc, hold, (rows, hidden, dev, dt) = _prenorm_desc(x, gamma, beta, p, keep, p_path, path_keep, rows_per_sample, eps, who)
+    x, dsc.x_ld = _bertnorm_rows(x, who, "x", (rows, hidden), dt)
+    b, dsc.b_ld = _bertnorm_rows(b, who, "b", (rows, hidden), dt)
+    if b.device != dev:
+        raise TadmmError(-1, f"{who}: b on {b.device}, x on {dev}")
+    dsc.x, dsc.b = x.data_ptr(), b.data_ptr()
+    s = torch.empty((rows, hidden), dtype=dt, device=dev)
+    y = torch.empty((rows, hidden), dtype=dt, device=dev)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=dev) if need_stats else None
+    dsc.s, dsc.y = s.data_ptr(), y.data_ptr()
+    dsc.stats = None if stats is None else stats.data_ptr()
+    h = _handle(dev)
+    h.check(h.lib.tadmm_prenorm_fwd(h.ptr, C.byref(dsc), _stream(dev)))
+    return s, y, stats
+
+
+def prenorm_bwd(s, gamma, stats, g_y, g_s, *, eps: float = 1e-6, p: float = 0.0, keep=None, p_path: float = 0.0,
+                path_keep=None, rows_per_sample: int = 1, need=(True, True, True, True)):
+    """(dx, db, dgamma, dbeta) of `tadmm_prenorm_bwd` for the gradients `g_y` of y and `g_s` of s ((rows, hidden),
+    float32 or bfloat16; either may be None, not both).  `s` and `stats` are what `prenorm_fwd(need_stats=True)`
+    returned; x and b are not needed.  dx and db are two tensors in the type of s, dgamma and dbeta float32 (hidden,);
+    `need` says which of the four are wanted (None for the others).  Two launches (one when neither dgamma nor dbeta is
+    wanted), no atomics, bitwise reproducible; nothing synchronises."""
+    who = "prenorm_bwd"
+    dsc, hold, (rows, hidden, dev, dt) = _prenorm_desc(s, gamma, None, p, keep, p_path, path_keep, rows_per_sample, eps, who)
+    s = _operand(s, who, "s", (dt,), (rows, hidden), layout="copy")
+    stats = _operand(stats, who, "stats", (torch.float32,), (rows, 2), layout="copy")
+    dsc.s, dsc.stats = s.data_ptr(), stats.data_ptr()
+    if g_y is None and g_s is None:
+        raise TadmmError(-1, f"{who}: g_y and g_s are both None")
+    if g_y is not None:
+        g_y = _operand(g_y, who, "g_y", (dt,), (rows, hidden), layout="copy")
+        dsc.g_y = g_y.data_ptr()
+    if g_s is not None:
+        g_s = _operand(g_s, who, "g_s", (dt,), (rows, hidden), layout="copy")
+        dsc.g_s = g_s.data_ptr()
+    want_dx, want_db, want_dg, want_dbeta = (bool(n) for n in need)
+    dx = torch.empty((rows, hidden), dtype=dt, device=dev) if want_dx else None
+    db = torch.empty((rows, hidden), dtype=dt, device=dev) if want_db else None
+    dgamma = torch.empty(hidden, dtype=torch.float32, device=dev) if want_dg else None
+    dbeta = torch.empty(hidden, dtype=torch.float32, device=dev) if want_dbeta else None
+    for name, t in (("dx", dx), ("db", db), ("dgamma", dgamma), ("dbeta", dbeta)):
+        setattr(dsc, name, None if t is None else t.data_ptr())
+    if want_dg or want_dbeta:
+        nbytes = prenorm_workspace_bytes(rows, hidden)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    h = _handle(dev)
+    h.check(h.lib.tadmm_prenorm_bwd(h.ptr, C.byref(dsc), _stream(dev)))
+    return dx, db, dgamma, dbeta
+
+
+def prenorm_pays(rows: int, hidden: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.add_layer_norm` sends a call the launch can take to it and not to the composed torch route.
+    A pure function of its arguments.  Measured (scripts/bench_vit_block.py, two runs) at rows =
+    197 B for B in {1, 64, 256}, hidden in {192, 384, 768}, float32 and bfloat16, a forward under no_grad and a training
+    step with drop_path_p = 0.1, against `add_layer_norm_composed` in the same run.  Up to 12608 x 384 both routes are
+    bound by the host and the composed route is ahead or level (forward 0.018 - 0.027 against 0.027 ms, training step
+    0.12 - 0.21 against 0.14 - 0.30 ms).  The launch's slowest window is below the composed route's fastest in both runs
+    for the forward of both types at 50432 x 192 and 12608 x 768 (one element count; 1.1x - 2.4x) and everything
+    larger (1.2x - 1.8x), the float32 training step at 50432 x 384, 12608 x 768 and 50432 x 768 (1.2x - 2.5x; at
+    50432 x 192 one run has the composed route ahead), the bfloat16 training step at 50432 rows of all three widths
+    (1.4x - 1.9x; behind at 12608 x 768).  So: a forward from 50432 x 192 elements, a float32 training step from
+    50432 x 384, a 16-bit training step from 50432 rows of at least 192 columns.  Not measured: row counts between 12608
+    and 50432 below 768 columns and beyond 50432, other widths, float16 (treated as bfloat16), dropout on the branch."""
+    n = int(rows) * int(hidden)
+    if not grad:
+        return n >= 50432 * 192
+    if dtype == torch.float32:
+        return n >= 50432 * 384
+    return rows >= 50432 and hidden >= 192

@@ -785,6 +785,66 @@ int tadmm_bertnorm_workspace_bytes(const tadmm_bertnorm_desc* d, size_t* bytes);
 int tadmm_bertnorm_fwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* stream);
 int tadmm_bertnorm_bwd(tadmm_handle h, const tadmm_bertnorm_desc* d, void* stream);
 
+/* ---- Pre-norm block tail: branch dropout, DropPath, residual add and LayerNorm in one launch (csrc/prenorm.hip) --------
+ * vit_tt.py: TTBlock through timm's Block.forward, x = x + drop_path(branch(norm(x))), where the next branch reads the
+ * LayerNorm of the new stream: both the stream and its LayerNorm are outputs.  x (the stream), b (the branch output):
+ * (rows, hidden) of `dtype`, read in place: unit element stride, row strides x_ld / b_ld >= hidden in elements, any
+ * element-aligned base (16-byte accesses when every base is 16-byte aligned, the row strides are whole 16-byte units and
+ * hidden is a multiple of 16 bytes of elements; element accesses otherwise).  rows = B * rows_per_sample.
+ *   scale_i = (path_keep[i / rows_per_sample] != 0) / (1 - p_path)    path_keep: bytes (B), read when p_path > 0; else 1
+ *   s_ij    = x_ij + scale_i b_ij (keep_ij != 0) / (1 - p)            keep: bytes (rows, hidden) contiguous, read when p > 0
+ *   mean_i, rstd_i = 1 / sqrt(var_i + eps) of s_i as stored (rounded to `dtype`), biased variance, sums added in double
+ *   y_ij    = gamma_j (s_ij - mean_i) rstd_i + beta_j                 gamma, beta: (hidden) of `param_dtype`
+ * tadmm_prenorm_fwd writes s and y ((rows, hidden) contiguous, of `dtype`, two buffers) and stats (float32 (rows, 2) =
+ * (mean, rstd); nullable).  One launch.  A row of a sample that DropPath drops has s == x bit for bit.
+ * tadmm_prenorm_bwd reads s (as the forward wrote it), stats, gamma, keep, path_keep and the gradients g_y of y and g_s of
+ * s (contiguous, of `dtype`; either may be NULL = zeros, not both) and writes, each nullable and contiguous of `dtype`,
+ *   dx_ij = g_s_ij + rstd_i (a_ij - mean_j a_i. - xhat_ij mean_j(a_i. xhat_i.)),  a = g_y gamma,  xhat = (s - mean) rstd
+ *   db_ij = dx_ij scale_i (keep_ij != 0) / (1 - p)                    (an exact zero in a dropped sample)
+ * (dx and db must be two buffers) and, each nullable, float32 (hidden): dgamma_j = sum_i g_y_ij xhat_ij, dbeta_j =
+ * sum_i g_y_ij.  Two launches: row blocks (per-workgroup partial sums to the workspace), then the fixed-order sum of the
+ * partials in double that tadmm_bertnorm_bwd uses; the second and the workspace (tadmm_prenorm_workspace_bytes, reads rows
+ * and hidden; 16-byte aligned) are needed only when dgamma or dbeta is given.  x, b, beta and y are not read.  No atomics;
+ * grids depend on (rows, hidden, dtype) alone: bitwise reproducible; no host synchronisation.
+ * tadmm_prenorm_fits is host only and reads hidden: 1 for 1 <= hidden <= HMAX (that of tadmm_bertnorm_fits; *hmax,
+ * nullable, receives it), 0 above, TADMM_ERR_INVALID for a NULL descriptor or hidden < 1.  The launches return
+ * TADMM_ERR_UNSUPPORTED where _fits returns 0 and TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or
+ * descriptor; rows < 0 or hidden < 1; rows_per_sample < 1 or rows not a multiple of it; an unknown dtype; TADMM_CHAIN_F16
+ * in _bwd; a param_dtype that is neither float32 nor dtype; p or p_path outside [0, 1); p > 0 without keep; p_path > 0
+ * without path_keep; eps negative or not finite; gamma or s NULL; a pointer not aligned to its element; in _fwd x, b, beta
+ * or y NULL, a row stride below hidden, y == s; in _bwd stats NULL, g_y and g_s both NULL, dx == db.
+ * TADMM_ERR_WORKSPACE: dgamma or dbeta given and the workspace NULL, misaligned or short.  rows == 0 succeeds and
+ * launches nothing. */
+typedef struct {
+  const void* x; const void* b;               /* forward */
+  int64_t x_ld, b_ld;                         /* row strides, elements */
+  const uint8_t* keep;                        /* (rows, hidden); required when p > 0 */
+  const uint8_t* path_keep;                   /* (rows / rows_per_sample); required when p_path > 0 */
+  const void* gamma; const void* beta;        /* (hidden) of param_dtype */
+  void* s;                                    /* forward writes it, backward reads it */
+  void* y;                                    /* forward */
+  float* stats;                               /* forward writes it (nullable), backward reads it */
+  const void* g_y; const void* g_s;           /* backward; either nullable */
+  void* dx; void* db;                         /* backward; each nullable */
+  float* dgamma; float* dbeta;                /* backward; each nullable */
+  void* workspace; size_t workspace_bytes;    /* backward with dgamma or dbeta */
+  double p;                                   /* dropout probability of the branch output, [0, 1) */
+  double p_path;                              /* DropPath probability, [0, 1) */
+  double eps;
+  int64_t rows;
+  int64_t rows_per_sample;
+  int32_t hidden;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (forward only) */
+  int32_t param_dtype;                        /* TADMM_CHAIN_F32 | dtype */
+  int32_t reserved;
+} tadmm_prenorm_desc;
+/* sizeof(tadmm_prenorm_desc) as the library was built */
+int tadmm_prenorm_desc_bytes(void);
+int tadmm_prenorm_fits(const tadmm_prenorm_desc* d, int* hmax);
+int tadmm_prenorm_workspace_bytes(const tadmm_prenorm_desc* d, size_t* bytes);
+int tadmm_prenorm_fwd(tadmm_handle h, const tadmm_prenorm_desc* d, void* stream);
+int tadmm_prenorm_bwd(tadmm_handle h, const tadmm_prenorm_desc* d, void* stream);
+
 /* ---- TinyBERT layer losses: masked attention MSE and hidden-state MSE with gradients (csrc/layermse.hip) -------------
  * xcompression/task_distill.py:810-828 (also task_distill1.py, task_distill2.py, general_distill.py:438-451) for all
  * pairs of a step in two launches.  A call carries npairs <= TADMM_LAYER_MSE_MAX_PAIRS pairs; pair i is s (student)
