@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, vit_tt.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, vit_tt.py, resnet_cifar_tt.py, resnet_inet_tt.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -43,8 +43,17 @@ def __getattr__(name):
     for kind in ("ttm", "ttr", "tkm", "tkr"):
         for arch in ("vit_small", "deit_tiny", "deit_small"):
             table[f"{kind}_{arch}_patch16_224"] = ("vit_layers", f"{kind}_{arch}_patch16_224")
-    if name == "optimization":    # the module itself, as the reference's scripts import it
-        return importlib.import_module(".optimization", __name__)
+    # resnet_cifar_tt.py and resnet_inet_tt.py: the factories (their names do not collide); both files define TTBasicBlock
+    # and TTResNet, so the classes are reached through the modules tadmm.resnet_cifar_layers / tadmm.resnet_inet_layers
+    for kind, archs in (("ttr", (20, 32, 56)), ("ttm", (20, 32)), ("tkr", (20, 32, 56)), ("tkm", (20, 32)),
+                        ("tkc", (20, 32)), ("stftkc", (32,))):
+        for depth in archs:
+            table[f"{kind}_resnet{depth}"] = ("resnet_cifar_layers", f"{kind}_resnet{depth}")
+    for fn in ("ttr_resnet18", "ttm_resnet18", "tkc_resnet18", "tkm_resnet18", "ttr_resnet34", "ttr_resnet50",
+               "tkr_resnet18", "tkr_resnet34", "tkr_resnet50", "tkm_resnet50", "tkc_resnet50"):
+        table[fn] = ("resnet_inet_layers", fn)
+    if name in ("optimization", "resnet_cifar_layers", "resnet_inet_layers"):    # the modules themselves
+        return importlib.import_module("." + name, __name__)
     if name in table:
         mod, attr = table[name]
         return getattr(importlib.import_module("." + mod, __name__), attr)

@@ -1560,3 +1560,175 @@ def add_layer_norm(x, branch, weight, bias, *, eps: float = 1e-6, dropout_p: flo
                             keep.reshape(rows, hidden) if p > 0.0 else None, path_keep if p_path > 0.0 else None,
                             float(eps), p, p_path, int(nper))
     return s.view(x.shape), y.view(x.shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ResNet block tail (csrc/bnact.hip): BatchNorm2d, the shortcut added over a channel window, ReLU -- relu(bn(conv(x)))
+# and relu(bn(conv(x)) + shortcut(x)) of resnet_cifar_tt.py and resnet_inet_tt.py.
+# ---------------------------------------------------------------------------------------------------------------
+class _BnActFn(torch.autograd.Function):
+    """x (N, C, H, W); `buffers` = (running_mean, running_var, num_batches_tracked), updated in place by the launch and
+    handed over as a tuple: they are no inputs of the graph."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, buffers, c0, training, momentum, eps, relu):
+        need = any(ctx.needs_input_grad[:4])
+        running_mean, running_var, nbt = buffers
+        y, stats = ops.bnact_fwd(x, weight, bias, running_mean, running_var, residual, c0=c0, training=training,
+                                 momentum=momentum, eps=eps, relu=relu, num_batches_tracked=nbt, need_stats=need)
+        if need:
+            ctx.save_for_backward(x, y, weight, stats)
+        ctx.cfg = (c0, 0 if residual is None else residual.shape[1], relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, weight, stats = ctx.saved_tensors
+        c0, cr, relu = ctx.cfg
+        need = ctx.needs_input_grad
+        dx, dres, dgamma, dbeta = ops.bnact_bwd(g, y if relu else None, x, weight, stats, relu=relu, c0=c0,
+                                                res_channels=cr, need=(need[0], need[3], need[1], need[2]))
+        return (dx, dgamma, dbeta, dres) + (None,) * 6
+
+
+def _batch_norm_act_args(x, running_mean, running_var, weight, bias, residual, c0, momentum, who):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be an (N, C, H, W) tensor")
+    c = x.shape[1]
+    for n, t in (("running_mean", running_mean), ("running_var", running_var), ("weight", weight), ("bias", bias)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (c,)):
+            raise ValueError(f"{who}: {n} must be a ({c},) tensor or None")
+    if momentum is not None and not 0.0 <= float(momentum) <= 1.0:
+        raise ValueError(f"{who}: momentum must be in [0, 1] or None (got {momentum})")
+    if residual is not None:
+        ok = isinstance(residual, torch.Tensor) and residual.dim() == 4 and residual.shape[1] >= 1 \
+            and (residual.shape[0], residual.shape[2], residual.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])
+        if not ok:
+            raise ValueError(f"{who}: residual must be ({x.shape[0]}, Cr, {x.shape[2]}, {x.shape[3]})")
+        if int(c0) < 0 or int(c0) + residual.shape[1] > c:
+            raise ValueError(f"{who}: the residual's channels [{c0}, {c0} + {residual.shape[1]}) are not inside the {c} of x")
+    elif int(c0) != 0:
+        raise ValueError(f"{who}: res_channel_offset without a residual")
+
+
+def batch_norm_act_composed(x, running_mean, running_var, weight, bias, residual=None, *, res_channel_offset: int = 0,
+                            training: bool, momentum=0.1, eps: float = 1e-5, relu: bool = True, num_batches_tracked=None):
+    """`batch_norm_act` from torch operations, under autograd, on any device and in float64: `F.batch_norm`, the
+    residual through `F.pad` over the channels where it is narrower than x, the add, `F.relu`.  As nn.BatchNorm2d does,
+    a training call first adds one to `num_batches_tracked` (where given and the running statistics are tracked) and
+    `momentum=None` is the cumulative average 1 / num_batches_tracked.  The route for what the launch refuses and the
+    yardstick of tests/test_gpu_bnact.py and scripts/bench_resnet_block.py."""
+    _batch_norm_act_args(x, running_mean, running_var, weight, bias, residual, res_channel_offset, momentum,
+                         "batch_norm_act_composed")
+    factor = 0.0 if momentum is None else float(momentum)
+    if training and running_mean is not None and num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+        if momentum is None:
+            factor = 1.0 / float(num_batches_tracked)
+    y = F.batch_norm(x, running_mean, running_var, weight, bias, training, factor, eps)
+    if residual is not None:
+        c0, extra = int(res_channel_offset), x.shape[1] - residual.shape[1]
+        if extra:
+            residual = F.pad(residual, (0, 0, 0, 0, c0, extra - c0), "constant", 0)
+        y = y + residual
+    return F.relu(y) if relu else y
+
+
+def batch_norm_act_launch_refusal(is_cuda: bool, dtype, shape, grad: bool, training: bool, contiguous: bool = True,
+                                  param_dtypes=(torch.float32,), affine: bool = True, tracked: bool = True,
+                                  momentum_given: bool = True, foreign: bool = False):
+    """None when csrc/bnact.hip takes a call with these properties, else the reason it does not (a string): CPU
+    tensors, a type other than float32 / bfloat16 / float16, float16 with gradients, eval mode with gradients, an x that
+    is not NCHW contiguous, more values per channel than the launch takes, parameters or running statistics that are
+    missing (`affine=False`, `track_running_stats=False`) or not float32, `momentum=None`, or an operand of another
+    type or on another device (`foreign`).  A pure function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    if dtype not in ops.BNACT_DTYPES:
+        return f"{dtype} operands"
+    if dtype == torch.float16 and grad:
+        return "float16 with gradients"
+    if grad and not training:
+        return "eval mode with gradients"
+    if not contiguous:
+        return "an x that is not NCHW contiguous"
+    if min(shape) < 1 or not ops.bnact_fits(*shape, dtype):
+        return f"shape = {tuple(shape)}"
+    if training and shape[0] * shape[2] * shape[3] < 2:
+        return "one value per channel in training"
+    if not affine:
+        return "affine=False"
+    if not tracked:
+        return "track_running_stats=False"
+    if any(d != torch.float32 for d in param_dtypes):
+        return "parameters or running statistics that are not float32"
+    if not momentum_given:
+        return "momentum=None"
+    if foreign:
+        return "a residual, parameter or buffer of another type or on another device"
+    return None
+
+
+def batch_norm_act(x, running_mean, running_var, weight, bias, residual=None, *, res_channel_offset: int = 0,
+                   training: bool, momentum=0.1, eps: float = 1e-5, relu: bool = True, num_batches_tracked=None,
+                   route: str = None):
+    """The tail of a ResNet block,
+
+        y = act(weight (x - mean) / sqrt(var + eps) + bias + residual),    act = relu or the identity,
+
+    over x (N, C, H, W) with the arguments of `F.batch_norm`: batch statistics (biased variance) when `training`, which
+    also updates `running_mean` / `running_var` in place (momentum, unbiased variance) and adds one to
+    `num_batches_tracked`; the running statistics otherwise.  `residual` (N, Cr, H, W) is added to the channels
+    [res_channel_offset, res_channel_offset + Cr) -- the whole of x, or the option-A shortcut
+    `x_in[:, :, ::2, ::2]` at offset planes // 4, read through its strides with neither the slice nor the zero padding
+    materialised.  Differentiable in x, weight, bias and residual.  `route`: None (the launch where it takes the call
+    and the measured rule `ops.bnact_pays` says it is ahead), "launch" (csrc/bnact.hip: two launches in training, one in
+    eval, two backward) or "composed" (torch operations).  The launch takes NCHW-contiguous HIP tensors of float32 or
+    bfloat16 (float16 without gradients) with float32 parameters and running statistics, a momentum, and gradients only
+    in training mode.  Everything else goes to the composed route under `route=None` and raises under `route="launch"`."""
+    who = "batch_norm_act"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    _batch_norm_act_args(x, running_mean, running_var, weight, bias, residual, res_channel_offset, momentum, who)
+    training = bool(training)
+    grad = _needs_grad(x, weight, bias, residual)
+    params = [t for t in (weight, bias, running_mean, running_var) if t is not None]
+    foreign = any(t.device != x.device for t in params) \
+        or (residual is not None and (residual.dtype != x.dtype or residual.device != x.device)) \
+        or (num_batches_tracked is not None and (num_batches_tracked.device != x.device
+                                                 or num_batches_tracked.dtype != torch.int64))
+    why = None
+    if route != "composed":
+        why = batch_norm_act_launch_refusal(x.is_cuda, x.dtype, tuple(x.shape), grad, training, x.is_contiguous(),
+                                            tuple(t.dtype for t in params), weight is not None and bias is not None,
+                                            running_mean is not None and running_var is not None, momentum is not None,
+                                            foreign)
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    n, c, h, w = x.shape
+    launch = route != "composed" and why is None and (
+        route == "launch" or ops.bnact_pays(n, c, h * w, x.dtype, grad, residual is not None))
+    if not launch:
+        return batch_norm_act_composed(x, running_mean, running_var, weight, bias, residual,
+                                       res_channel_offset=res_channel_offset, training=training, momentum=momentum,
+                                       eps=eps, relu=relu, num_batches_tracked=num_batches_tracked)
+    return _BnActFn.apply(x, weight, bias, residual, (running_mean, running_var, num_batches_tracked),
+                          int(res_channel_offset), training, float(momentum), float(eps), bool(relu))
+
+
+def batch_norm_act_module(bn, x, residual=None, res_channel_offset: int = 0, relu: bool = True, route: str = None):
+    """`batch_norm_act` with the parameters, buffers and mode of the module `bn`.  An nn.BatchNorm2d keeps its state-dict
+    keys and semantics (batch statistics in training mode or when it tracks none); any other norm layer is called as
+    it is and the residual and the ReLU are composed around it."""
+    if not isinstance(bn, torch.nn.BatchNorm2d):
+        y = bn(x)
+        if residual is not None:
+            extra = y.shape[1] - residual.shape[1]
+            if extra:
+                residual = F.pad(residual, (0, 0, 0, 0, res_channel_offset, extra - res_channel_offset), "constant", 0)
+            y = y + residual
+        return F.relu(y) if relu else y
+    training = bn.training or (bn.running_mean is None and bn.running_var is None)
+    return batch_norm_act(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, residual,
+                          res_channel_offset=res_channel_offset, training=training, momentum=bn.momentum, eps=bn.eps,
+                          relu=relu, num_batches_tracked=bn.num_batches_tracked if bn.training else None, route=route)

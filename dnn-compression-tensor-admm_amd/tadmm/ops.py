@@ -2547,3 +2547,166 @@ def prenorm_pays(rows: int, hidden: int, dtype, grad: bool = False) -> bool:
     if dtype == torch.float32:
         return n >= 50432 * 384
     return rows >= 50432 and hidden >= 192
+
+
+# ------------------------------------------------------------------ ResNet block tail (csrc/bnact.hip)
+BNACT_DTYPES = BERTNORM_DTYPES
+
+
+def _bnact_shape_desc(n, c, h, w, dtype):
+    dsc = _cabi.BnActDesc()
+    dsc.N, dsc.C, dsc.H, dsc.W, dsc.dtype = int(n), int(c), int(h), int(w), BNACT_DTYPES[dtype]
+    return dsc
+
+
+def bnact_max_m() -> int:
+    """The most values per channel (N H W) `tadmm_bnact_fwd` / `_bwd` take (what `tadmm_bnact_fits` reports).  Host only."""
+    m = C.c_int64()
+    _cabi.load().tadmm_bnact_fits(None, C.byref(m))
+    return int(m.value)
+
+
+def bnact_fits(n: int, c: int, h: int, w: int, dtype=torch.float32) -> bool:
+    """True when the launches take an (n, c, h, w) tensor (`tadmm_bnact_fits`: n h w <= `bnact_max_m()`).  Raises
+    TadmmError for a dimension < 1.  Host only."""
+    rc = _cabi.load().tadmm_bnact_fits(C.byref(_bnact_shape_desc(n, c, h, w, dtype)), None)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_bnact_fits: shape = {(n, c, h, w)}")
+    return rc == 1
+
+
+def bnact_workspace_bytes(n: int, c: int, h: int, w: int, dtype=torch.float32) -> int:
+    """Bytes of the workspace of the training forward and of the backward (`tadmm_bnact_workspace_bytes`: a pair of
+    doubles per channel and split for min(trips, 128, ceil(2048 / c)) splits, a trip being 1024 float32 or 2048 16-bit
+    values; rounded up to 256 bytes; never smaller for a larger n, h or w).  Host only."""
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_bnact_workspace_bytes(C.byref(_bnact_shape_desc(n, c, h, w, dtype)), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_bnact_workspace_bytes: shape = {(n, c, h, w)}")
+    return int(size.value)
+
+
+def _bnact_desc(x, gamma, who):
+    """The descriptor fields forward and backward share.  Returns (descriptor, tensors to keep alive, (shape, device,
+    dtype))."""
+    x = _operand(x, who, "x", tuple(BNACT_DTYPES), layout="copy")
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise TadmmError(-1, f"{who}: x must be (N, C, H, W) with every dimension >= 1 (got {tuple(x.shape)})")
+    n, c, h, w = x.shape
+    dsc = _bnact_shape_desc(n, c, h, w, x.dtype)
+    gamma = _operand(gamma, who, "gamma", (torch.float32,), (c,), layout="copy")
+    if gamma.device != x.device:
+        raise TadmmError(-1, f"{who}: gamma on {gamma.device}, x on {x.device}")
+    dsc.x, dsc.gamma = x.data_ptr(), gamma.data_ptr()
+    return dsc, [x, gamma], ((n, c, h, w), x.device, x.dtype)
+
+
+def bnact_fwd(x, gamma, beta, running_mean, running_var, res=None, *, c0: int = 0, training: bool, momentum: float = 0.1,
+              eps: float = 1e-5, relu: bool = True, num_batches_tracked=None, need_stats: bool = False):
+    """(y, stats) of `tadmm_bnact_fwd`: y = act(BatchNorm2d(x) + res) for x (N, C, H, W) float32, bfloat16 or float16
+    (a non-contiguous x is copied).  `gamma`, `beta`, `running_mean`, `running_var`: float32 (C,).  `res`: (N, Cr, H, W)
+    of the type of x with any non-negative strides, read in place and added to the channels [c0, c0 + Cr).  With
+    `training` the batch statistics are used, the running statistics (both or neither) are updated in place with
+    `momentum` and the unbiased variance, `num_batches_tracked` (int64 scalar tensor, optional) rises by one, and
+    stats is float32 (C, 2) = (mean, 1 / sqrt(var + eps)) when `need_stats` (the backward reads it); two launches.
+    Without, the running statistics are read and nothing but y is written; one launch.  Nothing synchronises."""
+    who = "bnact_fwd"
+    dsc, hold, ((n, c, h, w), dev, dt) = _bnact_desc(x, gamma, who)
+    named = [("beta", beta), ("running_mean", running_mean), ("running_var", running_var)]
+    for name, t in named:
+        if t is None and name != "beta" and training:
+            continue
+        # updated in place: a copy would take the update with it
+        t = _operand(t, who, name, (torch.float32,), (c,), layout="copy" if name == "beta" else "raise")
+        hold.append(t)
+        setattr(dsc, name, t.data_ptr())
+    if num_batches_tracked is not None and training:
+        nbt = _operand(num_batches_tracked, who, "num_batches_tracked", (torch.int64,), (), layout="raise")
+        hold.append(nbt)
+        dsc.num_batches_tracked = nbt.data_ptr()
+    if res is not None:
+        res = _operand(res, who, "res", (dt,), layout=None)
+        if res.dim() != 4 or (res.shape[0], res.shape[2], res.shape[3]) != (n, h, w):
+            raise TadmmError(-1, f"{who}: res must be ({n}, Cr, {h}, {w}) (got {tuple(res.shape)})")
+        hold.append(res)
+        dsc.res, dsc.c0, dsc.Cr = res.data_ptr(), int(c0), res.shape[1]
+        for i in range(4):
+            dsc.res_stride[i] = res.stride(i)
+    for t in hold:
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: an operand on {t.device}, x on {dev}")
+    dsc.eps, dsc.momentum, dsc.training, dsc.relu = float(eps), float(momentum), int(bool(training)), int(bool(relu))
+    y = torch.empty((n, c, h, w), dtype=dt, device=dev)
+    stats = torch.empty((c, 2), dtype=torch.float32, device=dev) if need_stats and training else None
+    dsc.y = y.data_ptr()
+    dsc.stats = None if stats is None else stats.data_ptr()
+    if training:
+        nbytes = bnact_workspace_bytes(n, c, h, w, dt)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_bnact_fwd(hd.ptr, C.byref(dsc), _stream(dev)))
+    return y, stats
+
+
+def bnact_bwd(g, y, x, gamma, stats, *, relu: bool = True, c0: int = 0, res_channels: int = 0,
+              need=(True, True, True, True)):
+    """(dx, dres, dgamma, dbeta) of `tadmm_bnact_bwd` for the gradient `g` of y: float32 or bfloat16 (float16 is
+    refused).  `y` is the output as `bnact_fwd(training=True)` stored it (the ReLU mask is y > 0; None without relu),
+    `stats` what it returned.  dx in the type and shape of x; dres (N, `res_channels`, H, W) contiguous, the masked
+    gradient over the channels [c0, c0 + res_channels) (None when res_channels is 0); dgamma and dbeta float32 (C,).
+    `need` says which of the four are wanted (None for the others).  Two launches (one for dres alone), no atomics,
+    bitwise reproducible; nothing synchronises."""
+    who = "bnact_bwd"
+    dsc, hold, ((n, c, h, w), dev, dt) = _bnact_desc(x, gamma, who)
+    stats = _operand(stats, who, "stats", (torch.float32,), (c, 2), layout="copy")
+    g = _operand(g, who, "g", (dt,), (n, c, h, w), layout="copy")
+    dsc.stats, dsc.g = stats.data_ptr(), g.data_ptr()
+    if relu:
+        y = _operand(y, who, "y", (dt,), (n, c, h, w), layout="copy")
+        dsc.y = y.data_ptr()
+    want_dx, want_dres, want_dg, want_db = (bool(v) for v in need)
+    cr = int(res_channels)
+    dx = torch.empty((n, c, h, w), dtype=dt, device=dev) if want_dx else None
+    dres = torch.empty((n, cr, h, w), dtype=dt, device=dev) if want_dres and cr > 0 else None
+    dgamma = torch.empty(c, dtype=torch.float32, device=dev) if want_dg else None
+    dbeta = torch.empty(c, dtype=torch.float32, device=dev) if want_db else None
+    for name, t in (("dx", dx), ("dres", dres), ("dgamma", dgamma), ("dbeta", dbeta)):
+        setattr(dsc, name, None if t is None else t.data_ptr())
+    dsc.c0, dsc.Cr, dsc.relu, dsc.training = int(c0), cr, int(bool(relu)), 1
+    if want_dx or want_dg or want_db:
+        nbytes = bnact_workspace_bytes(n, c, h, w, dt)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_bnact_bwd(hd.ptr, C.byref(dsc), _stream(dev)))
+    return dx, dres, dgamma, dbeta
+
+
+def bnact_pays(n: int, c: int, hw: int, dtype, grad: bool = False, residual: bool = False) -> bool:
+    """True when `functional.batch_norm_act` sends a call the launch can take to it and not to the composed torch route.
+    A pure function of its arguments.  Measured (scripts/bench_resnet_block.py, two runs) at
+    (n, c, hw) = CIFAR n in {1, 128} x (16, 1024), (32, 256), (64, 64) and ImageNet n in {1, 32} x (64, 3136), (256, 3136),
+    (512, 784), (2048, 49), float32 and bfloat16, without a residual, with a full-width one and (CIFAR, c > 16) with the
+    option-A window, a forward in eval mode under no_grad and a training step, against `batch_norm_act_composed` in the
+    same run.  Most classes are bound by the host: the launch's floor is 0.021 - 0.027 ms for the forward and 0.087 -
+    0.127 ms for the step, the composed route's 0.019 - 0.044 and 0.064 - 0.126.  The launch's slowest window is below
+    the composed route's fastest in both runs for
+      * the forward with a residual in every class measured (1.03x - 2.5x; option A 1.37x - 1.6x: the slice copy and the
+        pad are gone);
+      * the forward without one at n >= 32 from 128 x 64 x 64 values and planes of at least 64 (1.07x - 1.9x), not at
+        n = 1 (0.88x - 1.0x) and not at 32 x 2048 x 49 (0.9x);
+      * the float32 step at 32 x 512 x 784 (1.15x, 1.34x with a residual), 32 x 256 x 3136 (1.38x, 1.44x) and, without a
+        residual, 32 x 64 x 3136 (1.33x; with one a window of one run was behind);
+      * the bfloat16 step at 32 x 256 x 3136 (1.69x, 1.8x; at 32 x 64 x 3136 1.01x - 1.06x, not taken; at 32 x 512 x 784
+        and below the composed route leads, 0.73x - 0.88x).
+    Every other step is behind or level (option A level, 0.99x - 1.09x).  So: a forward with a residual always; without,
+    from n = 32, hw = 64 and 128 * 64 * 64 values; a float32 step from 32 * 512 * 784 values (32 * 64 * 3136 without a
+    residual); a 16-bit step from 32 * 256 * 3136 values.  Not measured: batch sizes between 1 and 32 / 128 and beyond,
+    other planes and widths, float16 (treated as bfloat16), a step in eval mode (the composed route takes it)."""
+    total = int(n) * int(c) * int(hw)
+    if not grad:
+        return bool(residual) or (n >= 32 and hw >= 64 and total >= 128 * 64 * 64)
+    if dtype == torch.float32:
+        return total >= (32 * 512 * 784 if residual else 32 * 64 * 3136)
+    return total >= 32 * 256 * 3136

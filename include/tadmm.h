@@ -845,6 +845,68 @@ int tadmm_prenorm_workspace_bytes(const tadmm_prenorm_desc* d, size_t* bytes);
 int tadmm_prenorm_fwd(tadmm_handle h, const tadmm_prenorm_desc* d, void* stream);
 int tadmm_prenorm_bwd(tadmm_handle h, const tadmm_prenorm_desc* d, void* stream);
 
+/* ---- ResNet block tail: BatchNorm2d, shortcut add and ReLU (csrc/bnact.hip) -------------------------------------------
+ * resnet_cifar_tt.py / resnet_inet_tt.py: relu(bn(conv(x))) and relu(bn(conv(x)) + shortcut(x)).  x: (N, C, H, W) of
+ * `dtype`, NCHW contiguous, any element-aligned base (16-byte accesses when every contiguous base is 16-byte aligned and
+ * H W is a whole number of 16-byte units; element accesses otherwise).  M = N H W values per channel.  gamma, beta,
+ * running_mean, running_var: float32 (C).
+ *   z = gamma_c (x - mean_c) rstd_c + beta_c + [c0 <= c < c0 + Cr] res[n, c - c0, h, w],   y = relu ? max(z, 0) : z
+ * res (nullable) is (N, Cr, H, W) of `dtype` read through the four element strides res_stride (>= 0): a plain tensor, or
+ * the option-A shortcut x_in[:, :, ::2, ::2] at channel offset c0 = planes / 4; channels outside the window get none.
+ * tadmm_bnact_fwd with training != 0, two launches: per-(channel, split) sums of x - K and (x - K)^2 in double to the
+ * workspace (K = x[0, c, 0, 0], so a channel with mean >> std keeps its variance), then every workgroup adds its
+ * channel's partials in a fixed order, mean_c and rstd_c = 1 / sqrt(var_c + eps) (biased variance) stay in double for
+ * y and are rounded once into stats (float32 (C, 2) = (mean, rstd); nullable).  running_mean and running_var (given
+ * together, or both NULL) become (1 - momentum) old + momentum new, the new variance unbiased (M / (M - 1));
+ * num_batches_tracked (int64, nullable) rises by one.  With training == 0, one launch: a_c = gamma_c / sqrt(running_var_c
+ * + eps), b_c = beta_c - running_mean_c a_c, y = act(a x + b + res); stats, the running statistics and the counter are
+ * not written and no workspace is needed.
+ * tadmm_bnact_bwd (training mode; float32 and bfloat16) reads g (the gradient of y, contiguous), y as the forward stored
+ * it (only when relu), x, stats and gamma; gz = g (y > 0), or g without relu; xhat = (x - mean) rstd from stats.  Two
+ * launches: partial sums of gz and gz xhat in double (and dres = gz over the window, contiguous (N, Cr, H, W)), then
+ *   dbeta_c = sum gz,  dgamma_c = sum gz xhat  (float32 (C)),   dx = gamma rstd (gz - dbeta / M - xhat dgamma / M).
+ * Every output is nullable; without dx the second launch only adds the partials; with dres alone there is one launch and
+ * no workspace; with no output nothing is launched.  c0 and Cr are read when dres is given.
+ * No atomics; grids depend on (N, C, H W, dtype) alone: bitwise reproducible; no host synchronisation.  The workspace
+ * (tadmm_bnact_workspace_bytes, reads N, C, H, W, dtype; 16-byte aligned) is sized for C min(trips, 128, ceil(2048 / C))
+ * pairs of doubles, a trip being 256 * 16 / sizeof(element) values (at most 2048); a channel's splits are that many,
+ * evened out so that none is empty.  The size never falls as N, H or W grows.
+ * tadmm_bnact_fits is host only: 1 for N H W <= 2^31 - 4096 (*max_m, nullable, receives the bound), 0 above,
+ * TADMM_ERR_INVALID for a NULL descriptor or N, C, H or W < 1.  The launches return TADMM_ERR_UNSUPPORTED where _fits
+ * returns 0 and TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or descriptor; N, C, H or W < 1; training
+ * (and _bwd) with M < 2; an unknown dtype; TADMM_CHAIN_F16 in _bwd; res (dres in _bwd) with c0 < 0, Cr < 1 or
+ * c0 + Cr > C; a negative stride; eps negative or not finite; momentum outside [0, 1]; x or gamma NULL; a pointer not
+ * aligned to its element; in _fwd beta or y NULL, y == x or y == res, eval mode without running statistics, one running
+ * statistic without the other; in _bwd stats or g NULL, y NULL with relu, dx == dres.  TADMM_ERR_WORKSPACE: the
+ * workspace is needed and NULL, misaligned or short. */
+typedef struct {
+  const void* x; const void* res;             /* res nullable (forward) */
+  int64_t res_stride[4];                      /* elements: n, channel, h, w */
+  const float* gamma; const float* beta;      /* (C) */
+  float* running_mean; float* running_var;    /* (C); training updates them (nullable there), eval reads them */
+  int64_t* num_batches_tracked;               /* training: += 1; nullable */
+  void* y;                                    /* forward writes it, backward reads it when relu */
+  float* stats;                               /* training forward writes it (nullable), backward reads it */
+  const void* g;                              /* backward */
+  void* dx; void* dres;                       /* backward; each nullable */
+  float* dgamma; float* dbeta;                /* backward; each nullable */
+  void* workspace; size_t workspace_bytes;    /* training forward; backward with dx, dgamma or dbeta */
+  double eps;
+  double momentum;                            /* [0, 1] */
+  int32_t N, C, H, W;
+  int32_t c0, Cr;                             /* the residual's channel window */
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (forward only) */
+  int32_t training;                           /* forward: nonzero = batch statistics, 0 = running statistics */
+  int32_t relu;
+  int32_t reserved;
+} tadmm_bnact_desc;
+/* sizeof(tadmm_bnact_desc) as the library was built */
+int tadmm_bnact_desc_bytes(void);
+int tadmm_bnact_fits(const tadmm_bnact_desc* d, int64_t* max_m);
+int tadmm_bnact_workspace_bytes(const tadmm_bnact_desc* d, size_t* bytes);
+int tadmm_bnact_fwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream);
+int tadmm_bnact_bwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream);
+
 /* ---- TinyBERT layer losses: masked attention MSE and hidden-state MSE with gradients (csrc/layermse.hip) -------------
  * xcompression/task_distill.py:810-828 (also task_distill1.py, task_distill2.py, general_distill.py:438-451) for all
  * pairs of a step in two launches.  A call carries npairs <= TADMM_LAYER_MSE_MAX_PAIRS pairs; pair i is s (student)
