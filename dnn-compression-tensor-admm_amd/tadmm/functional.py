@@ -1732,3 +1732,166 @@ def batch_norm_act_module(bn, x, residual=None, res_channel_offset: int = 0, rel
     return batch_norm_act(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, residual,
                           res_channel_offset=res_channel_offset, training=training, momentum=bn.momentum, eps=bn.eps,
                           relu=relu, num_batches_tracked=bn.num_batches_tracked if bn.training else None, route=route)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# MobileNetV2 depthwise stage (csrc/dwbn.hip): relu6(bn(depthwise_conv3x3(x))), the middle of every inverted-residual
+# block of mobilenetv2_cifar_tt.py and mobilenetv2_tt.py.
+# ---------------------------------------------------------------------------------------------------------------
+class _DwBnFn(torch.autograd.Function):
+    """x (N, C, H, W); `buffers` = (running_mean, running_var, num_batches_tracked), updated in place by the launch and
+    handed over as a tuple: they are no inputs of the graph."""
+
+    @staticmethod
+    def forward(ctx, x, conv_weight, weight, bias, buffers, stride, training, momentum, eps):
+        need = any(ctx.needs_input_grad[:4])
+        running_mean, running_var, nbt = buffers
+        y, z, stats = ops.dwbn_fwd(x, conv_weight, weight, bias, running_mean, running_var, stride=stride,
+                                   training=training, momentum=momentum, eps=eps, num_batches_tracked=nbt,
+                                   need_stats=need)
+        if need:
+            ctx.save_for_backward(x, y, z, conv_weight, weight, stats)
+        ctx.stride = stride
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, z, conv_weight, weight, stats = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, dgamma, dbeta = ops.dwbn_bwd(g, y, z, x, conv_weight, weight, stats, stride=ctx.stride,
+                                             need=(need[0], need[1], need[2], need[3]))
+        return (dx, dw, dgamma, dbeta) + (None,) * 5
+
+
+def _depthwise_args(x, conv_weight, running_mean, running_var, weight, bias, momentum, who):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be an (N, C, H, W) tensor")
+    c = x.shape[1]
+    if not isinstance(conv_weight, torch.Tensor) or conv_weight.dim() != 4 or conv_weight.shape[0] != c \
+            or conv_weight.shape[1] != 1:
+        raise ValueError(f"{who}: conv_weight must be a ({c}, 1, kh, kw) tensor (depth multiplier 1)")
+    for n, t in (("running_mean", running_mean), ("running_var", running_var), ("weight", weight), ("bias", bias)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (c,)):
+            raise ValueError(f"{who}: {n} must be a ({c},) tensor or None")
+    if momentum is not None and not 0.0 <= float(momentum) <= 1.0:
+        raise ValueError(f"{who}: momentum must be in [0, 1] or None (got {momentum})")
+
+
+def depthwise_bn_relu6_composed(x, conv_weight, running_mean, running_var, weight, bias, *, stride=1, padding=1,
+                                dilation=1, training: bool, momentum=0.1, eps: float = 1e-5, num_batches_tracked=None):
+    """`depthwise_bn_relu6` from torch operations, under autograd, on any device and in float64: `F.conv2d` with
+    `groups = C` (the weight cast to the type of x), `F.batch_norm`, `F.relu6`.  As nn.BatchNorm2d does, a training
+    call first adds one to `num_batches_tracked` (where given and the running statistics are tracked) and
+    `momentum=None` is the cumulative average 1 / num_batches_tracked.  The route for what the launch refuses and the
+    yardstick of tests/test_gpu_dwbn.py and scripts/bench_mobilenet_block.py."""
+    _depthwise_args(x, conv_weight, running_mean, running_var, weight, bias, momentum, "depthwise_bn_relu6_composed")
+    factor = 0.0 if momentum is None else float(momentum)
+    if training and running_mean is not None and num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+        if momentum is None:
+            factor = 1.0 / float(num_batches_tracked)
+    z = F.conv2d(x, conv_weight.to(x.dtype), None, stride, padding, dilation, x.shape[1])
+    return F.relu6(F.batch_norm(z, running_mean, running_var, weight, bias, training, factor, eps))
+
+
+def depthwise_bn_relu6_launch_refusal(is_cuda: bool, dtype, shape, stride, grad: bool, training: bool,
+                                      contiguous: bool = True, kernel=(3, 3), padding=(1, 1), dilation=(1, 1),
+                                      param_dtypes=(torch.float32,), affine: bool = True, tracked: bool = True,
+                                      momentum_given: bool = True, foreign: bool = False):
+    """None when csrc/dwbn.hip takes a call with these properties, else the reason it does not (a string): CPU tensors,
+    a type other than float32 / bfloat16 / float16, float16 with gradients, eval mode with gradients, an x that is not
+    NCHW contiguous, a kernel other than 3x3 with padding 1 and dilation 1, a stride other than 1 and 2 (or two
+    different ones), a plane wider than the launch takes, fewer than two output values per channel in training,
+    parameters or running statistics that are missing (`affine=False`, `track_running_stats=False`) or not float32,
+    `momentum=None`, or an operand on another device (`foreign`).  A pure function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    if dtype not in ops.DWBN_DTYPES:
+        return f"{dtype} operands"
+    if dtype == torch.float16 and grad:
+        return "float16 with gradients"
+    if grad and not training:
+        return "eval mode with gradients"
+    if not contiguous:
+        return "an x that is not NCHW contiguous"
+    if ops._pair(kernel) != (3, 3) or ops._pair(padding) != (1, 1) or ops._pair(dilation) != (1, 1):
+        return f"kernel {ops._pair(kernel)}, padding {ops._pair(padding)}, dilation {ops._pair(dilation)}"
+    st = ops._pair(stride)
+    if st not in ((1, 1), (2, 2)):
+        return f"stride {st}"
+    if min(shape) < 1 or not ops.dwbn_fits(*shape, st[0], dtype):
+        return f"shape = {tuple(shape)}"
+    ho, wo = ops.dwbn_out_hw(shape[2], shape[3], st[0])
+    if training and shape[0] * ho * wo < 2:
+        return "one output value per channel in training"
+    if not affine:
+        return "affine=False"
+    if not tracked:
+        return "track_running_stats=False"
+    if any(d != torch.float32 for d in param_dtypes):
+        return "parameters or running statistics that are not float32"
+    if not momentum_given:
+        return "momentum=None"
+    if foreign:
+        return "a parameter or buffer of another type or on another device"
+    return None
+
+
+def depthwise_bn_relu6(x, conv_weight, running_mean, running_var, weight, bias, *, stride, padding=1, dilation=1,
+                       training: bool, momentum=0.1, eps: float = 1e-5, num_batches_tracked=None, route: str = None):
+    """The middle of a MobileNetV2 inverted-residual block,
+
+        y = relu6(weight (z - mean) / sqrt(var + eps) + bias),    z = depthwise_conv3x3(x; conv_weight, stride, padding 1),
+
+    over x (N, C, H, W) and `conv_weight` (C, 1, 3, 3) with the batch-norm arguments of `F.batch_norm`: batch statistics
+    (biased variance) when `training`, which also updates `running_mean` / `running_var` in place (momentum, unbiased
+    variance) and adds one to `num_batches_tracked`; the running statistics otherwise.  Differentiable in x,
+    conv_weight, weight and bias.  `route`: None (the launch where it takes the call and the measured rule
+    `ops.dwbn_pays` says it is ahead), "launch" (csrc/dwbn.hip: two launches in training, one in eval, three backward)
+    or "composed" (`F.conv2d(groups=C)`, `F.batch_norm`, `F.relu6`).  The launch takes NCHW-contiguous HIP tensors of
+    float32 or bfloat16 (float16 without gradients), a 3x3 kernel with padding 1, dilation 1 and stride 1 or 2, float32
+    parameters and running statistics, a momentum, and gradients only in training mode.  Everything else goes to the
+    composed route under `route=None` and raises under `route="launch"`."""
+    who = "depthwise_bn_relu6"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    _depthwise_args(x, conv_weight, running_mean, running_var, weight, bias, momentum, who)
+    training = bool(training)
+    grad = _needs_grad(x, conv_weight, weight, bias)
+    params = [t for t in (conv_weight, weight, bias, running_mean, running_var) if t is not None]
+    foreign = any(t.device != x.device for t in params) \
+        or (num_batches_tracked is not None and (num_batches_tracked.device != x.device
+                                                 or num_batches_tracked.dtype != torch.int64))
+    why = None
+    if route != "composed":
+        why = depthwise_bn_relu6_launch_refusal(
+            x.is_cuda, x.dtype, tuple(x.shape), stride, grad, training, x.is_contiguous(), tuple(conv_weight.shape[2:]),
+            padding, dilation, tuple(t.dtype for t in params), weight is not None and bias is not None,
+            running_mean is not None and running_var is not None, momentum is not None, foreign)
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    n, c, h, w = x.shape
+    launch = route != "composed" and why is None and (
+        route == "launch" or ops.dwbn_pays(n, c, h, w, ops._pair(stride)[0], x.dtype, grad))
+    if not launch:
+        return depthwise_bn_relu6_composed(x, conv_weight, running_mean, running_var, weight, bias, stride=stride,
+                                           padding=padding, dilation=dilation, training=training, momentum=momentum,
+                                           eps=eps, num_batches_tracked=num_batches_tracked)
+    return _DwBnFn.apply(x, conv_weight, weight, bias, (running_mean, running_var, num_batches_tracked),
+                         ops._pair(stride)[0], training, float(momentum), float(eps))
+
+
+def depthwise_bn_relu6_module(conv, bn, x, route: str = None):
+    """`depthwise_bn_relu6` with the parameters, buffers and mode of the modules `conv` (an nn.Conv2d with groups equal
+    to its channels) and `bn`.  An nn.BatchNorm2d keeps its state-dict keys and semantics; a convolution with a bias or a
+    depth multiplier, or any other norm layer, is called as it is with `F.relu6` behind it."""
+    ok = isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.BatchNorm2d) and conv.bias is None \
+        and conv.groups == conv.in_channels == conv.out_channels and conv.padding_mode == "zeros" \
+        and not isinstance(conv.padding, str)
+    if not ok:
+        return F.relu6(bn(conv(x)))
+    training = bn.training or (bn.running_mean is None and bn.running_var is None)
+    return depthwise_bn_relu6(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, stride=conv.stride,
+                              padding=conv.padding, dilation=conv.dilation, training=training, momentum=bn.momentum,
+                              eps=bn.eps, num_batches_tracked=bn.num_batches_tracked if bn.training else None,
+                              route=route)

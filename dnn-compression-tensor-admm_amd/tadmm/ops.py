@@ -2710,3 +2710,175 @@ def bnact_pays(n: int, c: int, hw: int, dtype, grad: bool = False, residual: boo
     if dtype == torch.float32:
         return total >= (32 * 512 * 784 if residual else 32 * 64 * 3136)
     return total >= 32 * 256 * 3136
+
+
+# ------------------------------------------------------------------ MobileNetV2 depthwise stage (csrc/dwbn.hip)
+DWBN_DTYPES = BERTNORM_DTYPES
+
+
+def _dwbn_shape_desc(n, c, h, w, stride, dtype):
+    dsc = _cabi.DwBnDesc()
+    dsc.N, dsc.C, dsc.H, dsc.W, dsc.stride, dsc.dtype = int(n), int(c), int(h), int(w), int(stride), DWBN_DTYPES[dtype]
+    return dsc
+
+
+def dwbn_out_hw(h: int, w: int, stride: int):
+    """(Ho, Wo) of a 3x3 convolution with padding 1: (h - 1) // stride + 1 and (w - 1) // stride + 1."""
+    return (int(h) - 1) // int(stride) + 1, (int(w) - 1) // int(stride) + 1
+
+
+def dwbn_max_w() -> int:
+    """The widest plane `tadmm_dwbn_fwd` / `_bwd` take (three haloed rows fit the staged tile).  Host only."""
+    m = C.c_int32()
+    _cabi.load().tadmm_dwbn_fits(None, C.byref(m))
+    return int(m.value)
+
+
+def dwbn_fits(n: int, c: int, h: int, w: int, stride: int = 1, dtype=torch.float32) -> bool:
+    """True when the launches take an (n, c, h, w) tensor (`tadmm_dwbn_fits`: w <= `dwbn_max_w()` and n h w <= 2^31 -
+    4096).  Raises TadmmError for a dimension < 1 or a stride other than 1 and 2.  Host only."""
+    rc = _cabi.load().tadmm_dwbn_fits(C.byref(_dwbn_shape_desc(n, c, h, w, stride, dtype)), None)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_dwbn_fits: shape = {(n, c, h, w)}, stride = {stride}")
+    return rc == 1
+
+
+def dwbn_plan(n: int, c: int, h: int, w: int, stride: int = 1, dtype=torch.float32) -> dict:
+    """The ownership `tadmm_dwbn_plan` derives from the shape alone, as a dict: `G` images share a staged tile (whole
+    planes), or the plane is cut into `NB` bands of `RB` output rows (G = 1); a channel's `U` = ceil(n / G) NB units go
+    to `S` workgroups of `per` consecutive units each.  The element type does not enter.  Host only."""
+    out = (C.c_int32 * 6)()
+    rc = _cabi.load().tadmm_dwbn_plan(C.byref(_dwbn_shape_desc(n, c, h, w, stride, dtype)), out)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_dwbn_plan: shape = {(n, c, h, w)}, stride = {stride}")
+    return dict(zip(("G", "RB", "NB", "U", "S", "per"), (int(v) for v in out)))
+
+
+def dwbn_workspace_bytes(n: int, c: int, h: int, w: int, stride: int = 1, dtype=torch.float32) -> int:
+    """Bytes of the workspace of the training forward and of the backward (`tadmm_dwbn_workspace_bytes`: eleven doubles
+    per channel and split for min(128, ceil(1024 / c)) splits, rounded up to 256 bytes; a function of c alone, so never
+    smaller for a larger n, h or w).  Host only."""
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_dwbn_workspace_bytes(C.byref(_dwbn_shape_desc(n, c, h, w, stride, dtype)), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_dwbn_workspace_bytes: shape = {(n, c, h, w)}, stride = {stride}")
+    return int(size.value)
+
+
+def _dwbn_desc(x, conv_weight, gamma, stride, who):
+    """The descriptor fields forward and backward share.  Returns (descriptor, tensors to keep alive, (shape, device,
+    dtype))."""
+    x = _operand(x, who, "x", tuple(DWBN_DTYPES), layout="copy")
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise TadmmError(-1, f"{who}: x must be (N, C, H, W) with every dimension >= 1 (got {tuple(x.shape)})")
+    if int(stride) not in (1, 2):
+        raise TadmmError(-1, f"{who}: stride is 1 or 2 (got {stride})")
+    n, c, h, w = x.shape
+    dsc = _dwbn_shape_desc(n, c, h, w, stride, x.dtype)
+    conv_weight = _operand(conv_weight, who, "conv_weight", (torch.float32,), (c, 1, 3, 3), layout="copy")
+    gamma = _operand(gamma, who, "gamma", (torch.float32,), (c,), layout="copy")
+    for t in (conv_weight, gamma):
+        if t.device != x.device:
+            raise TadmmError(-1, f"{who}: a parameter on {t.device}, x on {x.device}")
+    dsc.x, dsc.w, dsc.gamma = x.data_ptr(), conv_weight.data_ptr(), gamma.data_ptr()
+    return dsc, [x, conv_weight, gamma], ((n, c, h, w), x.device, x.dtype)
+
+
+def dwbn_fwd(x, conv_weight, gamma, beta, running_mean, running_var, *, stride: int, training: bool,
+             momentum: float = 0.1, eps: float = 1e-5, num_batches_tracked=None, need_stats: bool = False):
+    """(y, z, stats) of `tadmm_dwbn_fwd`: y = relu6(BatchNorm2d(depthwise_conv3x3(x))) for x (N, C, H, W) float32,
+    bfloat16 or float16 (a non-contiguous x is copied), `conv_weight` float32 (C, 1, 3, 3), padding 1, `stride` 1 or 2.
+    `gamma`, `beta`, `running_mean`, `running_var`: float32 (C,).  With `training` the batch statistics of the
+    convolution's output z as stored are used, the running statistics (both or neither) are updated in place with
+    `momentum` and the unbiased variance, `num_batches_tracked` (int64 scalar tensor, optional) rises by one, z is
+    returned (the backward reads it) and stats is float32 (C, 2) = (mean, 1 / sqrt(var + eps)) when `need_stats`; two
+    launches.  Without, the running statistics are read, nothing but y is written and z and stats are None; one launch.
+    Nothing synchronises."""
+    who = "dwbn_fwd"
+    dsc, hold, ((n, c, h, w), dev, dt) = _dwbn_desc(x, conv_weight, gamma, stride, who)
+    for name, t in (("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is None and name != "beta" and training:
+            continue
+        # updated in place: a copy would take the update with it
+        t = _operand(t, who, name, (torch.float32,), (c,), layout="copy" if name == "beta" else "raise")
+        hold.append(t)
+        setattr(dsc, name, t.data_ptr())
+    if num_batches_tracked is not None and training:
+        nbt = _operand(num_batches_tracked, who, "num_batches_tracked", (torch.int64,), (), layout="raise")
+        hold.append(nbt)
+        dsc.num_batches_tracked = nbt.data_ptr()
+    for t in hold:
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: an operand on {t.device}, x on {dev}")
+    dsc.eps, dsc.momentum, dsc.training = float(eps), float(momentum), int(bool(training))
+    ho, wo = dwbn_out_hw(h, w, stride)
+    y = torch.empty((n, c, ho, wo), dtype=dt, device=dev)
+    z = torch.empty((n, c, ho, wo), dtype=dt, device=dev) if training else None
+    stats = torch.empty((c, 2), dtype=torch.float32, device=dev) if need_stats and training else None
+    dsc.y = y.data_ptr()
+    dsc.z = None if z is None else z.data_ptr()
+    dsc.stats = None if stats is None else stats.data_ptr()
+    if training:
+        nbytes = dwbn_workspace_bytes(n, c, h, w, stride, dt)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_dwbn_fwd(hd.ptr, C.byref(dsc), _stream(dev)))
+    return y, z, stats
+
+
+def dwbn_bwd(g, y, z, x, conv_weight, gamma, stats, *, stride: int, need=(True, True, True, True)):
+    """(dx, dw, dgamma, dbeta) of `tadmm_dwbn_bwd` for the gradient `g` of y: float32 or bfloat16 (float16 is refused).
+    `y`, `z` and `stats` are what `dwbn_fwd(training=True, need_stats=True)` returned (the mask is 0 < y < 6).  dx in the
+    type and shape of x; dw float32 (C, 1, 3, 3); dgamma and dbeta float32 (C,).  `need` says which of the four are
+    wanted (None for the others).  Three launches (two without dw), no atomics, bitwise reproducible; nothing
+    synchronises."""
+    who = "dwbn_bwd"
+    dsc, hold, ((n, c, h, w), dev, dt) = _dwbn_desc(x, conv_weight, gamma, stride, who)
+    ho, wo = dwbn_out_hw(h, w, stride)
+    stats = _operand(stats, who, "stats", (torch.float32,), (c, 2), layout="copy")
+    g = _operand(g, who, "g", (dt,), (n, c, ho, wo), layout="copy")
+    y = _operand(y, who, "y", (dt,), (n, c, ho, wo), layout="copy")
+    z = _operand(z, who, "z", (dt,), (n, c, ho, wo), layout="copy")
+    dsc.stats, dsc.g, dsc.y, dsc.z = stats.data_ptr(), g.data_ptr(), y.data_ptr(), z.data_ptr()
+    want_dx, want_dw, want_dg, want_db = (bool(v) for v in need)
+    dx = torch.empty((n, c, h, w), dtype=dt, device=dev) if want_dx else None
+    dw = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=dev) if want_dw else None
+    dgamma = torch.empty(c, dtype=torch.float32, device=dev) if want_dg else None
+    dbeta = torch.empty(c, dtype=torch.float32, device=dev) if want_db else None
+    for name, t in (("dx", dx), ("dw", dw), ("dgamma", dgamma), ("dbeta", dbeta)):
+        setattr(dsc, name, None if t is None else t.data_ptr())
+    dsc.training = 1
+    if want_dx or want_dw or want_dg or want_db:
+        nbytes = dwbn_workspace_bytes(n, c, h, w, stride, dt)
+        ws = _scratch(nbytes, dev)
+        dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), nbytes
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_dwbn_bwd(hd.ptr, C.byref(dsc), _stream(dev)))
+    return dx, dw, dgamma, dbeta
+
+
+def dwbn_pays(n: int, c: int, h: int, w: int, stride: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.depthwise_bn_relu6` sends a call the launch can take to it and not to the composed torch
+    route.  A pure function of its arguments.  Measured (scripts/bench_mobilenet_block.py, two runs, DESIGN.md section
+    25) at (c, h = w, stride) = CIFAR n in {1, 128} x (32, 32, 1), (96, 32, 1), (144, 32, 1), (192, 32, 2), (384, 16, 1),
+    (576, 16, 2), (960, 8, 1) and ImageNet n in {1, 32} x (32, 112, 1), (96, 112, 2), (144, 56, 2), (192, 28, 1),
+    (384, 14, 1), (576, 14, 2), (960, 7, 1), float32 and bfloat16, a forward in eval mode under no_grad and a training
+    step, against `depthwise_bn_relu6_composed` in the same run.  The launch's floor is 0.023 - 0.026 ms for the forward
+    and 0.102 - 0.112 ms for the step, the composed route's 0.043 - 0.047 and 0.137 - 0.146 ms: torch's grouped
+    convolution, batch norm and hardtanh are three to four launches forward and more backward.  The launch's slowest
+    window is below the composed route's fastest in both runs for
+      * the forward in all 56 classes (n = 1: 1.5x - 2.8x; n = 128 / 32: 1.2x - 7.0x, 5x - 7x for the CIFAR classes from
+        96 channels);
+      * the bfloat16 step in all 28 classes (n = 1: 1.1x - 2.6x; n = 128 / 32: 3.1x - 30x: torch's bfloat16 depthwise
+        weight gradient is slow);
+      * the float32 step in 26 of 28 classes (n = 1: 1.3x - 1.9x; n = 128 / 32: 2.8x - 14x).  At 1 x 32 x 32 x 32 and
+        1 x 192 x 32 x 32 (stride 2) one run had a launch window inside the composed route's spread (0.69x - 2.1x), so
+        those two are not taken.
+    So: every forward; every 16-bit step; a float32 step unless n == 1 with fewer than 2^18 input values per image, which
+    keeps the two classes that were not ahead in both runs, and the six batch-1 classes below that size that were, with
+    the composed route.  Not measured: batch sizes between 1 and 32 / 128 and beyond, planes that are not square, other
+    widths, float16 (treated as bfloat16), a step in eval mode (the composed route takes it)."""
+    if not grad or dtype != torch.float32:
+        return True
+    return not (int(n) == 1 and int(c) * int(h) * int(w) < 2 ** 18)

@@ -907,6 +907,75 @@ int tadmm_bnact_workspace_bytes(const tadmm_bnact_desc* d, size_t* bytes);
 int tadmm_bnact_fwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream);
 int tadmm_bnact_bwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream);
 
+/* ---- MobileNetV2 depthwise stage: depthwise 3x3 convolution, BatchNorm2d and ReLU6 (csrc/dwbn.hip) -------------------
+ * mobilenetv2_cifar_tt.py / mobilenetv2_tt.py: relu6(bn(depthwise_conv3x3(x))).  x: (N, C, H, W) of `dtype`, NCHW
+ * contiguous; w: float32 (C, 1, 3, 3); kernel 3, padding 1, dilation 1, depth multiplier 1, no bias, stride s = 1 or 2.
+ * The output plane is Ho = (H - 1) / s + 1 by Wo = (W - 1) / s + 1; M = N Ho Wo output values per channel.  gamma, beta,
+ * running_mean, running_var: float32 (C).
+ *   z[n,c,i,j] = sum_{a,b} w[c,a,b] x[n,c, i s + a - 1, j s + b - 1]   (zero outside the plane; float32, taps in the order
+ *                                                                       a, b ascending)
+ *   y = min(max(gamma_c (z - mean_c) rstd_c + beta_c, 0), 6)
+ * Accesses are 16 bytes wide when x, y (z, g, dx) are 16-byte aligned and W and Wo are whole numbers of 16-byte units, one
+ * element otherwise; any element-aligned base is taken.
+ * tadmm_dwbn_fwd with training != 0, two launches: z, stored in `dtype` (N, C, Ho, Wo), with per-(channel, split) sums
+ * of z - K and (z - K)^2 of z as stored, in double, K = z[0, c, 0, 0]; then every workgroup adds its channel's partials in
+ * a fixed order, mean_c and rstd_c = 1 / sqrt(var_c + eps) (biased variance) stay in double for y and are rounded once
+ * into stats (float32 (C, 2) = (mean, rstd); nullable).  running_mean and running_var (given together, or both NULL)
+ * become (1 - momentum) old + momentum new, the new variance unbiased (M / (M - 1)); num_batches_tracked (int64,
+ * nullable) rises by one.  With training == 0, one launch: a_c = gamma_c / sqrt(running_var_c + eps), b_c = beta_c -
+ * running_mean_c a_c (folded in double), y = clamp(a conv(x) + b); z, stats, the running statistics and the counter are
+ * not written and no workspace is needed.
+ * tadmm_dwbn_bwd (training mode; float32 and bfloat16) reads g (the gradient of y, contiguous), y and z as the forward
+ * stored them, x, w, stats and gamma; gz = g (0 < y < 6); xhat = (z - mean) rstd from stats.  Three launches: partial
+ * sums of gz and gz xhat in double; then dbeta_c = sum gz, dgamma_c = sum gz xhat (float32 (C)),
+ *   dz = gamma rstd (gz - dbeta / M - xhat dgamma / M)   (formed on a haloed tile on chip, never stored),
+ *   dx[n,c,h,w] = sum_{a,b} w[c,a,b] dz[n,c,(h + 1 - a) / s,(w + 1 - b) / s]   (terms with whole quotients inside the plane)
+ * and per-workgroup partials of dw[c,a,b] = sum_{n,i,j} dz[n,c,i,j] x[n,c, i s + a - 1, j s + b - 1] in double; then dw
+ * (float32 (C, 1, 3, 3)) from the partials in a fixed order, in double.  dx, dw, dgamma and dbeta are each nullable;
+ * without dw there are two launches; with no output nothing is launched.
+ * No atomics; grids depend on (N, C, H, W, stride) alone: bitwise reproducible; no host synchronisation.  Ownership
+ * (tadmm_dwbn_plan, host only, plan6 = G, RB, NB, U, S, per): a plane whose haloed input and haloed dz each fit 4096
+ * floats is taken whole, G images to a tile (at most 2048 outputs); a larger one is cut into NB bands of RB output rows;
+ * the U = ceil(N / G) NB units of a channel go to S workgroups of `per` consecutive units.  The workspace
+ * (tadmm_dwbn_workspace_bytes; 16-byte aligned) holds 11 doubles for each of C min(128, ceil(1024 / C)) splits; it
+ * depends on C alone, so it never falls as N, H or W grows.
+ * tadmm_dwbn_fits is host only: 1 for W <= 1363 (*max_w, nullable, receives the bound) and N H W <= 2^31 - 4096, 0
+ * above, TADMM_ERR_INVALID for a NULL descriptor, N, C, H or W < 1 or a stride other than 1 and 2.  The launches return
+ * TADMM_ERR_UNSUPPORTED where _fits returns 0 and TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or
+ * descriptor; N, C, H or W < 1; a stride other than 1 and 2; training (and _bwd) with M < 2; an unknown dtype;
+ * TADMM_CHAIN_F16 in _bwd; eps negative or not finite; momentum outside [0, 1]; x, w, gamma or y NULL; z NULL in
+ * training mode and _bwd; a pointer not aligned to its element; in _fwd beta NULL, y == x, z == x or z == y, eval mode
+ * without running statistics, one running statistic without the other; in _bwd stats or g NULL, dx equal to x, g, y or
+ * z.  TADMM_ERR_WORKSPACE: the workspace is needed and NULL, misaligned or short. */
+typedef struct {
+  const void* x;                              /* (N, C, H, W) */
+  const float* w;                             /* (C, 1, 3, 3) */
+  const float* gamma; const float* beta;      /* (C) */
+  float* running_mean; float* running_var;    /* (C); training updates them (nullable there), eval reads them */
+  int64_t* num_batches_tracked;               /* training: += 1; nullable */
+  void* z;                                    /* (N, C, Ho, Wo); training forward writes it, backward reads it */
+  void* y;                                    /* (N, C, Ho, Wo); forward writes it, backward reads it */
+  float* stats;                               /* training forward writes it (nullable), backward reads it */
+  const void* g;                              /* backward */
+  void* dx;                                   /* backward; nullable */
+  float* dw; float* dgamma; float* dbeta;     /* backward; each nullable */
+  void* workspace; size_t workspace_bytes;    /* training forward; backward with any output */
+  double eps;
+  double momentum;                            /* [0, 1] */
+  int32_t N, C, H, W;
+  int32_t stride;                             /* 1 or 2 */
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (forward only) */
+  int32_t training;                           /* forward: nonzero = batch statistics, 0 = running statistics */
+  int32_t reserved;
+} tadmm_dwbn_desc;
+/* sizeof(tadmm_dwbn_desc) as the library was built */
+int tadmm_dwbn_desc_bytes(void);
+int tadmm_dwbn_fits(const tadmm_dwbn_desc* d, int32_t* max_w);
+int tadmm_dwbn_plan(const tadmm_dwbn_desc* d, int32_t* plan6);
+int tadmm_dwbn_workspace_bytes(const tadmm_dwbn_desc* d, size_t* bytes);
+int tadmm_dwbn_fwd(tadmm_handle h, const tadmm_dwbn_desc* d, void* stream);
+int tadmm_dwbn_bwd(tadmm_handle h, const tadmm_dwbn_desc* d, void* stream);
+
 /* ---- TinyBERT layer losses: masked attention MSE and hidden-state MSE with gradients (csrc/layermse.hip) -------------
  * xcompression/task_distill.py:810-828 (also task_distill1.py, task_distill2.py, general_distill.py:438-451) for all
  * pairs of a step in two launches.  A call carries npairs <= TADMM_LAYER_MSE_MAX_PAIRS pairs; pair i is s (student)
