@@ -238,6 +238,26 @@ __device__ __forceinline__ void mma_tile(const bf16x8_t (&a)[P], const bf16x8_t 
   }
 }
 
+// mma_tile for the long reductions (taps * rank / 32 k-steps of the k x k core): float32's leading pair x1 y1 goes to `acc`,
+// its five low-order pairs (2^-8 of a product and less) to `lo`, so that `acc` is rounded once per k-step instead of
+// six times -- with one accumulator the rms error of a 3 x 3 core at rank 150 was 2.2 times a float32 GEMM's.  The
+// caller adds `lo` to `acc` once, after the last step.  One plane: `lo` is never touched.
+template <int P, int NB, bool F16 = false>
+__device__ __forceinline__ void mma_tile_split(const bf16x8_t (&a)[P], const bf16x8_t (&b)[P][NB], float4v_t (&acc)[NB],
+                                               float4v_t (&lo)[NB]) {
+  if constexpr (P == 1) {
+    mma_tile<P, NB, F16>(a, b, acc);
+  } else {
+    constexpr int pa[5] = {2, 0, 1, 1, 0}, pb[5] = {0, 2, 1, 0, 1};
+#pragma unroll
+    for (int pr = 0; pr < 5; ++pr)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[pb[pr]][j], a[pa[pr]], lo[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0][j], a[0], acc[j], 0, 0, 0);
+  }
+}
+
 // ---- tap <-> pixel maps of a convolution axis (coreconv.hip, convchain.hip).  transposed 0: destination = output
 // coordinate, source = input coordinate; 1: the data gradient's map (destination = input, source = output)
 // first and last source coordinate that destination coordinates [t0, t0 + n) reach over all taps of one axis

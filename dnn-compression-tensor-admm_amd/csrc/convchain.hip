@@ -258,11 +258,11 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
 
   // ---------------- product 2: the k x k core convolution as taps * R1/32 k-steps with gathered token rows
   {
-    float4v_t acc[MT][NBW];
+    float4v_t acc[MT][NBW], lo[MT][NBW];                      // lo: float32's low-order pairs (mma_tile_split)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int j = 0; j < NBW; ++j) acc[mt][j] = float4v_t{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < NBW; ++j) acc[mt][j] = lo[mt][j] = float4v_t{0.f, 0.f, 0.f, 0.f};
     const int KSR = d.R1 / 32, taps = d.kh * d.kw, S = taps * KSR, nt2 = d.R2 / 16;
     gw_t w2[NBW];
 #pragma unroll
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
             const int row = live ? (int)tab[tap * TM + 16 * mt + r] : -1;
             bf16x8_t a[P];
             gather_x<P>(a, H1s, prow1, ld1, row, ks, q);
-            mma_tile<P, NBW, F16>(a, b[u], acc[mt]);
+            mma_tile_split<P, NBW, F16>(a, b[u], acc[mt], lo[mt]);
           }
         } else {
           const int dy = tap / d.kw, dx = tap - dy * d.kw;
@@ -309,13 +309,19 @@ __global__ __launch_bounds__(256) void tt_conv_kernel(const ConvChainDesc d) {
             const bool in = live && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
             bf16x8_t a[P];
             gather_x<P>(a, H1s, prow1, ld1, in ? (iy - iy_lo) * d.W + ix : -1, ks, q);
-            mma_tile<P, NBW, F16>(a, b[u], acc[mt]);
+            mma_tile_split<P, NBW, F16>(a, b[u], acc[mt], lo[mt]);
           }
         }
         ks += 1;
         if (ks == KSR) { ks = 0; tap += 1; }
         if (tap >= taps) { tap = taps - 1; }                  // keeps the surplus steps' addresses valid
       }
+    }
+    if constexpr (P > 1) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) acc[mt][j] += lo[mt][j];
     }
     acc_to_lds<P, TM, NBW, F16>(acc, H2s, TM, 0, ld2, wave * NBW * 16, d.R2, r, q);
   }

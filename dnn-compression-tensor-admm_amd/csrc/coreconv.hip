@@ -154,11 +154,11 @@ __global__ __launch_bounds__(256) void core_conv_kernel(const CoreConvArgs d) {
     ft = ft < d.nt ? ft : d.nt - 1;
     w[j] = (gw_t)d.Wp + ((int64_t)ft * S_all * 64 + lane) * 8;
   }
-  float4v_t acc[MT][NBW];
+  float4v_t acc[MT][NBW], lo[MT][NBW];                         // lo: float32's low-order pairs (mma_tile_split)
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-    for (int j = 0; j < NBW; ++j) acc[mt][j] = float4v_t{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NBW; ++j) acc[mt][j] = lo[mt][j] = float4v_t{0.f, 0.f, 0.f, 0.f};
 
   const int nchunks = empty ? 0 : (d.K + KC - 1) / KC;
   if (nchunks > 0) halo_load<P, KC, T>(Xs, S, chan0, d.K, splane, 0, d.HP, p0, nrun, runlen, d.Ws, svec, tid);
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void core_conv_kernel(const CoreConvArgs d) {
             const int row = live ? (int)tab[tap * kCcTok + 16 * mt + r] : -1;
             bf16x8_t a[P];
             gather_x<P>(a, Xc, d.HP, LDK, row, ks, q);
-            mma_tile<P, NBW>(a, b[u], acc[mt]);
+            mma_tile_split<P, NBW>(a, b[u], acc[mt], lo[mt]);
           }
           tap = ntap; ks = nk;
         }
@@ -195,6 +195,12 @@ __global__ __launch_bounds__(256) void core_conv_kernel(const CoreConvArgs d) {
     __syncthreads();
   }
   if (!active) return;
+  if constexpr (P > 1) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int j = 0; j < NBW; ++j) acc[mt][j] += lo[mt][j];
+  }
 
   // ---- stores: features f_base .. f_base + nf of the tile's pixels; destination rows are runs of tcols pixels (one run
   // of ntok pixels per feature when the tile spans the plane's width)

@@ -201,13 +201,19 @@ def test_no_operand_copies():
     ops.wgrad(gr[:1], x[:1])                                # handle, library and kernel images are loaded
     nbytes, _ = ops.wgrad_plan(gr, x)
     torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    c = ops.wgrad(gr, x)
-    torch.cuda.synchronize()
-    rise = torch.cuda.max_memory_allocated() - base
+    # The launch allocates from an empty pool of its own.  torch's caching allocator hands out a cached block whole when
+    # what a split would leave is 1 MiB or less, and counts the whole block as allocated: a 4.7 or 5 MiB block left by
+    # some earlier test, served for the 4 MiB workspace, would be measured here as if `wgrad` had asked for it.
+    pool = torch.cuda.MemPool()
+    with torch.cuda.use_mem_pool(pool):
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        c = ops.wgrad(gr, x)
+        torch.cuda.synchronize()
+        rise = torch.cuda.max_memory_allocated() - base
     assert rise <= 4 * R * Cin + nbytes + 2 * 512, (rise, nbytes)
-    del c, gr
+    assert rise >= 4 * R * Cin + nbytes, (rise, nbytes)        # the pool's allocations are in the device-wide figures
+    del c, gr, pool
     # one backward of conv1x1_chain: neither of the two channel-major copies (4 * C * B*H*W bytes each) appears
     wi = (torch.randn(R, Cin, device=DEV) / Cin ** 0.5).requires_grad_()
     wo = (torch.randn(N, R, device=DEV) / R ** 0.5).requires_grad_()
