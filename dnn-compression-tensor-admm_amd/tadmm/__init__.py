@@ -1,7 +1,7 @@
 """tadmm -- MI355X-native ADMM low-rank projection path (host-side mirror of the reference API).
 
 Public surface mirrors the reference modules (admm.py, ttd.py, TTConv.py, TTLinear.py, TKConv.py,
-TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, vit_tt.py, resnet_cifar_tt.py, resnet_inet_tt.py, mobilenetv2_cifar_tt.py, mobilenetv2_tt.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
+TKLinear.py, SVDConv.py, StfTKConv.py, the three *Embedding.py, ablation/tt_lstm_inference.py, losses.py, the layer losses of xcompression/task_distill.py, xcompression/transformer/optimization.py, the self-attention of xcompression/transformer/compressed_modeling*.py, vit_tt.py, resnet_cifar_tt.py, resnet_inet_tt.py, mobilenetv2_cifar_tt.py, mobilenetv2_tt.py, densenet_cifar_tt.py, densenet_inet_tt.py, utils.get_hp_dict); arithmetic runs in libtadmm_hip.so (csrc/) through the C ABI of
 include/tadmm.h.  Importing the package does not need a GPU; computing does, and there is no CPU
 fallback: a missing library or device raises.
 """
@@ -58,8 +58,14 @@ def __getattr__(name):
         table[f"{kind}_mobilenetv2_cifar"] = ("mobilenet_cifar_layers", f"{kind}_mobilenetv2_cifar")
     for kind in ("ttr", "tkc", "svdc", "svdm"):
         table[f"{kind}_mobilenetv2"] = ("mobilenet_inet_layers", f"{kind}_mobilenetv2")
+    # densenet_cifar_tt.py and densenet_inet_tt.py: the factories; both files define TenDenseBlock and TenDenseNet, so the
+    # classes are reached through the modules tadmm.densenet_cifar_layers / tadmm.densenet_inet_layers
+    table["tkr_densenet40"] = ("densenet_cifar_layers", "tkr_densenet40")
+    for fn in ("tkc_densenet121", "tkc_densenet201", "tkc_densenet264"):
+        table[fn] = ("densenet_inet_layers", fn)
+    table["DenseFeatures"] = ("functional", "DenseFeatures")
     if name in ("optimization", "resnet_cifar_layers", "resnet_inet_layers", "mobilenet_cifar_layers",
-                "mobilenet_inet_layers"):    # the modules themselves
+                "mobilenet_inet_layers", "densenet_cifar_layers", "densenet_inet_layers"):    # the modules themselves
         return importlib.import_module("." + name, __name__)
     if name in table:
         mod, attr = table[name]

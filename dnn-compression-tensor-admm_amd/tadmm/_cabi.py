@@ -251,6 +251,26 @@ class DwBnDesc(C.Structure):
     ]
 
 
+DENSEBN_MAX_SEGMENTS = 128                  # TADMM_DENSEBN_MAX_SEGMENTS
+
+
+class DenseBnSeg(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("stats", C.c_void_p), ("dx", C.c_void_p), ("C", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DenseBnDesc(C.Structure):
+    _fields_ = [
+        ("seg", DenseBnSeg * DENSEBN_MAX_SEGMENTS),
+        ("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+        ("num_batches_tracked", C.c_void_p),
+        ("y", C.c_void_p), ("g", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("eps", C.c_double), ("momentum", C.c_double),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("nseg", C.c_int32),
+        ("dtype", C.c_int32), ("training", C.c_int32), ("relu", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -401,6 +421,13 @@ ABI = {
     "tadmm_bnact_workspace_bytes": (C.c_int, [C.POINTER(BnActDesc), C.POINTER(C.c_size_t)]),
     "tadmm_bnact_fwd": (C.c_int, [C.c_void_p, C.POINTER(BnActDesc), C.c_void_p]),
     "tadmm_bnact_bwd": (C.c_int, [C.c_void_p, C.POINTER(BnActDesc), C.c_void_p]),
+    "tadmm_densebn_desc_bytes": (C.c_int, []),
+    "tadmm_densebn_max_segments": (C.c_int, []),
+    "tadmm_densebn_fits": (C.c_int, [C.POINTER(DenseBnDesc), C.POINTER(C.c_int64)]),
+    "tadmm_densebn_workspace_bytes": (C.c_int, [C.POINTER(DenseBnDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_densebn_stats": (C.c_int, [C.c_void_p, C.POINTER(DenseBnDesc), C.c_void_p]),
+    "tadmm_densebn_fwd": (C.c_int, [C.c_void_p, C.POINTER(DenseBnDesc), C.c_void_p]),
+    "tadmm_densebn_bwd": (C.c_int, [C.c_void_p, C.POINTER(DenseBnDesc), C.c_void_p]),
     "tadmm_dwbn_desc_bytes": (C.c_int, []),
     "tadmm_dwbn_fits": (C.c_int, [C.POINTER(DwBnDesc), C.POINTER(C.c_int32)]),
     "tadmm_dwbn_plan": (C.c_int, [C.POINTER(DwBnDesc), C.POINTER(C.c_int32)]),
@@ -519,6 +546,9 @@ def load():
             raise TadmmLibraryError(f"{path}: tadmm_prenorm_desc layout mismatch")
         if lib.tadmm_bnact_desc_bytes() != C.sizeof(BnActDesc):
             raise TadmmLibraryError(f"{path}: tadmm_bnact_desc layout mismatch")
+        if lib.tadmm_densebn_desc_bytes() != C.sizeof(DenseBnDesc) \
+                or lib.tadmm_densebn_max_segments() != DENSEBN_MAX_SEGMENTS:
+            raise TadmmLibraryError(f"{path}: tadmm_densebn_desc layout mismatch")
         if lib.tadmm_dwbn_desc_bytes() != C.sizeof(DwBnDesc):
             raise TadmmLibraryError(f"{path}: tadmm_dwbn_desc layout mismatch")
         if lib.tadmm_core_conv_desc_bytes() != C.sizeof(CoreConvDesc):

@@ -1735,6 +1735,227 @@ def batch_norm_act_module(bn, x, residual=None, res_channel_offset: int = 0, rel
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# DenseNet pre-activation (csrc/densebn.hip): relu(bn(torch.cat(features, 1))) in front of every convolution of a dense
+# block of densenet_cifar_tt.py and densenet_inet_tt.py, with neither the concatenation nor repeated statistics.
+# ---------------------------------------------------------------------------------------------------------------
+class DenseFeatures:
+    """The feature tensors of one dense block, in order: a small list-like holder (`append`, `len`, indexing,
+    iteration, `channels`, `cat()`) that also keeps, per segment, the batch statistics `ops.densebn_stats` computed for
+    it -- float64 (C_k, 2) = (mean, biased variance), created on first use in training mode and kept for the life of
+    the holder: channel c of the concatenation holds the same numbers for every later layer of the block, so its mean
+    and variance are computed once per feature tensor, not once per consumer."""
+
+    def __init__(self, tensors=()):
+        self._segments = []
+        self._stats = []
+        for t in ([tensors] if isinstance(tensors, torch.Tensor) else tensors):
+            self.append(t)
+
+    def append(self, t):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError("DenseFeatures: a segment is an (N, C, H, W) tensor")
+        self._segments.append(t)
+        self._stats.append(None)
+        return self
+
+    def __len__(self):
+        return len(self._segments)
+
+    def __getitem__(self, i):
+        return self._segments[i]
+
+    def __iter__(self):
+        return iter(self._segments)
+
+    @property
+    def channels(self) -> int:
+        return sum(t.shape[1] for t in self._segments)
+
+    def cat(self):
+        """torch.cat(segments, 1); a single segment is returned as it is."""
+        return self._segments[0] if len(self._segments) == 1 else torch.cat(self._segments, 1)
+
+    def stats(self):
+        """One stats tensor per segment (two launches for each segment that has none yet)."""
+        for k, t in enumerate(self._segments):
+            if self._stats[k] is None:
+                self._stats[k] = ops.densebn_stats(t.detach())
+        return list(self._stats)
+
+
+def _dense_features(feats):
+    if isinstance(feats, DenseFeatures):
+        return feats
+    return DenseFeatures(feats)
+
+
+class _DenseBnFn(torch.autograd.Function):
+    """The tensor inputs are weight, bias and the segments.  `buffers` = (running_mean, running_var,
+    num_batches_tracked), updated in place by the launch, and `stats` (one per segment, from the holder) are handed over
+    as tuples: they are no inputs of the graph.  The backward returns one fresh contiguous gradient per segment that
+    needs one; torch's own accumulation adds the contributions of the layers that share a segment."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, buffers, stats, training, momentum, eps, relu, *segments):
+        running_mean, running_var, nbt = buffers
+        y = ops.densebn_fwd(segments, stats, weight, bias, running_mean, running_var, training=training,
+                            momentum=momentum, eps=eps, relu=relu, num_batches_tracked=nbt)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(y, weight, *segments)
+            ctx.stats = stats
+        ctx.cfg = (eps, relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, weight, *segments = ctx.saved_tensors
+        eps, relu = ctx.cfg
+        need = ctx.needs_input_grad
+        dxs, dgamma, dbeta = ops.densebn_bwd(g, y if relu else None, segments, ctx.stats, weight, eps=eps, relu=relu,
+                                             need_dx=need[8:], need_dgamma=need[0], need_dbeta=need[1])
+        return (dgamma, dbeta) + (None,) * 6 + tuple(dxs)
+
+
+def _dense_batch_norm_act_args(feats, running_mean, running_var, weight, bias, momentum, who):
+    if len(feats) < 1:
+        raise ValueError(f"{who}: at least one feature tensor is needed")
+    c = feats.channels
+    for n, t in (("running_mean", running_mean), ("running_var", running_var), ("weight", weight), ("bias", bias)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (c,)):
+            raise ValueError(f"{who}: {n} must be a ({c},) tensor or None")
+    if momentum is not None and not 0.0 <= float(momentum) <= 1.0:
+        raise ValueError(f"{who}: momentum must be in [0, 1] or None (got {momentum})")
+
+
+def dense_batch_norm_act_composed(feats, running_mean, running_var, weight, bias, *, training: bool, momentum=0.1,
+                                  eps: float = 1e-5, relu: bool = True, num_batches_tracked=None):
+    """`dense_batch_norm_act` from torch operations, under autograd, on any device and in float64: `torch.cat` of the
+    feature tensors, `F.batch_norm`, `F.relu`.  As nn.BatchNorm2d does, a training call first adds one to
+    `num_batches_tracked` (where given and the running statistics are tracked) and `momentum=None` is the cumulative
+    average 1 / num_batches_tracked.  The route for everything the launch refuses and the yardstick of
+    tests/test_gpu_densebn.py and scripts/bench_densenet_block.py."""
+    feats = _dense_features(feats)
+    _dense_batch_norm_act_args(feats, running_mean, running_var, weight, bias, momentum, "dense_batch_norm_act_composed")
+    factor = 0.0 if momentum is None else float(momentum)
+    if training and running_mean is not None and num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+        if momentum is None:
+            factor = 1.0 / float(num_batches_tracked)
+    y = F.batch_norm(feats.cat(), running_mean, running_var, weight, bias, training, factor, eps)
+    return F.relu(y) if relu else y
+
+
+def dense_batch_norm_act_launch_refusal(is_cuda: bool, dtypes, shapes, grad: bool, training: bool,
+                                        contiguous: bool = True, param_dtypes=(torch.float32,), affine: bool = True,
+                                        tracked: bool = True, momentum_given: bool = True, foreign: bool = False):
+    """None when csrc/densebn.hip takes a call with these properties, else the reason it does not (a string).  `dtypes`
+    and `shapes` are those of the feature tensors, in order.  Reasons: CPU tensors, mixed types, a type other than float32
+    / bfloat16 / float16, float16 with gradients, a step in eval mode, a segment that is not NCHW contiguous, segments
+    whose (N, H, W) differ, more segments than `ops.densebn_max_segments()`, more values per channel than the launch
+    takes, one value per channel in training, parameters or running statistics that are missing (`affine=False`,
+    `track_running_stats=False`) or not float32, `momentum=None`, or an operand on another device (`foreign`).  A pure
+    function."""
+    if not is_cuda:
+        return "operands that are not on a HIP device"
+    dtypes, shapes = tuple(dtypes), tuple(tuple(s) for s in shapes)
+    if len(set(dtypes)) != 1:
+        return "feature tensors of mixed types"
+    if dtypes[0] not in ops.DENSEBN_DTYPES:
+        return f"{dtypes[0]} operands"
+    if dtypes[0] == torch.float16 and grad:
+        return "float16 with gradients"
+    if grad and not training:
+        return "eval mode with gradients"
+    if not contiguous:
+        return "a feature tensor that is not NCHW contiguous"
+    if any(len(s) != 4 or min(s) < 1 for s in shapes) or len({(s[0], s[2], s[3]) for s in shapes}) != 1:
+        return "feature tensors of mixed shapes"
+    if len(shapes) > ops.densebn_max_segments():
+        return f"{len(shapes)} feature tensors (at most {ops.densebn_max_segments()})"
+    n, _, h, w = shapes[0]
+    if not ops.densebn_fits(n, [s[1] for s in shapes], h, w, dtypes[0]):
+        return f"shape = {(n, sum(s[1] for s in shapes), h, w)}"
+    if training and n * h * w < 2:
+        return "one value per channel in training"
+    if not affine:
+        return "affine=False"
+    if not tracked:
+        return "track_running_stats=False"
+    if any(d != torch.float32 for d in param_dtypes):
+        return "parameters or running statistics that are not float32"
+    if not momentum_given:
+        return "momentum=None"
+    if foreign:
+        return "a feature tensor, parameter or buffer on another device"
+    return None
+
+
+def dense_batch_norm_act(feats, running_mean, running_var, weight, bias, *, training: bool, momentum=0.1,
+                         eps: float = 1e-5, relu: bool = True, num_batches_tracked=None, route: str = None):
+    """The pre-activation of a DenseNet layer,
+
+        y = act(weight (cat(feats, 1) - mean) / sqrt(var + eps) + bias),    act = relu or the identity,
+
+    over the feature tensors `feats` (a `DenseFeatures`, a sequence of (N, C_k, H, W) tensors, or a plain tensor as a
+    one-segment list) with the arguments of `F.batch_norm`: batch statistics (biased variance) when `training`, which
+    also updates `running_mean` / `running_var` in place (momentum, unbiased variance) and adds one to
+    `num_batches_tracked`; the running statistics otherwise.  Differentiable in every feature tensor, weight and bias.
+    `route`: None (the launch where it takes the call and the measured rule `ops.densebn_pays` says it is ahead),
+    "launch" (csrc/densebn.hip: every channel read from the tensor that owns it, y written once; the batch statistics
+    of a feature tensor are computed once, by the `DenseFeatures` that holds it, so hand the same holder to every layer
+    of a block; two launches backward) or "composed" (torch.cat + F.batch_norm + relu).  The launch takes NCHW-contiguous
+    HIP tensors of one type, float32 or bfloat16 (float16 without gradients), with float32 parameters and running
+    statistics, a momentum, and gradients only in training mode.  Everything else goes to the composed route under
+    `route=None` and raises under `route="launch"`."""
+    who = "dense_batch_norm_act"
+    if route not in (None, "launch", "composed"):
+        raise ValueError(f"{who}: route is None, 'launch' or 'composed' (got {route!r})")
+    feats = _dense_features(feats)
+    _dense_batch_norm_act_args(feats, running_mean, running_var, weight, bias, momentum, who)
+    training = bool(training)
+    segments = list(feats)
+    x0 = segments[0]
+    grad = _needs_grad(weight, bias, *segments)
+    params = [t for t in (weight, bias, running_mean, running_var) if t is not None]
+    foreign = any(t.device != x0.device for t in params + segments) \
+        or (num_batches_tracked is not None and (num_batches_tracked.device != x0.device
+                                                 or num_batches_tracked.dtype != torch.int64))
+    why = None
+    if route != "composed":
+        why = dense_batch_norm_act_launch_refusal(
+            all(t.is_cuda for t in segments), [t.dtype for t in segments], [t.shape for t in segments], grad, training,
+            all(t.is_contiguous() for t in segments), tuple(t.dtype for t in params),
+            weight is not None and bias is not None, running_mean is not None and running_var is not None,
+            momentum is not None, foreign)
+    if route == "launch" and why is not None:
+        raise TadmmError(-1, f"{who}: route='launch' cannot take {why}")
+    launch = route != "composed" and why is None and (
+        route == "launch" or ops.densebn_pays(x0.shape[0], feats.channels, x0.shape[2] * x0.shape[3], len(segments),
+                                              x0.dtype, grad))
+    if not launch:
+        return dense_batch_norm_act_composed(feats, running_mean, running_var, weight, bias, training=training,
+                                             momentum=momentum, eps=eps, relu=relu,
+                                             num_batches_tracked=num_batches_tracked)
+    stats = tuple(feats.stats()) if training else None
+    return _DenseBnFn.apply(weight, bias, (running_mean, running_var, num_batches_tracked), stats, training,
+                            float(momentum), float(eps), bool(relu), *segments)
+
+
+def dense_batch_norm_act_module(bn, feats, route: str = None, relu: bool = True):
+    """`dense_batch_norm_act` with the parameters, buffers and mode of the module `bn`.  An nn.BatchNorm2d keeps its
+    state-dict keys and semantics (batch statistics in training mode or when it tracks none); any other norm layer is
+    called on the concatenation and the ReLU is composed behind it."""
+    feats = _dense_features(feats)
+    if not isinstance(bn, torch.nn.BatchNorm2d):
+        y = bn(feats.cat())
+        return F.relu(y) if relu else y
+    training = bn.training or (bn.running_mean is None and bn.running_var is None)
+    return dense_batch_norm_act(feats, bn.running_mean, bn.running_var, bn.weight, bn.bias, training=training,
+                                momentum=bn.momentum, eps=bn.eps, relu=relu,
+                                num_batches_tracked=bn.num_batches_tracked if bn.training else None, route=route)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # MobileNetV2 depthwise stage (csrc/dwbn.hip): relu6(bn(depthwise_conv3x3(x))), the middle of every inverted-residual
 # block of mobilenetv2_cifar_tt.py and mobilenetv2_tt.py.
 # ---------------------------------------------------------------------------------------------------------------

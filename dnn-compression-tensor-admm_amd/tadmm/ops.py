@@ -8,6 +8,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import functools
+import struct
 import weakref
 from typing import List, Optional, Sequence
 
@@ -2710,6 +2711,245 @@ def bnact_pays(n: int, c: int, hw: int, dtype, grad: bool = False, residual: boo
     if dtype == torch.float32:
         return total >= (32 * 512 * 784 if residual else 32 * 64 * 3136)
     return total >= 32 * 256 * 3136
+
+
+# ------------------------------------------------------------------ DenseNet pre-activation (csrc/densebn.hip)
+DENSEBN_DTYPES = BERTNORM_DTYPES
+
+
+_DENSEBN_ROWS = {}
+
+
+def _densebn_table(dsc, xs, stats, dxs, channels):
+    """Writes the first len(channels) rows of the segment table (data, stats and dx addresses, 0 for NULL, and the
+    channel counts) in one call: a ctypes store per field costs more than the launch of a small layer."""
+    k = len(channels)
+    rows = _DENSEBN_ROWS.get(k)
+    if rows is None:
+        rows = _DENSEBN_ROWS[k] = struct.Struct("=" + "QQQii" * k)
+    rows.pack_into(dsc, 0, *[v for row in zip(xs, stats, dxs, channels) for v in (*row, 0)])
+
+
+def _densebn_shape_desc(n, channels, h, w, dtype):
+    dsc = _cabi.DenseBnDesc()
+    channels = [int(c) for c in channels]
+    dsc.N, dsc.H, dsc.W, dsc.nseg, dsc.dtype = int(n), int(h), int(w), len(channels), DENSEBN_DTYPES[dtype]
+    channels = channels[:_cabi.DENSEBN_MAX_SEGMENTS]
+    zeros = [0] * len(channels)
+    if channels:
+        _densebn_table(dsc, zeros, zeros, zeros, channels)
+    return dsc
+
+
+def densebn_max_segments() -> int:
+    """The most feature tensors one `tadmm_densebn_fwd` / `_bwd` call takes (TADMM_DENSEBN_MAX_SEGMENTS: the segment
+    table travels in the kernel arguments).  Host only."""
+    return int(_cabi.load().tadmm_densebn_max_segments())
+
+
+def densebn_max_m() -> int:
+    """The most values per channel (N H W) the launches take (what `tadmm_densebn_fits` reports).  Host only."""
+    m = C.c_int64()
+    _cabi.load().tadmm_densebn_fits(None, C.byref(m))
+    return int(m.value)
+
+
+def densebn_fits(n: int, channels: Sequence[int], h: int, w: int, dtype=torch.float32) -> bool:
+    """True when the launches take segments of `channels` = (C_0, C_1, ...) channels over an (n, ., h, w) plane
+    (`tadmm_densebn_fits`: n h w <= `densebn_max_m()`, at most `densebn_max_segments()` segments).  Raises TadmmError for
+    a dimension or a C_k < 1 or an empty list.  Host only."""
+    rc = _cabi.load().tadmm_densebn_fits(C.byref(_densebn_shape_desc(n, channels, h, w, dtype)), None)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_densebn_fits: n, channels, h, w = {(n, tuple(channels), h, w)}")
+    return rc == 1
+
+
+def densebn_workspace_bytes(n: int, channels: Sequence[int], h: int, w: int, dtype=torch.float32) -> int:
+    """Bytes of the workspace of `densebn_stats` (channels = (C_k,)) and of `densebn_bwd` (every segment's channels)
+    (`tadmm_densebn_workspace_bytes`: a pair of doubles per channel and split for min(trips, 128, ceil(2048 / C)) splits,
+    C the sum of `channels`, a trip being 1024 float32 or 2048 16-bit values; rounded up to 256 bytes).  Host only."""
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_densebn_workspace_bytes(C.byref(_densebn_shape_desc(n, channels, h, w, dtype)), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_densebn_workspace_bytes: n, channels, h, w = {(n, tuple(channels), h, w)}")
+    return int(size.value)
+
+
+def _densebn_segments(segments, who):
+    """The segments checked against the first: (list, (n, channels, h, w), device, dtype)."""
+    segments = list(segments)
+    if not segments or len(segments) > _cabi.DENSEBN_MAX_SEGMENTS:
+        raise TadmmError(-1, f"{who}: 1 .. {_cabi.DENSEBN_MAX_SEGMENTS} segments are taken (got {len(segments)})")
+    x0 = _operand(segments[0], who, "segment 0", tuple(DENSEBN_DTYPES))
+    if x0.dim() != 4 or min(x0.shape) < 1:
+        raise TadmmError(-1, f"{who}: a segment must be (N, C, H, W) with every dimension >= 1 (got {tuple(x0.shape)})")
+    n, c0, h, w = x0.shape
+    channels = [c0]
+    for k in range(1, len(segments)):
+        x = segments[k]
+        ok = isinstance(x, torch.Tensor) and x.dim() == 4 and x.dtype == x0.dtype and x.device == x0.device \
+            and x.is_contiguous()
+        if not ok or x.shape[1] < 1 or (x.shape[0], x.shape[2], x.shape[3]) != (n, h, w):
+            x = _operand(x, who, f"segment {k}", (x0.dtype,))         # words the common refusals
+            raise TadmmError(-1, f"{who}: segment {k} must be ({n}, C, {h}, {w}) on {x0.device} (got {tuple(x.shape)} on "
+                                 f"{x.device})")
+        channels.append(x.shape[1])
+    return segments, (n, channels, h, w), x0.device, x0.dtype
+
+
+def _densebn_stats_ptrs(stats, channels, dev, who):
+    if stats is None or len(stats) != len(channels):
+        raise TadmmError(-1, f"{who}: one stats tensor per segment is read")
+    for k, st in enumerate(stats):
+        ok = isinstance(st, torch.Tensor) and st.dtype == torch.float64 and st.device == dev and st.is_contiguous() \
+            and tuple(st.shape) == (channels[k], 2)
+        if not ok:
+            _operand(st, who, f"stats {k}", (torch.float64,), (channels[k], 2))
+            raise TadmmError(-1, f"{who}: stats {k} on {st.device}, the segments on {dev}")
+    return [st.data_ptr() for st in stats]
+
+
+def _densebn_workspace(dsc, dev, who):
+    size = C.c_size_t()
+    rc = _cabi.load().tadmm_densebn_workspace_bytes(C.byref(dsc), C.byref(size))
+    if rc < 0:
+        raise TadmmError(rc, f"{who}: tadmm_densebn_workspace_bytes")
+    ws = _scratch(size.value, dev)
+    dsc.workspace, dsc.workspace_bytes = ws.data_ptr(), size.value
+    return ws
+
+
+def densebn_stats(x, out=None):
+    """stats of `tadmm_densebn_stats` for ONE contiguous (N, C, H, W) feature tensor (float32, bfloat16 or float16):
+    float64 (C, 2) = (batch mean, biased batch variance) per channel, into `out` where given.  The variance is stored,
+    not rstd: every layer that consumes the tensor applies its own eps.  Two launches, no atomics; nothing synchronises."""
+    who = "densebn_stats"
+    (x,), (n, (c,), h, w), dev, dt = _densebn_segments([x], who)
+    stats = _output(out, (c, 2), torch.float64, dev, "stats")
+    dsc = _cabi.DenseBnDesc()
+    dsc.N, dsc.H, dsc.W, dsc.nseg, dsc.dtype = n, h, w, 1, DENSEBN_DTYPES[dt]
+    _densebn_table(dsc, [x.data_ptr()], [stats.data_ptr()], [0], [c])
+    _ws = _densebn_workspace(dsc, dev, who)                  # noqa: F841 (held until the launches are queued)
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_densebn_stats(hd.ptr, C.byref(dsc), _stream(dev)))
+    return stats
+
+
+def densebn_fwd(segments, stats, gamma, beta, running_mean, running_var, *, training: bool, momentum: float = 0.1,
+                eps: float = 1e-5, relu: bool = True, num_batches_tracked=None):
+    """y of `tadmm_densebn_fwd`: act(BatchNorm2d(cat(segments, 1))) as one contiguous (N, sum C_k, H, W) tensor, with no
+    concatenation formed.  `segments`: contiguous (N, C_k, H, W) tensors of one type (float32, bfloat16 or float16);
+    `stats`: what `densebn_stats` returned for each of them (read with `training`; None otherwise).  `gamma`, `beta`,
+    `running_mean`, `running_var`: float32 (sum C_k,), those of the consuming layer.  With `training` the running
+    statistics (both or neither) are updated in place with `momentum` and the unbiased variance and
+    `num_batches_tracked` (int64 scalar tensor, optional) rises by one.  Without, the running statistics are read and
+    nothing but y is written.  One launch either way; nothing synchronises."""
+    who = "densebn_fwd"
+    segments, (n, channels, h, w), dev, dt = _densebn_segments(segments, who)
+    c = sum(channels)
+    dsc = _cabi.DenseBnDesc()
+    dsc.N, dsc.H, dsc.W, dsc.nseg, dsc.dtype = n, h, w, len(segments), DENSEBN_DTYPES[dt]
+    hold = []
+    zeros = [0] * len(segments)
+    _densebn_table(dsc, [x.data_ptr() for x in segments],
+                   _densebn_stats_ptrs(stats, channels, dev, who) if training else zeros, zeros, channels)
+    for name, t in (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is None and name.startswith("running") and training:
+            continue
+        # the running statistics are updated in place: a copy would take the update with it
+        t = _operand(t, who, name, (torch.float32,), (c,), layout="raise" if name.startswith("running") else "copy")
+        hold.append(t)
+        setattr(dsc, name, t.data_ptr())
+    if num_batches_tracked is not None and training:
+        nbt = _operand(num_batches_tracked, who, "num_batches_tracked", (torch.int64,), ())
+        hold.append(nbt)
+        dsc.num_batches_tracked = nbt.data_ptr()
+    for t in hold:
+        if t.device != dev:
+            raise TadmmError(-1, f"{who}: an operand on {t.device}, the segments on {dev}")
+    dsc.eps, dsc.momentum, dsc.training, dsc.relu = float(eps), float(momentum), int(bool(training)), int(bool(relu))
+    y = torch.empty((n, c, h, w), dtype=dt, device=dev)
+    dsc.y = y.data_ptr()
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_densebn_fwd(hd.ptr, C.byref(dsc), _stream(dev)))
+    return y
+
+
+def densebn_bwd(g, y, segments, stats, gamma, *, eps: float = 1e-5, relu: bool = True, need_dx=None,
+                need_dgamma: bool = True, need_dbeta: bool = True):
+    """(dxs, dgamma, dbeta) of `tadmm_densebn_bwd` for the gradient `g` (N, sum C_k, H, W) of y: float32 or bfloat16
+    (float16 is refused).  `y` is the output as `densebn_fwd(training=True)` stored it (the ReLU mask is y > 0; None
+    without relu), `segments`, `stats`, `gamma` and `eps` what it was called with.  dxs: one fresh contiguous
+    (N, C_k, H, W) gradient per segment, None where `need_dx[k]` is false (a sequence of one flag per segment; None
+    wants all) -- such a segment is only summed, and nothing of it is written.  dgamma and dbeta: float32 (sum C_k,) or
+    None.  Two launches, no atomics, bitwise reproducible; nothing synchronises."""
+    who = "densebn_bwd"
+    segments, (n, channels, h, w), dev, dt = _densebn_segments(segments, who)
+    c = sum(channels)
+    need_dx = [True] * len(segments) if need_dx is None else [bool(v) for v in need_dx]
+    if len(need_dx) != len(segments):
+        raise TadmmError(-1, f"{who}: need_dx has {len(need_dx)} flags for {len(segments)} segments")
+    dsc = _cabi.DenseBnDesc()
+    dsc.N, dsc.H, dsc.W, dsc.nseg, dsc.dtype = n, h, w, len(segments), DENSEBN_DTYPES[dt]
+    gamma = _operand(gamma, who, "gamma", (torch.float32,), (c,), layout="copy")
+    g = _operand(g, who, "g", (dt,), (n, c, h, w), layout="copy")
+    dsc.gamma, dsc.g = gamma.data_ptr(), g.data_ptr()
+    if relu:
+        y = _operand(y, who, "y", (dt,), (n, c, h, w), layout="copy")
+        dsc.y = y.data_ptr()
+    dxs = [torch.empty_like(x) if want else None for x, want in zip(segments, need_dx)]
+    _densebn_table(dsc, [x.data_ptr() for x in segments], _densebn_stats_ptrs(stats, channels, dev, who),
+                   [0 if dx is None else dx.data_ptr() for dx in dxs], channels)
+    dgamma = torch.empty(c, dtype=torch.float32, device=dev) if need_dgamma else None
+    dbeta = torch.empty(c, dtype=torch.float32, device=dev) if need_dbeta else None
+    dsc.dgamma = None if dgamma is None else dgamma.data_ptr()
+    dsc.dbeta = None if dbeta is None else dbeta.data_ptr()
+    dsc.eps, dsc.relu, dsc.training = float(eps), int(bool(relu)), 1
+    _ws = _densebn_workspace(dsc, dev, who) if any(need_dx) or need_dgamma or need_dbeta else None      # noqa: F841
+    hd = _handle(dev)
+    hd.check(hd.lib.tadmm_densebn_bwd(hd.ptr, C.byref(dsc), _stream(dev)))
+    return dxs, dgamma, dbeta
+
+
+def densebn_pays(n: int, c: int, hw: int, nseg: int, dtype, grad: bool = False) -> bool:
+    """True when `functional.dense_batch_norm_act` sends a call the launch can take to it and not to the composed torch
+    route (`torch.cat` + `F.batch_norm` + relu).  A pure function of its arguments: n the batch, c the channels of the
+    concatenation, hw the plane, nseg the feature tensors, grad whether a gradient is wanted.  Measured
+    (scripts/bench_densenet_block.py, two runs) at the first, middle and last layer of every block,
+    every transition and the final norm of DenseNet-40 (n in {1, 128}; hw 1024, 256, 64; c 32 .. 344; nseg 1, 7, 12, 13)
+    and DenseNet-121 (n in {1, 32}; hw 3136, 784, 196, 49; c 64 .. 1024; nseg 1 .. 25), float32 and bfloat16, a forward
+    in eval mode under no_grad and a training step in which the launch computes the statistics of the newest feature
+    tensor only, against `dense_batch_norm_act_composed` in the same run.  Both routes are bound by the host in most
+    classes: the launch costs 0.027 ms + 0.0022 ms per feature tensor for a forward (0.080 ms at 25 tensors) and 0.11 ms +
+    0.010 ms per tensor for a step, whatever the sizes measured; the composed route 0.019 - 0.036 ms and 0.063 - 0.19 ms
+    at a batch of one.  The launch's slowest window is below the composed route's fastest in both runs for
+      * the forward at n = 128 on planes of 1024 and 256 values in every class (1.30x - 2.76x; one tensor 1.3x - 1.6x,
+        thirteen tensors at hw 1024 2.7x float32, 2.0x bfloat16), and on the 64-value plane in bfloat16 (1.18x - 1.42x;
+        float32 there 0.91x - 1.19x, not taken);
+      * the forward at n = 32, hw 3136 from four feature tensors (1.44x - 2.62x); with one tensor the composed route
+        leads (0.82x - 0.89x: nothing is concatenated), and on planes of 784 values and below it leads or is level
+        (0.46x - 1.02x);
+      * the training step at n = 128, hw 1024 with 12 and 13 tensors (208 and 224 channels: 1.51x - 1.66x float32,
+        1.19x - 1.26x bfloat16; with 7 tensors and 128 channels one run was ahead, 1.2x, and one behind, 0.7x - 0.8x);
+      * the training step at n = 32, hw 3136 with 4, 6 and 7 tensors in float32 (1.41x - 1.94x) and with 6 and 7 in
+        bfloat16 (1.29x - 1.36x; with 4 tensors 1.22x, but a window of one run overlapped).
+    Every class at a batch of one (0.43x - 0.90x) and every other step (0.51x - 0.95x) is behind.  A whole dense block's
+    training step with every BatchNorm forced to the launch is ahead for block 1 of tkr_densenet40 at n = 128 (9.25 -
+    9.33 ms against 9.98 - 9.99, 1.07x - 1.08x) and denseblock1 of tkc_densenet121 at n = 32 (6.17 - 6.63 against 6.97 -
+    6.98, 1.05x - 1.13x).  So: a forward from n = 128 and hw = 256 (16-bit: hw = 64), or from four tensors on planes of
+    at least 3136 values with 32 * 160 * 3136 values in all; a step from four tensors and either 128 * 208 * 1024 values
+    or hw >= 3136 with 32 * 160 * 3136 values (16-bit: 32 * 224 * 3136).  Not measured: batch sizes between 1 and 32 /
+    128 and beyond, other planes, widths and growth rates, more than 25 feature tensors, float16 (treated as bfloat16),
+    a step in eval mode (the composed route takes it)."""
+    total = int(n) * int(c) * int(hw)
+    wide = dtype == torch.float32
+    if not grad:
+        if n >= 128 and hw >= (256 if wide else 64):
+            return True
+        return nseg >= 4 and hw >= 3136 and total >= 32 * 160 * 3136
+    if nseg < 4:
+        return False
+    return total >= 128 * 208 * 1024 or (hw >= 3136 and total >= 32 * (160 if wide else 224) * 3136)
 
 
 # ------------------------------------------------------------------ MobileNetV2 depthwise stage (csrc/dwbn.hip)

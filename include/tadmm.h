@@ -976,6 +976,80 @@ int tadmm_dwbn_workspace_bytes(const tadmm_dwbn_desc* d, size_t* bytes);
 int tadmm_dwbn_fwd(tadmm_handle h, const tadmm_dwbn_desc* d, void* stream);
 int tadmm_dwbn_bwd(tadmm_handle h, const tadmm_dwbn_desc* d, void* stream);
 
+/* ---- DenseNet pre-activation: BatchNorm2d and ReLU over a list of feature tensors (csrc/densebn.hip) ------------------
+ * densenet_cifar_tt.py / densenet_inet_tt.py: relu(bn(torch.cat(features, 1))) in front of every convolution of a dense
+ * block, with neither the concatenation nor a second statistics pass over channels an earlier layer has seen.
+ * Segment k = 0 .. nseg - 1 (nseg <= TADMM_DENSEBN_MAX_SEGMENTS) is x_k: (N, C_k, H, W) of `dtype`, NCHW contiguous, any
+ * element-aligned base; channel c of the concatenation, C = sum C_k wide, is channel c - first_k of the segment with
+ * first_k <= c < first_k + C_k.  M = N H W values per channel.  16-byte accesses when every base in use is 16-byte
+ * aligned and H W is a whole number of 16-byte units; element accesses otherwise.  The segment table travels in the
+ * kernel arguments: no host-to-device copy, no host synchronisation.  gamma, beta, running_mean, running_var: float32
+ * (C), those of the consuming layer.
+ * tadmm_densebn_stats takes ONE segment (nseg == 1; seg[0].x, seg[0].stats, seg[0].C), two launches: per-(channel,
+ * split) sums of x - K and (x - K)^2 in double to the workspace (K = x[0, c, 0, 0], so a channel with mean >> std keeps
+ * its variance), then the partials of a channel are added in ascending order into stats_k, double (C_k, 2) = (mean,
+ * biased variance).  The variance is stored, not rstd: a channel's batch statistics are the same for every later layer
+ * of the block, and every consuming layer applies its own eps.
+ * tadmm_densebn_fwd with training != 0, ONE launch: rstd_c = 1 / sqrt(var_c + eps) in double from the segment's stats,
+ *   y[n, c, h, w] = act(gamma_c (x_k[n, c - first_k, h, w] - mean_c) rstd_c + beta_c),    act = relu or the identity,
+ * written to one contiguous (N, C, H, W) tensor.  running_mean and running_var (given together, or both NULL) become
+ * (1 - momentum) old + momentum new, the new variance unbiased (M / (M - 1)); num_batches_tracked (int64, nullable)
+ * rises by one.  With training == 0, one launch: a_c = gamma_c / sqrt(running_var_c + eps), b_c = beta_c -
+ * running_mean_c a_c, y = act(a x + b); no stats are read, nothing but y is written.  The forward needs no workspace.
+ * tadmm_densebn_bwd (training mode; float32 and bfloat16) reads g (the gradient of y, contiguous (N, C, H, W)), y as the
+ * forward stored it (only when relu), every x_k and stats_k, gamma and eps; gz = g (y > 0), or g without relu; xhat =
+ * (x - mean) rstd.  Two launches: partial sums of gz and gz xhat in double, then
+ *   dbeta_c = sum gz,  dgamma_c = sum gz xhat  (float32 (C), each nullable),   dx = gamma rstd (gz - dbeta / M - xhat dgamma / M)
+ * with dx written per segment into seg[k].dx, that segment's own contiguous (N, C_k, H, W) output.  A NULL seg[k].dx
+ * means the segment wants no gradient: its channels are only summed (and not even that without dgamma and dbeta).
+ * With no output nothing is launched.
+ * No atomics; grids depend on (N, C, H W, dtype) alone: bitwise reproducible.  The workspace
+ * (tadmm_densebn_workspace_bytes, reads N, H, W, dtype, nseg and every C_k; 16-byte aligned) is sized as bnact's for the
+ * C = sum C_k channels of the call: C min(trips, 128, ceil(2048 / C)) pairs of doubles.  _stats and _bwd need it.
+ * tadmm_densebn_fits is host only: 1 for N H W <= 2^31 - 4096 (*max_m, nullable, receives the bound), nseg <=
+ * TADMM_DENSEBN_MAX_SEGMENTS and C <= (2^31 - 1) / 128, 0 above, TADMM_ERR_INVALID for a NULL descriptor, N, H, W or nseg
+ * < 1 or a C_k < 1.  The launches return TADMM_ERR_UNSUPPORTED where N H W or C is above the bound and
+ * TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or descriptor; N, H or W < 1; nseg < 1 or above the
+ * maximum (other than 1 in _stats); a C_k < 1; training (_stats, _bwd) with M < 2; an unknown dtype; TADMM_CHAIN_F16 in
+ * _bwd; eps negative or not finite; momentum outside [0, 1]; an x_k or gamma NULL; a pointer not aligned to its element;
+ * stats_k NULL in training mode, _stats and _bwd; in _fwd beta or y NULL, y overlapping a segment, eval mode without
+ * running statistics, one running statistic without the other; in _bwd g NULL, y NULL with relu, a dx_k equal to x_k, g
+ * or y.  TADMM_ERR_WORKSPACE: the workspace is needed and NULL, misaligned or short. */
+#define TADMM_DENSEBN_MAX_SEGMENTS 128
+typedef struct {
+  const void* x;                              /* (N, C, H, W) */
+  double* stats;                              /* (C, 2) = (mean, biased variance); _stats writes it, training reads it */
+  void* dx;                                   /* backward; (N, C, H, W); nullable */
+  int32_t C;
+  int32_t reserved;
+} tadmm_densebn_seg;
+typedef struct {
+  tadmm_densebn_seg seg[TADMM_DENSEBN_MAX_SEGMENTS];
+  const float* gamma; const float* beta;      /* (sum C_k) */
+  float* running_mean; float* running_var;    /* training updates them (nullable there), eval reads them */
+  int64_t* num_batches_tracked;               /* training: += 1; nullable */
+  void* y;                                    /* (N, sum C_k, H, W); forward writes it, backward reads it when relu */
+  const void* g;                              /* backward */
+  float* dgamma; float* dbeta;                /* backward; each nullable */
+  void* workspace; size_t workspace_bytes;    /* _stats; backward with any output */
+  double eps;
+  double momentum;                            /* [0, 1] */
+  int32_t N, H, W;
+  int32_t nseg;
+  int32_t dtype;                              /* TADMM_CHAIN_F32 | TADMM_CHAIN_BF16 | TADMM_CHAIN_F16 (forward only) */
+  int32_t training;                           /* forward: nonzero = batch statistics, 0 = running statistics */
+  int32_t relu;
+  int32_t reserved;
+} tadmm_densebn_desc;
+/* sizeof(tadmm_densebn_desc) as the library was built */
+int tadmm_densebn_desc_bytes(void);
+int tadmm_densebn_max_segments(void);
+int tadmm_densebn_fits(const tadmm_densebn_desc* d, int64_t* max_m);
+int tadmm_densebn_workspace_bytes(const tadmm_densebn_desc* d, size_t* bytes);
+int tadmm_densebn_stats(tadmm_handle h, const tadmm_densebn_desc* d, void* stream);
+int tadmm_densebn_fwd(tadmm_handle h, const tadmm_densebn_desc* d, void* stream);
+int tadmm_densebn_bwd(tadmm_handle h, const tadmm_densebn_desc* d, void* stream);
+
 /* ---- TinyBERT layer losses: masked attention MSE and hidden-state MSE with gradients (csrc/layermse.hip) -------------
  * xcompression/task_distill.py:810-828 (also task_distill1.py, task_distill2.py, general_distill.py:438-451) for all
  * pairs of a step in two launches.  A call carries npairs <= TADMM_LAYER_MSE_MAX_PAIRS pairs; pair i is s (student)
