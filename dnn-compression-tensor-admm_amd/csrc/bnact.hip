@@ -420,6 +420,16 @@ int tadmm_bnact_workspace_bytes(const tadmm_bnact_desc* d, size_t* bytes) {
   return TADMM_OK;
 }
 
+int tadmm_bnact_plan(const tadmm_bnact_desc* d, int32_t* plan3) {
+  if (!d || !plan3 || d->N < 1 || d->C < 1 || d->H < 1 || d->W < 1) return TADMM_ERR_INVALID;
+  if (d->dtype != TADMM_CHAIN_F32 && d->dtype != TADMM_CHAIN_BF16 && d->dtype != TADMM_CHAIN_F16) return TADMM_ERR_INVALID;
+  const int64_t M = (int64_t)d->N * d->H * d->W;
+  if (M > kBaMaxM) return TADMM_ERR_UNSUPPORTED;
+  const BaPlan p = ba_plan(M, d->C, d->dtype == TADMM_CHAIN_F32 ? 4 : 2);
+  plan3[0] = p.S; plan3[1] = p.span; plan3[2] = p.cap;
+  return TADMM_OK;
+}
+
 int tadmm_bnact_fwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream_) {
   if (!h) return TADMM_ERR_INVALID;
   bool wide = false;

@@ -481,6 +481,17 @@ int tadmm_densebn_workspace_bytes(const tadmm_densebn_desc* d, size_t* bytes) {
   return TADMM_OK;
 }
 
+int tadmm_densebn_plan(const tadmm_densebn_desc* d, int32_t* plan3) {
+  if (!plan3 || !d || !db_dtype_ok(d->dtype)) return TADMM_ERR_INVALID;
+  const int64_t C = db_channels(d);
+  if (C < 1) return TADMM_ERR_INVALID;
+  const int64_t M = (int64_t)d->N * d->H * d->W;
+  if (M > kDbMaxM || C * (int64_t)kDbMaxSplit > INT32_MAX) return TADMM_ERR_UNSUPPORTED;
+  const DbPlan p = db_plan(M, C, d->dtype == TADMM_CHAIN_F32 ? 4 : 2);
+  plan3[0] = p.S; plan3[1] = p.span; plan3[2] = p.cap;
+  return TADMM_OK;
+}
+
 int tadmm_densebn_stats(tadmm_handle h, const tadmm_densebn_desc* d, void* stream_) {
   if (!h) return TADMM_ERR_INVALID;
   int64_t C = 0;

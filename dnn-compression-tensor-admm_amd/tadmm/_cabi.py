@@ -419,12 +419,14 @@ ABI = {
     "tadmm_bnact_desc_bytes": (C.c_int, []),
     "tadmm_bnact_fits": (C.c_int, [C.POINTER(BnActDesc), C.POINTER(C.c_int64)]),
     "tadmm_bnact_workspace_bytes": (C.c_int, [C.POINTER(BnActDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_bnact_plan": (C.c_int, [C.POINTER(BnActDesc), C.POINTER(C.c_int32)]),
     "tadmm_bnact_fwd": (C.c_int, [C.c_void_p, C.POINTER(BnActDesc), C.c_void_p]),
     "tadmm_bnact_bwd": (C.c_int, [C.c_void_p, C.POINTER(BnActDesc), C.c_void_p]),
     "tadmm_densebn_desc_bytes": (C.c_int, []),
     "tadmm_densebn_max_segments": (C.c_int, []),
     "tadmm_densebn_fits": (C.c_int, [C.POINTER(DenseBnDesc), C.POINTER(C.c_int64)]),
     "tadmm_densebn_workspace_bytes": (C.c_int, [C.POINTER(DenseBnDesc), C.POINTER(C.c_size_t)]),
+    "tadmm_densebn_plan": (C.c_int, [C.POINTER(DenseBnDesc), C.POINTER(C.c_int32)]),
     "tadmm_densebn_stats": (C.c_int, [C.c_void_p, C.POINTER(DenseBnDesc), C.c_void_p]),
     "tadmm_densebn_fwd": (C.c_int, [C.c_void_p, C.POINTER(DenseBnDesc), C.c_void_p]),
     "tadmm_densebn_bwd": (C.c_int, [C.c_void_p, C.POINTER(DenseBnDesc), C.c_void_p]),

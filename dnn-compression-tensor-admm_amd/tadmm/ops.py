@@ -2587,6 +2587,17 @@ def bnact_workspace_bytes(n: int, c: int, h: int, w: int, dtype=torch.float32) -
     return int(size.value)
 
 
+def bnact_plan(n: int, c: int, h: int, w: int, dtype=torch.float32) -> dict:
+    """The ownership `tadmm_bnact_plan` derives from (n h w, c, dtype) alone, as a dict: a channel's n h w values go to
+    `S` workgroups of `span` consecutive values each (a whole number of trips of 1024 float32 or 2048 16-bit values);
+    the workspace is sized for `cap` splits.  Host only."""
+    out = (C.c_int32 * 3)()
+    rc = _cabi.load().tadmm_bnact_plan(C.byref(_bnact_shape_desc(n, c, h, w, dtype)), out)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_bnact_plan: shape = {(n, c, h, w)}")
+    return dict(zip(("S", "span", "cap"), (int(v) for v in out)))
+
+
 def _bnact_desc(x, gamma, who):
     """The descriptor fields forward and backward share.  Returns (descriptor, tensors to keep alive, (shape, device,
     dtype))."""
@@ -2773,6 +2784,17 @@ def densebn_workspace_bytes(n: int, channels: Sequence[int], h: int, w: int, dty
     if rc < 0:
         raise TadmmError(rc, f"tadmm_densebn_workspace_bytes: n, channels, h, w = {(n, tuple(channels), h, w)}")
     return int(size.value)
+
+
+def densebn_plan(n: int, channels: Sequence[int], h: int, w: int, dtype=torch.float32) -> dict:
+    """The ownership `tadmm_densebn_plan` derives from (n h w, sum of `channels`, dtype) alone, as `bnact_plan` returns
+    it: channels = (C_k,) for the plan of `densebn_stats` on that segment, every segment's channels for the plan of
+    `densebn_fwd` and `densebn_bwd`.  Host only."""
+    out = (C.c_int32 * 3)()
+    rc = _cabi.load().tadmm_densebn_plan(C.byref(_densebn_shape_desc(n, channels, h, w, dtype)), out)
+    if rc < 0:
+        raise TadmmError(rc, f"tadmm_densebn_plan: n, channels, h, w = {(n, tuple(channels), h, w)}")
+    return dict(zip(("S", "span", "cap"), (int(v) for v in out)))
 
 
 def _densebn_segments(segments, who):

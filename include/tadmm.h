@@ -870,7 +870,9 @@ int tadmm_prenorm_bwd(tadmm_handle h, const tadmm_prenorm_desc* d, void* stream)
  * No atomics; grids depend on (N, C, H W, dtype) alone: bitwise reproducible; no host synchronisation.  The workspace
  * (tadmm_bnact_workspace_bytes, reads N, C, H, W, dtype; 16-byte aligned) is sized for C min(trips, 128, ceil(2048 / C))
  * pairs of doubles, a trip being 256 * 16 / sizeof(element) values (at most 2048); a channel's splits are that many,
- * evened out so that none is empty.  The size never falls as N, H or W grows.
+ * evened out so that none is empty.  The size never falls as N, H or W grows.  tadmm_bnact_plan is host only and refuses
+ * as _workspace_bytes does: plan3 = S, span, cap -- the S workgroups of a channel own `span` consecutive values each (a
+ * whole number of trips) and the workspace is sized for `cap` of them.
  * tadmm_bnact_fits is host only: 1 for N H W <= 2^31 - 4096 (*max_m, nullable, receives the bound), 0 above,
  * TADMM_ERR_INVALID for a NULL descriptor or N, C, H or W < 1.  The launches return TADMM_ERR_UNSUPPORTED where _fits
  * returns 0 and TADMM_ERR_INVALID, with nothing launched, for: a NULL handle or descriptor; N, C, H or W < 1; training
@@ -904,6 +906,7 @@ typedef struct {
 int tadmm_bnact_desc_bytes(void);
 int tadmm_bnact_fits(const tadmm_bnact_desc* d, int64_t* max_m);
 int tadmm_bnact_workspace_bytes(const tadmm_bnact_desc* d, size_t* bytes);
+int tadmm_bnact_plan(const tadmm_bnact_desc* d, int32_t* plan3);
 int tadmm_bnact_fwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream);
 int tadmm_bnact_bwd(tadmm_handle h, const tadmm_bnact_desc* d, void* stream);
 
@@ -1006,6 +1009,8 @@ int tadmm_dwbn_bwd(tadmm_handle h, const tadmm_dwbn_desc* d, void* stream);
  * No atomics; grids depend on (N, C, H W, dtype) alone: bitwise reproducible.  The workspace
  * (tadmm_densebn_workspace_bytes, reads N, H, W, dtype, nseg and every C_k; 16-byte aligned) is sized as bnact's for the
  * C = sum C_k channels of the call: C min(trips, 128, ceil(2048 / C)) pairs of doubles.  _stats and _bwd need it.
+ * tadmm_densebn_plan is host only and refuses as _workspace_bytes does: plan3 = S, span, cap as tadmm_bnact_plan writes
+ * them, over the descriptor's channels -- one segment for the plan of its _stats launch, all of them for _fwd and _bwd.
  * tadmm_densebn_fits is host only: 1 for N H W <= 2^31 - 4096 (*max_m, nullable, receives the bound), nseg <=
  * TADMM_DENSEBN_MAX_SEGMENTS and C <= (2^31 - 1) / 128, 0 above, TADMM_ERR_INVALID for a NULL descriptor, N, H, W or nseg
  * < 1 or a C_k < 1.  The launches return TADMM_ERR_UNSUPPORTED where N H W or C is above the bound and
@@ -1046,6 +1051,7 @@ int tadmm_densebn_desc_bytes(void);
 int tadmm_densebn_max_segments(void);
 int tadmm_densebn_fits(const tadmm_densebn_desc* d, int64_t* max_m);
 int tadmm_densebn_workspace_bytes(const tadmm_densebn_desc* d, size_t* bytes);
+int tadmm_densebn_plan(const tadmm_densebn_desc* d, int32_t* plan3);
 int tadmm_densebn_stats(tadmm_handle h, const tadmm_densebn_desc* d, void* stream);
 int tadmm_densebn_fwd(tadmm_handle h, const tadmm_densebn_desc* d, void* stream);
 int tadmm_densebn_bwd(tadmm_handle h, const tadmm_densebn_desc* d, void* stream);

@@ -64,8 +64,39 @@ def test_descriptor_size_fits_and_workspace():
     dsc.dtype = _cabi.CHAIN_F32
     assert lib.tadmm_bnact_workspace_bytes(C.byref(dsc), None) == -1
     assert lib.tadmm_bnact_workspace_bytes(None, C.byref(C.c_size_t())) == -1
+    assert lib.tadmm_bnact_plan(C.byref(dsc), None) == -1 and lib.tadmm_bnact_plan(None, (C.c_int32 * 3)()) == -1
+    dsc.dtype = 7
+    assert lib.tadmm_bnact_plan(C.byref(dsc), (C.c_int32 * 3)()) == -1
+    dsc.dtype = _cabi.CHAIN_F32
     dsc.N, dsc.H, dsc.W = 2 ** 15, 2 ** 8, 2 ** 8
     assert lib.tadmm_bnact_workspace_bytes(C.byref(dsc), C.byref(C.c_size_t())) == -5
+    assert lib.tadmm_bnact_plan(C.byref(dsc), (C.c_int32 * 3)()) == -5
+
+
+def test_plan_query():
+    """`tadmm_bnact_plan`: S splits of `span` values, span a whole number of trips, `cap` what the workspace holds."""
+    plan = ops.bnact_plan
+    for shape in ((0, 1, 1, 1), (1, 0, 1, 1), (1, 1, -1, 1), (1, 1, 1, 0)):
+        with pytest.raises(_cabi.TadmmError):
+            plan(*shape)
+    assert plan(1, 1, 1, 1) == dict(S=1, span=1024, cap=1)
+    assert plan(128, 16, 32, 32) == dict(S=128, span=1024, cap=128)                 # the CIFAR stem: a split per trip
+    assert plan(128, 16, 32, 32, torch.bfloat16) == dict(S=64, span=2048, cap=64)
+    assert plan(2, 2048, 7, 7) == dict(S=1, span=1024, cap=1)
+    assert plan(15, 2048, 12, 12) == dict(S=1, span=3072, cap=1)                    # one workgroup walks three trips
+    assert plan(15, 2048, 12, 12, torch.bfloat16) == dict(S=1, span=4096, cap=1)
+    assert plan(9, 1, 256, 257) == dict(S=116, span=5120, cap=128)                  # 579 trips, 5 to a split: 116 of 128
+    assert plan(32, 64, 56, 56) == dict(S=25, span=4096, cap=32)                    # 98 trips, 4 to a split
+    assert plan(8, 3, 7, 7, torch.float16) == plan(8, 3, 7, 7, torch.bfloat16) == dict(S=1, span=2048, cap=1)
+    for dt, trip in ((torch.float32, 1024), (torch.bfloat16, 2048), (torch.float16, 2048)):
+        for n, c, h, w in ((1, 1, 1, 1), (7, 3, 33, 70), (128, 64, 8, 8), (32, 32, 112, 112), (5, 2000, 9, 1363),
+                           (300, 1, 64, 64), (3, 40, 200, 31), (65, 2, 32, 32), (130, 2, 32, 32)):
+            p, m = plan(n, c, h, w, dt), n * h * w
+            trips = -(-m // trip)
+            assert p["cap"] == min(trips, 128, -(-2048 // c)) and 1 <= p["S"] <= p["cap"], (n, c, h, w, p)
+            assert p["span"] % trip == 0 and p["S"] * p["span"] >= m > (p["S"] - 1) * p["span"]   # covered, none empty
+            assert p["span"] // trip == -(-trips // p["cap"])                                      # evened out
+            assert c * p["cap"] * 16 <= ops.bnact_workspace_bytes(n, c, h, w, dt)
 
 
 def test_launch_entries_refuse_before_launching():

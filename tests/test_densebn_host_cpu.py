@@ -70,9 +70,37 @@ def test_descriptor_size_fits_and_workspace():
     assert lib.tadmm_densebn_workspace_bytes(None, C.byref(C.c_size_t())) == -1
     dsc.nseg = MAX_SEG + 1
     assert lib.tadmm_densebn_workspace_bytes(C.byref(dsc), C.byref(C.c_size_t())) == -1
+    assert lib.tadmm_densebn_plan(C.byref(dsc), (C.c_int32 * 3)()) == -1
     dsc.nseg = 1
+    assert lib.tadmm_densebn_plan(C.byref(dsc), None) == -1 and lib.tadmm_densebn_plan(None, (C.c_int32 * 3)()) == -1
+    dsc.dtype = 7
+    assert lib.tadmm_densebn_plan(C.byref(dsc), (C.c_int32 * 3)()) == -1
+    dsc.dtype = _cabi.CHAIN_F32
     dsc.N, dsc.H, dsc.W = 2 ** 15, 2 ** 8, 2 ** 8
     assert lib.tadmm_densebn_workspace_bytes(C.byref(dsc), C.byref(C.c_size_t())) == -5
+    assert lib.tadmm_densebn_plan(C.byref(dsc), (C.c_int32 * 3)()) == -5
+
+
+def test_plan_query():
+    """`tadmm_densebn_plan`: bnact's plan for the channels of the descriptor, however they are cut into segments -- one
+    segment for its statistics launch, all of them for the consumer."""
+    plan = ops.densebn_plan
+    for args in ((0, (1,), 1, 1), (1, (0,), 1, 1), (1, (2, -1), 1, 1), (1, (1,), -1, 1), (1, (1,), 1, 0), (1, (), 1, 1),
+                 (2, (1,) * (MAX_SEG + 1), 4, 4)):
+        with pytest.raises(_cabi.TadmmError):
+            plan(*args)
+    assert plan(1, (1,), 1, 1) == dict(S=1, span=1024, cap=1)
+    assert plan(4, (5, 3, 3), 24, 24) == dict(S=3, span=1024, cap=3)                # a split per trip
+    assert plan(15, (1024, 512, 512), 12, 12) == dict(S=1, span=3072, cap=1)        # the consumer: three trips in one split
+    assert plan(15, (1024,), 12, 12) == dict(S=2, span=2048, cap=2)                 # the statistics of its segments
+    assert plan(15, (512,), 12, 12) == dict(S=3, span=1024, cap=3)
+    assert plan(65, (1, 1), 32, 32) == dict(S=65, span=1024, cap=65)
+    assert plan(130, (1, 1), 32, 32, torch.bfloat16) == dict(S=65, span=2048, cap=65)
+    for n, chans, h, w in ((1, (1,), 1, 1), (128, (16,), 32, 32), (128, (8, 4, 4), 32, 32), (2, (2048,), 7, 7),
+                           (2, (1024, 512, 512), 7, 7), (32, (64,), 56, 56), (9, (1,), 256, 257), (5, (1, 1, 1), 1, 1),
+                           (8, (5, 3, 3), 7, 7), (2, (1,) * MAX_SEG, 4, 4)):
+        for dt in (torch.float32, torch.bfloat16, torch.float16):
+            assert plan(n, chans, h, w, dt) == ops.bnact_plan(n, sum(chans), h, w, dt)
 
 
 def test_launch_entries_refuse_before_launching():
