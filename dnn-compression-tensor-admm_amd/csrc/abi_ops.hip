@@ -724,6 +724,7 @@ int tadmm_dgemm_tile_f64(tadmm_handle h, int nprob, const tadmm_dgemm_tile_prob*
   hipStream_t s = (hipStream_t)stream_;
   std::vector<DgemmDesc> descs((size_t)nprob);
   std::vector<BlockRef> map;
+  std::vector<TileProb> tiles;
   for (int i = 0; i < nprob; ++i) {
     const tadmm_dgemm_tile_prob& q = probs[i];
     DgemmDesc& g = descs[(size_t)i];
@@ -735,8 +736,10 @@ int tadmm_dgemm_tile_f64(tadmm_handle h, int nprob, const tadmm_dgemm_tile_prob*
     g.tiles_m = q.M / 32; g.tiles_n = q.N / 32; g.mode = q.mode;
     g.coef = q.coef; g.theta = q.theta; g.rowpart = q.rowpart; g.gate = q.gate; g.gate_min = q.gate_min;
     const int nb = (int)dgemm_tile_blocks(q, tile_m, tile_n, axpby);
-    for (int b = 0; b < nb; ++b) map.push_back(BlockRef{i, b});
+    if (axpby) for (int b = 0; b < nb; ++b) map.push_back(BlockRef{i, b});
+    else tiles.push_back(TileProb{q.M, q.N, q.K, tile_m, tile_n});
   }
+  if (!axpby) map = tile_map_build(tiles);        // the order the filter gives these launches (host.h)
   DgemmDesc* gd = (DgemmDesc*)scratch;
   BlockRef* md = (BlockRef*)((char*)scratch + align_up((size_t)nprob * sizeof(DgemmDesc), 256));
   HIP_OK(h, hipMemcpyAsync(gd, descs.data(), descs.size() * sizeof(DgemmDesc), hipMemcpyHostToDevice, s));
@@ -747,6 +750,26 @@ int tadmm_dgemm_tile_f64(tadmm_handle h, int nprob, const tadmm_dgemm_tile_prob*
   HIP_OK(h, hipStreamSynchronize(s));
   HIP_OK(h, hipGetLastError());
   return TADMM_OK;
+}
+
+// The block map the filter and tadmm_dgemm_tile_f64 give a grouped tile product (host.h: tile_map_build), host only.
+int64_t tadmm_tile_map(int nprob, const tadmm_tile_map_prob* probs, int32_t* map_out, int64_t capacity, double* cost_out) {
+  if (nprob <= 0 || nprob > 4096 || !probs) return TADMM_ERR_INVALID;
+  std::vector<TileProb> t((size_t)nprob);
+  int64_t blocks = 0;
+  for (int i = 0; i < nprob; ++i) {
+    const tadmm_tile_map_prob& q = probs[i];
+    if (q.M <= 0 || q.N <= 0 || q.K <= 0 || q.tile_m <= 0 || q.tile_n <= 0) return TADMM_ERR_INVALID;
+    t[(size_t)i] = TileProb{q.M, q.N, q.K, q.tile_m, q.tile_n};
+    blocks += (int64_t)tile_rows(t[(size_t)i]) * tile_cols(t[(size_t)i]);
+    if (blocks > (1 << 24)) return TADMM_ERR_INVALID;
+  }
+  if (!map_out && !cost_out) return blocks;
+  if (map_out && capacity < blocks) return TADMM_ERR_WORKSPACE;
+  const std::vector<BlockRef> m = tile_map_build(t);
+  if (map_out) memcpy(map_out, m.data(), m.size() * sizeof(BlockRef));
+  if (cost_out) { cost_out[0] = tile_map_cost(m, t); cost_out[1] = tile_map_cost(tile_map_plain(t), t); }
+  return blocks;
 }
 
 }  // extern "C"

@@ -209,6 +209,7 @@ static inline void filter_layout(FilterGroup& fg, const std::vector<FilterSpec>&
   std::vector<DgemmDesc> d_cgram;
   std::vector<CholDesc> c_comp;
   std::vector<BlockRef> m_cform, m_cgram, m_cemit, m_csolve;
+  std::vector<TileProb> t_stage0, t_gram, t_verify, t_cgram;      // populations of the launch_dgemm_nt64 maps
   fg.ncomp = 0; fg.comp_npad_max = 0;
   const size_t zero_begin = align_up(ar.off, 256);
   std::vector<size_t> xth_off(nf), vh_offs(nf);
@@ -224,7 +225,7 @@ static inline void filter_layout(FilterGroup& fg, const std::vector<FilterSpec>&
     const int rp = sp.rp, Npad = sp.Npad, r32 = (int)align_up(sp.r, 32), ldy = Npad, ldh = (int)align_up(rp, 128);
     const int TNW = filter_tile_n();
     const int TMW = fg.tile_m;
-    const int tn = (Npad + TNW - 1) / TNW, tr = (rp + TMW - 1) / TMW;      // TMW x TNW tiles of the NT products with G
+    const int tn = (Npad + TNW - 1) / TNW;                                 // TMW x TNW tiles of the NT products with G
     size_t ring_off[3];
     for (auto& o : ring_off) o = ar.take((size_t)rp * ldy * 8);
     const size_t st_off = ar.take(sizeof(FiltState));
@@ -384,7 +385,7 @@ static inline void filter_layout(FilterGroup& fg, const std::vector<FilterSpec>&
       c.gate = w_alive; c.gate_min = 1;
       c_comp.push_back(c);
       for (int b = 0; b < (cr + 3) / 4; ++b) { m_cform.push_back(BlockRef{ci, b}); m_cemit.push_back(BlockRef{ci, b}); }
-      for (int b = 0; b < ((cr + TMW - 1) / TMW) * ((cr + TNW - 1) / TNW); ++b) m_cgram.push_back(BlockRef{ci, b});
+      t_cgram.push_back(TileProb{cr, cr, Npad, TMW, TNW});
       for (int b = 0; b < Npad / kCholStrip; ++b) m_csolve.push_back(BlockRef{ci, b});
     }
 
@@ -403,16 +404,25 @@ static inline void filter_layout(FilterGroup& fg, const std::vector<FilterSpec>&
     // block maps
     const int el_blocks = (int)(((size_t)rp * ldy + 1023) / 1024);
     for (int b = 0; b < el_blocks; ++b) { m_init.push_back(BlockRef{i, b}); m_axpby.push_back(BlockRef{i, b}); }
-    for (int b = 0; b < tr * tn; ++b) m_stage0.push_back(BlockRef{i, b});
+    t_stage0.push_back(TileProb{rp, Npad, Npad, TMW, TNW});
     for (int b = 0; b < (rp / 32) * ((Npad + 63) / 64); ++b) m_fast.push_back(BlockRef{i, b});   // dgemm3: 32 x 64 tiles
     for (int b = 0; b < (gnt * gks + 3) / 4; ++b) m_gp.push_back(BlockRef{i, b});
-    for (int b = 0; b < tr * ((rp + TNW - 1) / TNW); ++b) { m_gram.push_back(BlockRef{i, b}); m_hform.push_back(BlockRef{i, b}); }
+    t_gram.push_back(TileProb{rp, rp, Npad, TMW, TNW});
     for (int b = 0; b < (r32 / 32) * (Npad / 32); ++b) m_uform.push_back(BlockRef{i, b});     // NN kernel: 32x32 tiles
-    for (int b = 0; b < ((r32 + TMW - 1) / TMW) * tn; ++b) m_verify.push_back(BlockRef{i, b});
+    t_verify.push_back(TileProb{r32, Npad, Npad, TMW, TNW});
     for (int b = 0; b < (sp.r + 3) / 4; ++b) m_emit.push_back(BlockRef{i, b});
     for (int b = 0; b < Npad / kCholStrip; ++b) m_solve.push_back(BlockRef{i, b});
     (void)vh_off;
   }
+  // the maps of the tile products, Grams and the verification: XCD-aware tile order (host.h: tile_map_build); the maps of
+  // one population come out equal, so a panel of G is consumed next to the same L2 in every product launch of the level
+  const bool by_problem = getenv("TADMM_FILTER_XCD") && atoi(getenv("TADMM_FILTER_XCD"));
+  auto tile_map = [&](const std::vector<TileProb>& t) { return by_problem ? tile_map_plain(t) : tile_map_build(t); };
+  m_stage0 = tile_map(t_stage0);
+  m_gram = tile_map(t_gram);
+  m_hform = m_gram;
+  m_verify = tile_map(t_verify);
+  m_cgram = tile_map(t_cgram);
   if (const char* e = getenv("TADMM_FILTER_XCD"); e && atoi(e)) {
     std::vector<double> wk(nf);
     for (int i = 0; i < nf; ++i) wk[i] = specs[i].Npad;          // cost of a block ~ its reduction length

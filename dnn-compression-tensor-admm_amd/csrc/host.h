@@ -1,7 +1,7 @@
 // Host-side pieces shared by the plan builders (plan.hip: TT / SVD projection, tucker_plan.hip: Tucker-2) and the
 // stand-alone entries (abi_ops.hip): the context object behind tadmm_handle, error macros, the two-pass workspace
 // arena and its placement helpers, the geometry of one eigen-problem, the XCD-aware block order of the Jacobi
-// tournament, and the layout and driver loop of one grouped eigen-solve.
+// tournament and of the grouped tile products, and the layout and driver loop of one grouped eigen-solve.
 #pragma once
 #include "common.h"
 
@@ -252,6 +252,119 @@ static inline void xcd_by_key(std::vector<BlockRef>& m, KeyFn key) {
     out.push_back(bin[x][head[x]++]);
   }
   m.swap(out);
+}
+
+// ---- Grouped NT tile products (dgemm_nt_tile_kernel): which tile runs next to which L2 ----
+// One problem of a grouped launch: C[M][N] = A[M][K] * B[N][K]^T in TM x TN tiles.  A tile (tm, tn) streams one TM-row
+// panel of A (the block image Y) and one TN-row panel of B (G); the plain map is problem-major with tn fastest, so with
+// blocks dealt round-robin over the eight XCDs nearly every L2 fetches nearly every panel of a problem.
+struct TileProb { int M, N, K, TM, TN; };
+static inline int tile_rows(const TileProb& q) { return (q.M + q.TM - 1) / q.TM; }
+static inline int tile_cols(const TileProb& q) { return (q.N + q.TN - 1) / q.TN; }
+
+// TADMM_XCD_MAP=0: plain order (as for the other maps here).  TADMM_TILE_MAP: 0 plain order for these maps alone, 1 the
+// band height with the smaller modelled traffic (default), 2 whole columns (h = tiles_m: one owner slot per G panel).
+// TADMM_TILE_MAP_LONGEST=0: the runs of a slot queue in problem order instead of longest K first.  (A/B measurements.)
+static inline int tile_map_mode() {
+  const char* e = getenv("TADMM_XCD_MAP");
+  if (e && !atoi(e)) return 0;
+  const char* b = getenv("TADMM_TILE_MAP");
+  return b ? std::max(0, std::min(2, atoi(b))) : 1;
+}
+
+static inline std::vector<BlockRef> tile_map_plain(const std::vector<TileProb>& probs) {
+  std::vector<BlockRef> m;
+  for (int p = 0; p < (int)probs.size(); ++p)
+    for (int b = 0; b < tile_rows(probs[p]) * tile_cols(probs[p]); ++b) m.push_back(BlockRef{p, b});
+  return m;
+}
+
+// Modelled operand traffic of one launch, bytes: position i of the map belongs to XCD slot i % 8, and every slot fetches
+// each distinct (problem, A panel) and (problem, B panel) among its tiles once -- no reuse between slots, none lost
+// inside one.
+static inline double tile_map_cost(const std::vector<BlockRef>& map, const std::vector<TileProb>& probs) {
+  std::vector<int> off(probs.size() + 1, 0);
+  for (size_t p = 0; p < probs.size(); ++p) off[p + 1] = off[p] + tile_rows(probs[p]) + tile_cols(probs[p]);
+  std::vector<char> seen((size_t)8 * off.back(), 0);
+  double bytes = 0;
+  for (size_t i = 0; i < map.size(); ++i) {
+    const TileProb& q = probs[map[i].prob];
+    const int tn = tile_cols(q), tr = tile_rows(q), r = map[i].local / tn, c = map[i].local - r * tn;
+    char* s = seen.data() + (i & 7) * (size_t)off.back() + off[map[i].prob];
+    if (!s[r]) { s[r] = 1; bytes += 8.0 * q.TM * q.K; }
+    if (!s[tr + c]) { s[tr + c] = 1; bytes += 8.0 * q.TN * q.K; }
+  }
+  return bytes;
+}
+
+// A problem's tiles in bands of about h tile rows, column by column inside a band, the bands in alternating column
+// direction: every stretch of the list is a compact patch of the (tm, tn) grid.
+static inline std::vector<int> tile_band_order(int tr, int tn, int h) {
+  std::vector<int> l;
+  l.reserve((size_t)tr * tn);
+  const int nb = (tr + h - 1) / h;
+  for (int b = 0; b < nb; ++b) {
+    const int r0 = b * tr / nb, r1 = (b + 1) * tr / nb;
+    for (int k = 0; k < tn; ++k) {
+      const int c = (b & 1) ? tn - 1 - k : k;
+      for (int r = r0; r < r1; ++r) l.push_back(r * tn + c);
+    }
+  }
+  return l;
+}
+
+// The map of a grouped launch, ordered so that position i belongs to XCD slot i % 8 (blocks i, i + 8, .. are observed to
+// share an XCD; placement is a speed matter only, no result depends on it).  A permutation of the plain map.
+//  - Every problem is cut into eight runs of its band order, run j for slot j: a slot sees a compact patch of every
+//    problem (few distinct panels), every problem runs on all eight XCDs, and the slot of a patch depends on the
+//    problem's own grid alone -- the panels of G meet the same L2 in every launch of a level.
+//  - Runs differ by at most one tile; the odd tiles go to the slots after the one the previous problem stopped at, which
+//    keeps the eight queues at the lengths the positions i % 8 give them (no padding entries).
+//  - The band height of a problem is the one whose runs touch the fewest panel bytes (ties: the taller band).
+//  - A slot's queue holds its runs longest K first: the short tiles fill in behind the long ones of the same XCD.
+// The plain map is returned where the model says the order gains nothing.
+static inline std::vector<BlockRef> tile_map_build(const std::vector<TileProb>& probs) {
+  const int mode = tile_map_mode();
+  std::vector<BlockRef> plain = tile_map_plain(probs);
+  if (mode == 0) return plain;
+  const int np = (int)probs.size();
+  std::vector<std::vector<BlockRef>> run((size_t)np * 8);
+  int fill = 0;                                  // slots [0, fill) are one tile ahead of the others
+  for (int p = 0; p < np; ++p) {
+    const TileProb& q = probs[p];
+    const int tr = tile_rows(q), tn = tile_cols(q), n = tr * tn;
+    int cnt[8];
+    for (int x = 0; x < 8; ++x) cnt[x] = n / 8;
+    for (int k = 0; k < n % 8; ++k) ++cnt[(fill + k) & 7];
+    fill = (fill + n) & 7;
+    std::vector<int> best;
+    double best_cost = 0;
+    for (int h = (mode == 2 ? tr : 1); h <= tr; ++h) {
+      std::vector<int> l = tile_band_order(tr, tn, h);
+      double cost = 0;
+      for (int x = 0, i = 0; x < 8; i += cnt[x++]) {
+        std::vector<char> seen((size_t)tr + tn, 0);
+        for (int k = i; k < i + cnt[x]; ++k) {
+          const int r = l[k] / tn, c = l[k] - r * tn;
+          if (!seen[r]) { seen[r] = 1; cost += q.TM; }
+          if (!seen[tr + c]) { seen[tr + c] = 1; cost += q.TN; }
+        }
+      }
+      if (best.empty() || cost <= best_cost) { best.swap(l); best_cost = cost; }
+    }
+    for (int x = 0, i = 0; x < 8; i += cnt[x++])
+      for (int k = i; k < i + cnt[x]; ++k) run[(size_t)p * 8 + x].push_back(BlockRef{p, best[k]});
+  }
+  std::vector<int> order(np);
+  for (int p = 0; p < np; ++p) order[p] = p;
+  if (const char* e = getenv("TADMM_TILE_MAP_LONGEST"); !(e && !atoi(e)))
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return probs[a].K > probs[b].K; });
+  std::vector<BlockRef> queue[8];
+  for (int x = 0; x < 8; ++x)
+    for (int p : order) queue[x].insert(queue[x].end(), run[(size_t)p * 8 + x].begin(), run[(size_t)p * 8 + x].end());
+  std::vector<BlockRef> out(plain.size());
+  for (size_t i = 0; i < out.size(); ++i) out[i] = queue[i & 7][i >> 3];
+  return tile_map_cost(out, probs) <= tile_map_cost(plain, probs) ? out : plain;
 }
 
 // Which tick kernel a group of problems uses.

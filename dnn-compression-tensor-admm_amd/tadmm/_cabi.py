@@ -117,6 +117,11 @@ class DgemmTileProb(C.Structure):
     ]
 
 
+class TileMapProb(C.Structure):
+    """tadmm_tile_map_prob: sizes and tile shape of one problem of a grouped tile product (host-only map builder)."""
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("tile_m", C.c_int32), ("tile_n", C.c_int32)]
+
+
 TTM_MAX_D = 4
 
 
@@ -463,6 +468,8 @@ ABI = {
     "tadmm_dgemm_tile_scratch_bytes": (C.c_size_t, [C.c_int, C.POINTER(DgemmTileProb)]),
     "tadmm_dgemm_tile_f64": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(DgemmTileProb), C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tadmm_tile_map": (C.c_int64, [C.c_int, C.POINTER(TileMapProb), C.POINTER(C.c_int32), C.c_int64,
+                                   C.POINTER(C.c_double)]),
     "tadmm_cholqr_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "tadmm_cholqr_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                    C.POINTER(C.c_int), C.c_void_p]),

@@ -1161,6 +1161,24 @@ def dgemm_tile(probs, tile_m: int, tile_n: int, axpby: bool = False, device=None
                                        scratch.numel(), _stream(device)))
 
 
+def tile_map(probs):
+    """The block map of one grouped tile product on `probs`, a list of (M, N, K, tile_m, tile_n), as the filter and
+    `dgemm_tile` build it (csrc/host.h `tile_map_build`): a list of (prob, local), position i expected on XCD i % 8,
+    with the modelled operand bytes of that map and of the problem-major order.  Host only, no device."""
+    import ctypes as C
+    from . import _cabi
+    lib = _cabi.load()
+    arr = (_cabi.TileMapProb * len(probs))(*[_cabi.TileMapProb(*map(int, p)) for p in probs])
+    n = lib.tadmm_tile_map(len(probs), arr, None, 0, None)
+    if n < 0:
+        raise ValueError(f"tadmm_tile_map refuses {probs!r}: status {n}")
+    out = (C.c_int32 * (2 * n))()
+    cost = (C.c_double * 2)()
+    got = lib.tadmm_tile_map(len(probs), arr, out, n, cost)
+    assert got == n, (got, n)
+    return [(out[2 * i], out[2 * i + 1]) for i in range(n)], float(cost[0]), float(cost[1])
+
+
 def dgemm3(a: torch.Tensor, g: torch.Tensor, repeats: int = 1) -> torch.Tensor:
     """a (M, N) @ g (N, N)^T at fp32 accuracy on the bf16 matrix cores (float64 in / out): the product the early
     stages of the filtered eigen-solver use (csrc/dgemm3.hip)."""

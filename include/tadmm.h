@@ -1172,6 +1172,15 @@ int tadmm_dgemm_tile_check(int nprob, const tadmm_dgemm_tile_prob* probs, int ti
 size_t tadmm_dgemm_tile_scratch_bytes(int nprob, const tadmm_dgemm_tile_prob* probs);
 int tadmm_dgemm_tile_f64(tadmm_handle h, int nprob, const tadmm_dgemm_tile_prob* probs, int tile_m, int tile_n, int axpby,
                          void* scratch, size_t scratch_bytes, void* stream);
+/* Host only, no device needed: the block map that the filter and tadmm_dgemm_tile_f64 give one grouped launch of the tile
+ * product on `nprob` problems C[M][N] = A[M][K] * B[N][K]^T in tile_m x tile_n tiles.  Position i of the map is
+ * (prob, local) = (map_out[2i], map_out[2i + 1]) with local = tm * ceil(N / tile_n) + tn, and is expected on XCD i % 8:
+ * a permutation of the problem-major order that keeps the tiles of one slot on few operand panels (csrc/host.h).
+ * Returns the number of blocks (map_out and cost_out both NULL: only that), TADMM_ERR_WORKSPACE when `capacity`
+ * (entries) is smaller, TADMM_ERR_INVALID for non-positive sizes.  cost_out[0] is the modelled operand traffic of the
+ * map in bytes, cost_out[1] that of the problem-major order.  Honours TADMM_XCD_MAP / TADMM_TILE_MAP like the plans. */
+typedef struct { int32_t M, N, K, tile_m, tile_n; } tadmm_tile_map_prob;
+int64_t tadmm_tile_map(int nprob, const tadmm_tile_map_prob* probs, int32_t* map_out, int64_t capacity, double* cost_out);
 
 #ifdef __cplusplus
 }
