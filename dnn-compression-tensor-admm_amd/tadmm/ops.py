@@ -322,8 +322,9 @@ class GemmBatch:
         rc = lib.tadmm_gemm_pack(n, arr, host.data_ptr(), nbytes, C.byref(nblocks))
         if rc < 0:
             raise TadmmError(rc, "tadmm_gemm_pack: invalid GEMM descriptor (each operand needs one unit stride)")
-        self.blob = host.to(device, non_blocking=True)
-        self._host = host
+        # a blocking copy: `run()` may be called under any stream and the caller holds no tensor to wait on, so the blob is
+        # valid for every stream when the constructor returns (what the native `*_plan_create` entries keep)
+        self.blob = host.to(device, non_blocking=False)
         self.n, self.nblocks = n, int(nblocks.value)
 
     def run(self):
