@@ -1,5 +1,6 @@
 """What the TT, Tucker and SVD layer files share: the bias constructor, the dense convolution of the R variants and the
-eligibility test of the fused linear chain."""
+eligibility test of the fused linear chain -- and what the model files share: the local state-dict loader and the body
+of their factories."""
 from __future__ import annotations
 
 import torch
@@ -48,6 +49,31 @@ class DenseConvMixin:
 
     def forward(self, x):
         return self._conv_forward(x, self._recover_weight())
+
+
+def _local_state_dict(path, what):
+    if path is None:
+        raise ValueError(f"{what}: give the dense state dict as dense_dict= or a local file as path=; nothing is downloaded")
+    if str(path).startswith('http'):
+        raise ValueError(f"{what}: path is a URL ({path}); nothing is downloaded -- fetch the file and pass its local path")
+    return torch.load(path, map_location='cpu')
+
+
+def create_model(name, build, hp_dict, decompose, pretrained, path, dense_dict, load_with_decompose=False):
+    """The body of every model factory `name(hp_dict, decompose, pretrained, path, dense_dict, **kwargs)`.
+    `build(hp_dict=, dense_dict=)` makes the model: with `decompose` it factorises the dense state dict given as
+    `dense_dict` (or saved at the local `path`), without it `dense_dict` is ignored.  `pretrained` then loads a
+    compressed state dict from the local `path` -- only without `decompose`, unless `load_with_decompose` says that
+    this factory of the reference loads it either way."""
+    if decompose:
+        if dense_dict is None:
+            dense_dict = _local_state_dict(path, name + "(decompose=True)")
+    else:
+        dense_dict = None
+    model = build(hp_dict=hp_dict, dense_dict=dense_dict)
+    if pretrained and (load_with_decompose or not decompose):
+        model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
+    return model
 
 
 def fused_linear_ok(x, bias, params, rank: int, in_features: int, out_features: int) -> bool:

@@ -26,7 +26,7 @@ from . import functional as HF
 from .functional import DenseFeatures
 from .tk_layers import TKConv2dC, TKConv2dM, TKConv2dR
 from .tt_layers import TTConv2dM, TTConv2dR
-from .vit_layers import _local_state_dict
+from ._layer_common import _local_state_dict
 
 
 def _conv(conv, hp_dict, dense_dict, w_name, in_planes, planes, kernel_size, padding):

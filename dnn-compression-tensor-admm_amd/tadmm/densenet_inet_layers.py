@@ -16,6 +16,7 @@ composed route (torch.cat inside the checkpoint).  Nothing is ever downloaded: w
 pretrained dense model (`decompose=True, pretrained=True`), the dense state dict comes from `dense_dict=` or a local file.
 No rank table ships for densenet264; its factory takes the caller's `hp_dict`."""
 from collections import OrderedDict
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -26,7 +27,7 @@ from . import functional as HF
 from .functional import DenseFeatures
 from .svd_layers import SVDConv2dC
 from .tk_layers import TKConv2dC
-from .vit_layers import _local_state_dict
+from ._layer_common import create_model
 
 
 class BatchNormAct2d(nn.BatchNorm2d):
@@ -295,16 +296,8 @@ def _ten_densenet(growth_rate=32, block_config=(6, 12, 24, 16), num_classes=1000
 
 def _factory(name, growth_rate, block_config):
     def create(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, **kwargs):
-        if decompose:
-            if dense_dict is None:
-                dense_dict = _local_state_dict(path, name + "(decompose=True)")
-        else:
-            dense_dict = None
-        model = _ten_densenet(growth_rate=growth_rate, block_config=block_config, conv=TKConv2dC, hp_dict=hp_dict,
-                              dense_dict=dense_dict, **kwargs)
-        if pretrained and not decompose:
-            model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
-        return model
+        build = partial(_ten_densenet, growth_rate=growth_rate, block_config=block_config, conv=TKConv2dC, **kwargs)
+        return create_model(name, build, hp_dict, decompose, pretrained, path, dense_dict)
     create.__name__ = create.__qualname__ = name
     create.__doc__ = (f"densenet_inet_tt.py: {name}(hp_dict, decompose=False, pretrained=False, path=None, **kwargs): growth "
                       f"{growth_rate}, blocks {block_config}.  decompose=True factorises the dense state dict given as "

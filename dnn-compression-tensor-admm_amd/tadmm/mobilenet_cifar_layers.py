@@ -13,6 +13,7 @@ nn.Conv2d.  Nothing is ever downloaded: a dense state dict comes from `dense_dic
 Deviation: no shipped table lists a depthwise kernel (`bottlenecks.i.conv2.weight`), and the reference builds conv2 as
 nn.Conv2d whatever the table says; a table that lists one is refused here with a ValueError instead of being ignored."""
 import math
+from functools import partial
 
 import torch.nn as nn
 import torch.nn.functional as F
@@ -20,7 +21,7 @@ import torch.nn.functional as F
 from . import functional as HF
 from .svd_layers import SVDConv2dC, SVDConv2dM, SVDConv2dR
 from .tk_layers import TKConv2dC, TKConv2dM, TKConv2dR
-from .vit_layers import _local_state_dict
+from ._layer_common import create_model
 
 
 def _pointwise(conv, hp_dict, dense_dict, w_name, inp, oup):
@@ -129,15 +130,8 @@ def _tt_mobilenetv2_cifar(num_classes=10, conv=TKConv2dC, hp_dict=None, dense_di
 
 def _factory(name, conv, always):
     def create(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, **kwargs):
-        if decompose:
-            if dense_dict is None:
-                dense_dict = _local_state_dict(path, name + "(decompose=True)")
-        else:
-            dense_dict = None
-        model = _tt_mobilenetv2_cifar(conv=conv, hp_dict=hp_dict, dense_dict=dense_dict, **kwargs)
-        if pretrained and (always or not decompose):
-            model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
-        return model
+        return create_model(name, partial(_tt_mobilenetv2_cifar, conv=conv, **kwargs), hp_dict, decompose, pretrained,
+                            path, dense_dict, load_with_decompose=always)
     create.__name__ = create.__qualname__ = name
     create.__doc__ = (f"mobilenetv2_cifar_tt.py: {name}(hp_dict, decompose=False, pretrained=False, path=None, "
                       "dense_dict=None, **kwargs).  decompose=True factorises the dense state dict given as dense_dict= (or "

@@ -18,6 +18,7 @@ Deviations: a table that lists a depthwise kernel is refused with a ValueError (
 factorised class, which raises there too); `decompose=True, pretrained=True`, where the reference downloads timm's
 `mobilenetv2_100`, wants `dense_dict=` or a local `path`: nothing is downloaded."""
 import math
+from functools import partial
 
 import torch.nn as nn
 
@@ -25,7 +26,7 @@ from . import functional as HF
 from .svd_layers import SVDConv2dC, SVDConv2dM
 from .tk_layers import TKConv2dC
 from .tt_layers import TTConv2dR
-from .vit_layers import _local_state_dict
+from ._layer_common import create_model
 
 
 def _make_divisible(v, divisor, min_value=None):
@@ -172,19 +173,12 @@ def _tt_mobilenetv2(conv, hp_dict, dense_dict=None, **kwargs):
 
 def _factory(name, conv):
     def create(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, **kwargs):
-        if decompose:
-            if dense_dict is None:
-                if pretrained and path is None:
-                    raise ValueError(f"{name}(decompose=True, pretrained=True): the reference downloads timm's "
-                                     "mobilenetv2_100 here; nothing is downloaded -- give the dense state dict as "
-                                     "dense_dict= or a local file as path=")
-                dense_dict = _local_state_dict(path, name + "(decompose=True)")
-        else:
-            dense_dict = None
-        model = _tt_mobilenetv2(conv=conv, hp_dict=hp_dict, dense_dict=dense_dict, **kwargs)
-        if pretrained and not decompose:
-            model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
-        return model
+        if decompose and dense_dict is None and pretrained and path is None:
+            raise ValueError(f"{name}(decompose=True, pretrained=True): the reference downloads timm's "
+                             "mobilenetv2_100 here; nothing is downloaded -- give the dense state dict as "
+                             "dense_dict= or a local file as path=")
+        return create_model(name, partial(_tt_mobilenetv2, conv=conv, **kwargs), hp_dict, decompose, pretrained, path,
+                            dense_dict)
     create.__name__ = create.__qualname__ = name
     create.__doc__ = (f"mobilenetv2_tt.py: {name}(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, "
                       "**kwargs).  decompose=True factorises the dense state dict given as dense_dict= (or saved at the "

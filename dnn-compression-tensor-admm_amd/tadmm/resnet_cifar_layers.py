@@ -13,6 +13,8 @@ the others are nn.Conv2d.  Nothing is ever downloaded: a dense state dict comes 
 Deliberate deviation: the reference's `TTBasicBlock.forward_flops` feeds the block input, not conv1's output, to a dense
 conv2 and counts conv2's weights for a dense conv1 (resnet_cifar_tt.py:112-125); here each convolution is fed and
 counted as itself."""
+from functools import partial
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -22,7 +24,7 @@ from . import functional as HF
 from .stf_layers import StfTKConv2dC
 from .tk_layers import TKConv2dC, TKConv2dM, TKConv2dR
 from .tt_layers import TTConv2dM, TTConv2dR
-from .vit_layers import _local_state_dict
+from ._layer_common import create_model
 
 _FLOPS_LAYERS = (TKConv2dC, TKConv2dM, TKConv2dR, TTConv2dM, TTConv2dR)
 
@@ -200,15 +202,9 @@ def _tt_resnet(num_blocks, num_classes=10, conv=TTConv2dR, hp_dict=None, dense_d
 
 def _factory(name, conv, num_blocks):
     def create(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, **kwargs):
-        if decompose:
-            if dense_dict is None:
-                dense_dict = _local_state_dict(path, name + "(decompose=True)")
-        else:
-            dense_dict = None
-        model = _tt_resnet(num_blocks, conv=conv, hp_dict=hp_dict, dense_dict=dense_dict, **kwargs)
-        if pretrained:
-            model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
-        return model
+        # as the reference does, pretrained loads `path` even behind decompose
+        return create_model(name, partial(_tt_resnet, num_blocks, conv=conv, **kwargs), hp_dict, decompose, pretrained,
+                            path, dense_dict, load_with_decompose=True)
     create.__name__ = create.__qualname__ = name
     create.__doc__ = (f"resnet_cifar_tt.py: {name}(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, "
                       "**kwargs).  decompose=True factorises the dense state dict given as dense_dict= (or saved at the "

@@ -10,6 +10,8 @@ and the downsample's own BatchNorm without ReLU.  `conv` is one of TTConv2dR / T
 TKConv2dR and builds the convolutions whose weight name is in `hp_dict.ranks`; the others are nn.Conv2d.  Nothing is ever
 downloaded: where the reference fetches timm's pretrained dense model (`decompose=True, pretrained=True`), the dense
 state dict comes from `dense_dict=` or a local file."""
+from functools import partial
+
 import torch
 import torch.nn as nn
 
@@ -17,7 +19,7 @@ from . import functional as HF
 from .svd_layers import SVDConv2dC, SVDConv2dM
 from .tk_layers import TKConv2dC, TKConv2dM, TKConv2dR
 from .tt_layers import TTConv2dM, TTConv2dR
-from .vit_layers import _local_state_dict
+from ._layer_common import create_model
 
 
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
@@ -276,15 +278,9 @@ def _tt_resnet(block, layers, conv, hp_dict, dense_dict=None, **kwargs):
 
 def _factory(name, conv, block, layers):
     def create(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, **kwargs):
-        if decompose:
-            if dense_dict is None:              # the reference downloads timm's dense model when pretrained is set too
-                dense_dict = _local_state_dict(path, name + "(decompose=True)")
-        else:
-            dense_dict = None
-        model = _tt_resnet(block, layers, conv=conv, hp_dict=hp_dict, dense_dict=dense_dict, **kwargs)
-        if pretrained and not decompose:
-            model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
-        return model
+        # the reference downloads timm's dense model when decompose and pretrained are both set; here `path` is read
+        return create_model(name, partial(_tt_resnet, block, layers, conv=conv, **kwargs), hp_dict, decompose, pretrained,
+                            path, dense_dict)
     create.__name__ = create.__qualname__ = name
     create.__doc__ = (f"resnet_inet_tt.py: {name}(hp_dict, decompose=False, pretrained=False, path=None, dense_dict=None, "
                       "**kwargs).  decompose=True factorises the dense state dict given as dense_dict= (or saved at the "

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as HF
+from ._layer_common import _local_state_dict, create_model  # noqa: F401 (_local_state_dict: the name stays importable here)
 from .tk_layers import TKLinearM, TKLinearR
 from .tt_layers import TTLinearM, TTLinearR
 
@@ -250,25 +251,10 @@ def _tt_vit(patch_size=16, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4, qk
     return model
 
 
-def _local_state_dict(path, what):
-    if path is None:
-        raise ValueError(f"{what}: give the dense state dict as dense_dict= or a local file as path=; nothing is downloaded")
-    if str(path).startswith('http'):
-        raise ValueError(f"{what}: path is a URL ({path}); nothing is downloaded -- fetch the file and pass its local path")
-    return torch.load(path, map_location='cpu')
-
-
 def _factory(name, linear, **arch):
     def create(hp_dict, pretrained=False, decompose=False, path=None, dense_dict=None, **kwargs):
-        if decompose:
-            if dense_dict is None:
-                dense_dict = _local_state_dict(path, name + "(decompose=True)")
-        else:
-            dense_dict = None
-        model = _tt_vit(linear=linear, hp_dict=hp_dict, dense_dict=dense_dict, **{**arch, **kwargs})
-        if pretrained and not decompose:
-            model.load_state_dict(_local_state_dict(path, name + "(pretrained=True)"))
-        return model
+        return create_model(name, partial(_tt_vit, linear=linear, **{**arch, **kwargs}), hp_dict, decompose, pretrained,
+                            path, dense_dict)
     create.__name__ = create.__qualname__ = name
     create.__doc__ = (f"vit_tt.py: {name}(hp_dict, pretrained=False, decompose=False, path=None, dense_dict=None, **kwargs).  "
                       "decompose=True factorises the dense state dict given as dense_dict= (or saved at the local `path`); "
